@@ -6,6 +6,12 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
     python bench.py --height 384 --width 1280 --batch 2    # BASELINE.json configs[2] shape
+    python bench.py --gpus 1 --steps K --warmup W --full   # + calibration, roofline, host-issue time, 384x1280 extra, baselines
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR   # + the last timed step's outputs as DIR/<name>.npy
+
+A plain run sets up, warms up, times the K steps and prints the result line; everything else it can measure (box calibration,
+per-launch roofline passes, host-issue time, the 384x1280 extra workload, the CPU and stock-PyTorch GPU baselines) runs only
+with --full, where the --no-* switches below still leave single parts out.
 
 One "step" = zero_grad -> PackNet01 + PoseNet forward -> multi-view photometric loss (4 scales, SSIM+L1, automask,
 smoothness) -> backward -> (N>1: RCCL gradient all-reduce, overlapped with backward) -> Adam, on a synthetic
@@ -575,9 +581,39 @@ def roofline_of(timed, iso, value, H, W, B, world, ms_per_step, nprof):
     }
 
 
-def run_workload(model, optimizer, H, W, B, steps, warmup, ctx, want_prof=True, layer_table=''):
+DUMP_SAMPLE = 1024          # elements per parameter (and per gradient) in the --dump-outputs sample
+
+
+def dump_outputs(out_dir, out, model):
+    """What the last timed step gave its caller, as out_dir/<name>.npy (float32): the loss, the four inverse-depth maps, the two
+    context poses, and a fixed sample (seeded indices, DUMP_SAMPLE per tensor, in named_parameters order) of the parameters after
+    the Adam update and of their gradients -- about 12 MB at 192x640 batch 4.  Returns the names written."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {'loss': out['loss'].detach().reshape(1)}
+    for i, d in enumerate(out['inv_depths']):
+        arrays['inv_depth_%d' % i] = d.detach()
+    for j, pose in enumerate(out['poses'] or []):
+        arrays['pose_%d' % j] = pose.mat.detach()
+    g = torch.Generator().manual_seed(0)
+    params, grads = [], []
+    for _, p in model.named_parameters():
+        n = p.numel()
+        idx = torch.arange(n) if n <= DUMP_SAMPLE else torch.randint(n, (DUMP_SAMPLE,), generator=g)
+        idx = idx.to(p.device)
+        params.append(p.detach().reshape(-1)[idx])
+        grads.append(p.grad.detach().reshape(-1)[idx] if p.grad is not None else torch.full((idx.numel(),), float('nan'), device=p.device))
+    arrays['params_sample'] = torch.cat(params)
+    arrays['grads_sample'] = torch.cat(grads)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), t.float().cpu().numpy())
+    return sorted(arrays)
+
+
+def run_workload(model, optimizer, H, W, B, steps, warmup, ctx, want_prof=True, layer_table='', full=True, dump_dir=''):
     """W untimed warm-up steps, then exactly K timed steps between barrier + synchronize fences; max over ranks.  Returns the
-    measurement (elapsed seconds, final loss, conv-launch timing of a few extra eager steps)."""
+    measurement (elapsed seconds, final loss; with `full`: clocks, host-issue time and conv-launch timing of a few extra eager
+    steps).  `dump_dir`: rank 0 writes the last timed step's outputs there (dump_outputs) before any extra step runs."""
     from packnet_sfm.hip import functional as HF
     from packnet_sfm.hip import ops
     rank, world, device, ddp = ctx['rank'], ctx['world'], ctx['device'], ctx['ddp']
@@ -588,7 +624,7 @@ def run_workload(model, optimizer, H, W, B, steps, warmup, ctx, want_prof=True, 
         out = model(batch, progress=0.0)
         out['loss'].backward()
         optimizer.step()
-        return out['loss']
+        return out
 
     def fence():
         if ddp:
@@ -602,17 +638,17 @@ def run_workload(model, optimizer, H, W, B, steps, warmup, ctx, want_prof=True, 
     fence()
     step = eager_step
     for _ in range(warmup):
-        loss = step()
+        out = step()
     fence()
     reducer = getattr(optimizer, '_reducer', None)
     if reducer is not None:
         reducer.exposed_reset(True)        # events around the end-of-backward join: all-reduce time NOT hidden behind backward
-    sampler = ClockSampler(device) if rank == 0 else None
+    sampler = ClockSampler(device) if (rank == 0 and full) else None
     if sampler is not None:
         sampler.__enter__()
     t0 = time.perf_counter()
     for _ in range(steps):
-        loss = step()
+        out = step()
     fence()
     elapsed = time.perf_counter() - t0
     if sampler is not None:
@@ -625,10 +661,15 @@ def run_workload(model, optimizer, H, W, B, steps, warmup, ctx, want_prof=True, 
         t = torch.tensor([elapsed], dtype=torch.float64, device=device if dist.get_backend() == 'nccl' else 'cpu')
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    res = {'elapsed': elapsed, 'loss': float(loss.detach().float().item()), 'timed': None, 'iso': None, 'nprof': 3,
+    res = {'elapsed': elapsed, 'loss': float(out['loss'].detach().float().item()), 'timed': None, 'iso': None, 'nprof': 3,
            'clocks': sampler.summary() if sampler is not None else None,
            'exposed_allreduce_ms_per_step': (round(exposed / steps, 4) if exposed is not None else None),
            'host_us_per_collective': (round(host_us, 1) if host_us is not None else None)}
+    if dump_dir and rank == 0:
+        res['dumped'] = dump_outputs(dump_dir, out, model)
+    del out
+    if not full:
+        return res
     # Host-issue headroom: wall time of the Python + ctypes + hipLaunchKernel work that ENQUEUES one step, measured
     # with an empty GPU queue in front of it (fence, then one step, clock stopped when the last launch call returns -- nothing in the
     # step synchronises, and one step's ~800 launches never fill the queue, so the GPU cannot push back).  If this approaches
@@ -700,7 +741,18 @@ def main():
     ap.add_argument('--optimizer', default='flat', choices=['flat', 'torch'],
                     help="'flat': FlatAdam (one gfx950 adam_kernel launch per group); 'torch': torch.optim.Adam(fused=True)")
     ap.add_argument('--layer-table', default='', help='write the per-launch conv table (CSV) of the profiled steps (the isolated pass: side streams off) here')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline measurement: box calibration, clocks, host-issue time, the per-launch roofline passes, '
+                         'the 384x1280 extra workload and the CPU / stock-PyTorch GPU baselines (each --no-* switch above still '
+                         'leaves its part out).  Off: set up, warm up, time the steps, print the result line')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='after the timed steps, write what the last timed step computed (loss, inverse depths, poses, a seeded '
+                         'sample of the updated parameters and their gradients) as DIR/<name>.npy, float32')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.layer_table and not args.full:
+        ap.error('--layer-table comes from the profiled steps of a --full run')
 
     if args.gpu_baseline_worker:          # child of gpu_eager_baseline_bounded: one JSON line, nothing else
         h, w, b = (int(v) for v in args.gpu_baseline_worker.split(','))
@@ -740,13 +792,14 @@ def main():
         optimizer = hvd.DistributedOptimizer(optimizer, named_parameters=model.named_parameters(),
                                              compression=hvd.Compression.none, force_collectives=force_ddp)
     ctx = {'rank': rank, 'world': world, 'device': device, 'ddp': ddp}
-    calibration = box_calibration(device) if (rank == 0 and not args.no_calibration) else None
+    calibration = box_calibration(device) if (rank == 0 and args.full and not args.no_calibration) else None
 
-    m = run_workload(model, optimizer, H, W, B, args.steps, args.warmup, ctx, want_prof=not args.no_prof,
-                     layer_table=args.layer_table)
+    m = run_workload(model, optimizer, H, W, B, args.steps, args.warmup, ctx, want_prof=args.full and not args.no_prof,
+                     layer_table=args.layer_table, full=args.full, dump_dir=args.dump_outputs)
     # configs[2] shape on the same model and optimizer, right behind the headline measurement (single GPU, default shape only)
     extra = None
-    if world == 1 and not ddp and (H, W, B) == (192, 640, 4) and not args.no_extra and args.depth_net == 'PackNet01':
+    if (args.full and world == 1 and not ddp and (H, W, B) == (192, 640, 4) and not args.no_extra
+            and args.depth_net == 'PackNet01'):
         extra = run_workload(model, optimizer, 384, 1280, 2, 6, 1, ctx, want_prof=not args.no_prof)
 
     if rank == 0:
@@ -767,9 +820,6 @@ def main():
             'metric': 'images/sec %s self-sup train %dx%d' % (args.depth_net, H, W), 'value': round(value, 3), 'unit': 'images/sec',
             'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(ms_step, 3),
             'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
-            # host time to ENQUEUE one step (empty queue in front of it, clock stopped before any fence) and its share of the step
-            'host_issue_ms_per_step': round(m['host_issue_ms'], 3), 'host_issue_frac': round(m['host_issue_ms'] / ms_step, 3),
-            'host_issue_ms_min': round(m['host_issue_ms_min'], 3),
             'config': {'workload': args.depth_net + '(1A)+PoseNet self-supervised train step (fwd+photometric loss+bwd+allreduce+Adam), '
                                    'KITTI-shaped %dx%d triplets, batch %d/GPU (%s)' % (H, W, B, shape_tag),
                        'global_batch': B * world, 'parallelism': 'dp%d' % world, 'final_loss': round(m['loss'], 6),
@@ -791,6 +841,13 @@ def main():
                        'rccl_ranks': dist.get_world_size() if (dist.is_initialized() and backend == 'nccl') else None},
             'roofline': roofline,
         }
+        if 'host_issue_ms' in m:
+            # host time to ENQUEUE one step (empty queue in front of it, clock stopped before any fence) and its share of the step
+            result.update({'host_issue_ms_per_step': round(m['host_issue_ms'], 3),
+                           'host_issue_frac': round(m['host_issue_ms'] / ms_step, 3),
+                           'host_issue_ms_min': round(m['host_issue_ms_min'], 3)})
+        if args.dump_outputs:
+            result['outputs_dumped'] = {'dir': args.dump_outputs, 'names': m['dumped']}
         if calibration is not None:
             calibration['clocks_during_timed_region'] = m.get('clocks')
             result['calibration'] = calibration
@@ -830,10 +887,10 @@ def main():
         # (~260 s on a fresh box, host-side) overlaps the ~75 s CPU leg; `auto` waits up to 420 s from its start (VERDICT r04 item 8:
         # the driver gives this script 1 800 s and the round-4 run used 96 s of them), `on` waits without a limit
         child = None
-        if world == 1 and not ddp and args.gpu_baseline != 'off':
+        if args.full and world == 1 and not ddp and args.gpu_baseline != 'off':
             torch.cuda.empty_cache()
             child = gpu_eager_baseline_start(H, W, B)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             if pinned is not None and all_cpus:
                 os.sched_setaffinity(0, all_cpus)          # the CPU leg sweeps thread counts over the whole box
             result['cpu_baseline'] = cpu_baseline(H, W)

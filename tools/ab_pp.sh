@@ -1,5 +1,5 @@
 cd $GRAFT_REPO_ROOT
-B="--steps 20 --warmup 4 --no-cpu-baseline --no-extra --gpu-baseline off"
+B="--steps 20 --warmup 4 --full --no-cpu-baseline --no-extra --gpu-baseline off"
 S='import sys,json; d=json.loads(sys.stdin.read()); r=d["roofline"] or {}; print(d["value"], d["ms_per_step"], "host", d.get("host_issue_ms_per_step"), "frac", r.get("frac"), "as_run", (r.get("as_run") or {}).get("frac"))'
 for m in 0 1 3; do
   rm -f /tmp/pp_$m.db

@@ -1,12 +1,12 @@
 #!/bin/bash
 # Same-box A/B of the round-4 kernel changes that still have a switch, on the final build: bench.py with each one switched off.
-mkdir -p gpurun_out
+L=${TMPDIR:-/tmp}/pnsfm_ab; mkdir -p $L
 run() { # name, env...
   name=$1; shift
-  env "$@" timeout 300 python bench.py --steps 30 --warmup 6 --no-cpu-baseline --no-extra --gpu-baseline off > gpurun_out/r04g_$name.log 2>&1
+  env "$@" timeout 300 python bench.py --steps 30 --warmup 6 --full --no-cpu-baseline --no-extra --gpu-baseline off > $L/switch_$name.log 2>&1
   python - <<P
 import json
-l=[x for x in open('gpurun_out/r04g_$name.log') if x.startswith('{')][-1]
+l=[x for x in open('$L/switch_$name.log') if x.startswith('{')][-1]
 d=json.loads(l); print('%-34s %8.3f img/s  %7.3f ms/step  conv frac %.4f  wgrad frac %.4f' % ('$name', d['value'], d['ms_per_step'], d['roofline']['frac'], d['roofline']['wgrad_kernel']['frac']))
 P
 }

@@ -29,15 +29,15 @@ smoke)
   timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke_$TAG.log 2>&1; tail -3 $O/smoke_$TAG.log ;;
 bench)
   echo "== bench (defaults: eager launches, FlatAdam), tune log on"
-  PNSFM_TUNE_LOG=$O/tunelog_$TAG.txt timeout 900 python bench.py --steps 10 --warmup 3 --layer-table $O/layers_$TAG.csv > $O/bench_$TAG.log 2>&1
+  PNSFM_TUNE_LOG=$O/tunelog_$TAG.txt timeout 900 python bench.py --full --steps 10 --warmup 3 --layer-table $O/layers_$TAG.csv > $O/bench_$TAG.log 2>&1
   tail -2 $O/bench_$TAG.log | cut -c1-1800 ;;
 bench_eager)
   echo "== bench"
-  timeout 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_eager_$TAG.log 2>&1
+  timeout 600 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_eager_$TAG.log 2>&1
   tail -1 $O/bench_eager_$TAG.log | cut -c1-600 ;;
 bench_c3)
   echo "== bench 384x1280 batch 2 (configs[2] shape)"
-  PNSFM_TUNE_LOG=$O/tunelog_c3_$TAG.txt timeout 900 python bench.py --height 384 --width 1280 --batch 2 --steps 6 --warmup 2 --no-cpu-baseline \
+  PNSFM_TUNE_LOG=$O/tunelog_c3_$TAG.txt timeout 900 python bench.py --full --height 384 --width 1280 --batch 2 --steps 6 --warmup 2 --no-cpu-baseline \
      --layer-table $O/layers_c3_$TAG.csv > $O/bench_c3_$TAG.log 2>&1
   tail -1 $O/bench_c3_$TAG.log | cut -c1-1500 ;;
 bench_2rank)
@@ -47,17 +47,17 @@ bench_2rank)
 prof)
   echo "== rocprofv3 kernel trace of bench.py (tuning database primed: no autotune candidates in the trace)"
   (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$TAG -o bench -- \
-      python $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline > $O/rocprof_$TAG.log 2>&1)
+      python $R/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline > $O/rocprof_$TAG.log 2>&1)
   tail -1 $O/rocprof_$TAG.log | cut -c1-400
   f=$(find $O/prof_$TAG -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && head -16 $f | cut -c1-160 ;;
 prof_iso)
   echo "== rocprofv3 kernel trace, weight-gradient side stream OFF (kernels run alone: the 'isolated' roofline)"
   (cd /tmp && PNSFM_WGRAD_STREAM=0 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_iso_$TAG -o bench -- \
-      python $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline > $O/rocprof_iso_$TAG.log 2>&1)
+      python $R/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline > $O/rocprof_iso_$TAG.log 2>&1)
   tail -1 $O/rocprof_iso_$TAG.log | cut -c1-400 ;;
 prof_eager)
   (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_eager_$TAG -o bench -- \
-      python $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline > $O/rocprof_eager_$TAG.log 2>&1)
+      python $R/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline > $O/rocprof_eager_$TAG.log 2>&1)
   tail -1 $O/rocprof_eager_$TAG.log | cut -c1-400 ;;
 pmc)
   echo "== rocprofv3 PMC passes (counters only, separate runs)"

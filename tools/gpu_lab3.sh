@@ -42,12 +42,12 @@ smoke)
   timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke_$TAG.log 2>&1; tail -3 $O/smoke_$TAG.log ;;
 bench)
   echo "== bench, fresh tuning database $DB"
-  PNSFM_TUNE_DB=$DB PNSFM_TUNE_LOG=$O/tunelog_$TAG.txt timeout 1500 python bench.py --steps 10 --warmup 3 --no-cpu-baseline \
+  PNSFM_TUNE_DB=$DB PNSFM_TUNE_LOG=$O/tunelog_$TAG.txt timeout 1500 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline \
      --layer-table $O/layers_$TAG.csv > $O/bench_$TAG.log 2>&1
   tail -1 $O/bench_$TAG.log | cut -c1-2500; wc -l $DB ;;
 benchfull)
   echo "== bench as the driver runs it"
-  timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/benchfull_$TAG.log 2>&1
+  timeout 1500 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/benchfull_$TAG.log 2>&1
   tail -1 $O/benchfull_$TAG.log | cut -c1-3500 ;;
 ab_1x1)
   echo "== bench with 1x1 layers on the f32 kernels"
@@ -72,22 +72,22 @@ ab_pack)
 ab_map)
   echo "== A/B: block order of the conv kernels (0 round robin as round 2, 1 operand-sharing order, 2 + contiguous range per XCD), same database"
   for i in 1 2; do for m in 2 0 1; do
-    PNSFM_BLOCK_MAP=$m PNSFM_TUNE_DB=$DB timeout 900 python bench.py --steps 15 --warmup 3 --no-cpu-baseline --no-extra > $O/bench_map${m}_$TAG.log 2>&1
+    PNSFM_BLOCK_MAP=$m PNSFM_TUNE_DB=$DB timeout 900 python bench.py --full --steps 15 --warmup 3 --no-cpu-baseline --no-extra > $O/bench_map${m}_$TAG.log 2>&1
     echo "map $m: $(tail -1 $O/bench_map${m}_$TAG.log | python -c "import sys,json; d=json.loads(sys.stdin.read()); r=d['roofline']; print(d['value'], 'img/s  fwd+dgrad', r['achieved'], 'TF  wgrad', r['wgrad_kernel']['achieved'], 'TF')")"
   done; done ;;
 ab_layout)
   echo "== A/B: LDS layout of the conv patch (1 half planes: conflict-free B fragments, 0 round 2: [pixel][half]), same database"
   for i in 1 2; do for m in 1 0; do
-    PNSFM_PATCH_LAYOUT=$m PNSFM_TUNE_DB=$DB timeout 900 python bench.py --steps 15 --warmup 3 --no-cpu-baseline --no-extra > $O/bench_layout${m}_$TAG.log 2>&1
+    PNSFM_PATCH_LAYOUT=$m PNSFM_TUNE_DB=$DB timeout 900 python bench.py --full --steps 15 --warmup 3 --no-cpu-baseline --no-extra > $O/bench_layout${m}_$TAG.log 2>&1
     echo "layout $m: $(tail -1 $O/bench_layout${m}_$TAG.log | python -c "import sys,json; d=json.loads(sys.stdin.read()); r=d['roofline']; print(d['value'], 'img/s  fwd+dgrad', r['achieved'], 'TF  wgrad', r['wgrad_kernel']['achieved'], 'TF')")"
   done; done ;;
 c3)
   echo "== 384x1280 batch 2 (BASELINE configs[2] shape): bench + layer table, rocprofv3 kernel summary, PMC traffic passes"
   C3="--height 384 --width 1280 --batch 2"
-  PNSFM_TUNE_DB=$DB timeout 900 python bench.py $C3 --steps 8 --warmup 2 --no-cpu-baseline --no-extra --layer-table $O/layers_c3_$TAG.csv > $O/bench_c3_$TAG.log 2>&1
+  PNSFM_TUNE_DB=$DB timeout 900 python bench.py $C3 --full --steps 8 --warmup 2 --no-cpu-baseline --no-extra --layer-table $O/layers_c3_$TAG.csv > $O/bench_c3_$TAG.log 2>&1
   tail -1 $O/bench_c3_$TAG.log | cut -c1-300
   (cd /tmp && PNSFM_TUNE_DB=$DB timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_c3_$TAG -o bench -- \
-      python $R/bench.py $C3 --steps 4 --warmup 2 --no-cpu-baseline --no-extra > $O/rocprof_c3_$TAG.log 2>&1)
+      python $R/bench.py $C3 --full --steps 4 --warmup 2 --no-cpu-baseline --no-extra > $O/rocprof_c3_$TAG.log 2>&1)
   for c in "FETCH_SIZE" "WRITE_SIZE"; do
     (cd /tmp && PNSFM_TUNE_DB=$DB timeout 900 rocprofv3 --pmc $c --output-format csv -d $O/pmc_c3_${TAG}_$c -o bench -- \
       python $R/bench.py $C3 --steps 2 --warmup 1 --no-cpu-baseline --no-prof --no-extra > $O/pmc_c3_${TAG}_$c.log 2>&1)
@@ -100,7 +100,7 @@ bench2)
 prof)
   echo "== rocprofv3 kernel trace (database primed)"
   (cd /tmp && PNSFM_TUNE_DB=$DB timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$TAG -o bench -- \
-      python $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-extra > $O/rocprof_$TAG.log 2>&1)
+      python $R/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-extra > $O/rocprof_$TAG.log 2>&1)
   tail -1 $O/rocprof_$TAG.log | cut -c1-300
   f=$(find $O/prof_$TAG -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && head -40 $f | cut -c1-150
   t=$(find $O/prof_$TAG -name "*kernel_trace.csv" | head -1); [ -n "$t" ] && python tools/step_breakdown.py $t 80 > $O/step_breakdown_$TAG.txt 2>&1 && head -60 $O/step_breakdown_$TAG.txt ;;

@@ -15,7 +15,7 @@ export TMPDIR=/tmp
 cd $R
 DB=/tmp/shipped_copy.db
 cp packnet-sfm_amd/csrc/tuned_gfx950.db $DB
-BARGS="--no-cpu-baseline --no-extra --gpu-baseline off"
+BARGS="--full --no-cpu-baseline --no-extra --gpu-baseline off"
 SUMMARY='import sys,json; d=json.loads(sys.stdin.read()); r=d["roofline"] or {}; print(d["value"], d["ms_per_step"], "host_issue", d.get("host_issue_ms_per_step"), "frac", r.get("frac"), "as_run", (r.get("as_run") or {}).get("frac"), "wgrad", (r.get("wgrad_kernel") or {}).get("frac"))'
 for w in "$@"; do
 t0=$(date +%s)
@@ -26,7 +26,7 @@ tests)
 quick)
   timeout 1500 python -m pytest tests -m gpu -x -q -k "${PYTEST_K:-round4}" > $O/r06_pytest_quick.log 2>&1; tail -6 $O/r06_pytest_quick.log ;;
 bench)
-  timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/r06_bench_default_run.log 2>&1
+  timeout 1500 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/r06_bench_default_run.log 2>&1
   tail -1 $O/r06_bench_default_run.log > $O/r06_bench_default_run.json; cut -c1-600 $O/r06_bench_default_run.json ;;
 benchq)
   PNSFM_TUNE_DB=$DB timeout 600 python bench.py --steps 20 --warmup 4 $BARGS > $O/r06_benchq.log 2>&1
@@ -57,9 +57,9 @@ lab)
   timeout 1500 python tools/conv_lab5.py $LAB_ARGS > $O/r06_lab.txt 2> $O/r06_lab.err; tail -70 $O/r06_lab.txt; tail -5 $O/r06_lab.err ;;
 tune)
   rm -f /tmp/new.db
-  PNSFM_TUNE_DB=/tmp/new.db PNSFM_TUNE_LOG=$O/r06_tunelog_192x640.txt timeout 1200 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --gpu-baseline off > $O/r06_tune_run.log 2>&1
+  PNSFM_TUNE_DB=/tmp/new.db PNSFM_TUNE_LOG=$O/r06_tunelog_192x640.txt timeout 1200 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --gpu-baseline off > $O/r06_tune_run.log 2>&1
   tail -1 $O/r06_tune_run.log | cut -c1-160
-  PNSFM_TUNE_DB=/tmp/new.db timeout 600 python bench.py --depth-net PackNetSlim01 --steps 5 --warmup 2 --no-cpu-baseline --no-extra --gpu-baseline off > $O/r06_tune_slim.log 2>&1
+  PNSFM_TUNE_DB=/tmp/new.db timeout 600 python bench.py --full --depth-net PackNetSlim01 --steps 5 --warmup 2 --no-cpu-baseline --no-extra --gpu-baseline off > $O/r06_tune_slim.log 2>&1
   cp /tmp/new.db $O/r06_tuned.db; wc -l $O/r06_tuned.db ;;
 prof)
   timeout 600 python bench.py --steps 10 --warmup 3 $BARGS --layer-table $O/r06_conv_layer_table.csv > $O/r06_bench.log 2>&1
