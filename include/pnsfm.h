@@ -477,6 +477,43 @@ int pnsfm_sparse_maxpool_backward(const float* dout, const int* arg, float* din,
 int pnsfm_sparse_densify(const float* feats, const int* imap, float* dense, int B, int C, int hw, void* stream);
 int pnsfm_sparse_gather(const float* dense, const int* sites, const int* count, float* rows, int cap, int C, int hw, void* stream);
 
+/* ---- fp16 forward (evaluation / inference) ------------------------------------------------------------------------------------
+ * The reference's `--half` path (scripts/eval.py, scripts/infer.py: module.to('cuda', dtype=torch.float16), every batch cast to fp16) on
+ * the depth networks PackNet01 / PackNetSlim01.  Forward only; training, backward and the pose / SAN networks stay fp32.
+ * Numerics contract:
+ *   - activations and parameters are STORED as IEEE fp16 (`void*` below: device pointers to contiguous fp16, NCHW); the convolution
+ *     bias is fp32 (the caller upcasts the fp16 parameter), as are the mean / rstd outputs of the GroupNorm;
+ *   - every kernel COMPUTES in fp32: fp16 x fp16 products are exact in fp32, sums are fp32, GroupNorm statistics are fp64;
+ *   - each kernel rounds its output ONCE to fp16, round to nearest even (v_cvt_f16_f32 semantics, never round-toward-zero), at the
+ *     module boundaries where the reference's fp16 run rounds (conv out, block out, head out), so overflow behaves like the
+ *     reference's; the fused GroupNorm + ELU and sigmoid / min_depth skip one intermediate rounding of the reference;
+ *   - results are bit-reproducible: no float atomics; a K-split convolution adds its fp32 partials in a fixed order.
+ * pnsfm_conv2d_*_h16: stride 1, zero pad ks/2, ks in {1, 3, 5, 7}, v_mfma_f32_32x32x16_f16 implicit GEMM (csrc/conv2d_h16.h).  The packed
+ *   weight holds pnsfm_conv2d_packed_elems_h16 fp16 elements; the packer reads an fp16 (src_is_f32 = 0) or fp32 (1) [Cout][Cin][ks][ks]
+ *   source.  The forward's input is the channel concatenation of x0 [B][C0], x1 [B][C1], x2 [B][C2] (x1 / x2 nullable when C1 / C2 = 0),
+ *   with no alignment rule on C0 / C1.  pnsfm_conv2d_last_config reports variant 9 for these launches: {9, NT, MT, WM, K splits, tile
+ *   width, workgroups, LDS bytes}.  A launch splits K over at most pnsfm_set_h16_max_split workgroup sets.
+ * pnsfm_groupnorm_act_forward_h16: pnsfm_groupnorm_act_forward on fp16 x / res (nullable) / gamma / beta / y (8-byte aligned).
+ * pnsfm_conv3d_forward_h16: pnsfm_conv3d_forward, fp16 p / w3 / b3 (nullable) / out.  pnsfm_space_to_depth_h16, pnsfm_depth_to_space_h16,
+ * pnsfm_upsample_nearest_forward_h16, pnsfm_invdepth_conv_forward_h16 (fp16 x / w / bias / y): their fp32 counterparts on fp16.
+ * pnsfm_region_ops_h16: pnsfm_region_ops with pnsfm_region_op's src / dst pointing at fp16 elements (strides in elements). */
+size_t pnsfm_conv2d_packed_elems_h16(int Cin, int Cout, int ks);
+/* At most n K splits per fp16 convolution launch (1: never split; <= 0: the default, 16).  Returns the previous setting. */
+int pnsfm_set_h16_max_split(int n);
+int pnsfm_conv2d_pack_weights_h16(const void* w, int src_is_f32, void* wp, int Cin, int Cout, int ks, void* stream);
+int pnsfm_conv2d_forward_h16(const void* x0, int C0, const void* x1 /*nullable*/, int C1, const void* x2 /*nullable*/, int C2,
+                             const void* wp, const float* bias /*nullable*/, void* y, int B, int Cout, int H, int W, int ks, void* stream);
+int pnsfm_groupnorm_act_forward_h16(const void* x, const void* res /*nullable*/, const void* gamma, const void* beta, void* y,
+                                    float* mean, float* rstd, int B, int C, int HW, int G, float eps, int act, void* stream);
+int pnsfm_conv3d_forward_h16(const void* p, const void* w3, const void* b3 /*nullable*/, void* out, int B, int D, int H, int W, int NF,
+                             void* stream);
+int pnsfm_space_to_depth_h16(const void* x, void* y, int B, int C, int H, int W, void* stream);
+int pnsfm_depth_to_space_h16(const void* x, void* y, int B, int C, int H, int W, void* stream);
+int pnsfm_upsample_nearest_forward_h16(const void* x, void* y, int N, int h, int w, int s, void* stream);
+int pnsfm_invdepth_conv_forward_h16(const void* x, const void* w, const void* bias, void* y, int B, int C, int H, int W, float min_depth,
+                                    void* stream);
+int pnsfm_region_ops_h16(const void* ops_host, int n_ops, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2356,3 +2356,5 @@ int pnsfm_tune_shipped_entries(void) {
 }
 
 }  // extern "C"
+
+#include "conv2d_h16.h"      // fp16 forward (evaluation / inference): variant 9

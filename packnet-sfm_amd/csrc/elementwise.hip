@@ -185,18 +185,22 @@ static int grid_for(size_t total) {
 // interior result and scatters / accumulates the matching gradients: ~33 slice-assignments, cats, fills and strided adds per block and
 // step on ATen (profiles/r04: ~0.5 ms per step in launches of 4-30 us).  Each autograd Function now issues one launch of this kernel.
 // dst / src addresses are base + sum_i idx_i * stride_i (element strides, any layout); blockIdx.y = operation, grid-stride over elements.
-struct RegionOp {
-  const float* src;      // null for zero
-  float* dst;
+template <class T>      // element type: float, or pnsfm_h16 (pnsfm_region_ops_h16; never vec)
+struct RegionOpT {
+  const T* src;          // null for zero
+  T* dst;
   unsigned n[4];         // extents (n[3] in float4 units when vec)
   long long ss[4], ds[4];
   int op;                // 0 copy, 1 add (dst += src), 2 zero
   int vec;               // innermost dimension contiguous, 16-byte aligned and a multiple of 4 on both sides: float4 accesses
 };
-struct RegionOps { RegionOp o[PNSFM_MAX_REGION_OPS]; };
+typedef RegionOpT<float> RegionOp;
+template <class T> struct RegionOpsT { RegionOpT<T> o[PNSFM_MAX_REGION_OPS]; };
+typedef RegionOpsT<float> RegionOps;
 
-__global__ void __launch_bounds__(256) region_ops_kernel(RegionOps ops) {
-  const RegionOp& r = ops.o[blockIdx.y];
+template <class T>
+__global__ void __launch_bounds__(256) region_ops_kernel(RegionOpsT<T> ops) {
+  const RegionOpT<T>& r = ops.o[blockIdx.y];
   const unsigned total = r.n[0] * r.n[1] * r.n[2] * r.n[3];        // (the entry point refuses windows of >= 2^31 elements)
   for (unsigned e = blockIdx.x * 256u + threadIdx.x; e < total; e += gridDim.x * 256u) {
     unsigned t = e;
@@ -204,17 +208,18 @@ __global__ void __launch_bounds__(256) region_ops_kernel(RegionOps ops) {
     const unsigned i2 = t % r.n[2]; t /= r.n[2];
     const unsigned i1 = t % r.n[1];
     const unsigned i0 = t / r.n[1];
-    if (r.vec) {
+    if (sizeof(T) == 4 && r.vec) {
       float4* d = reinterpret_cast<float4*>(r.dst + i0 * r.ds[0] + i1 * r.ds[1] + i2 * r.ds[2]) + i3;
       if (r.op == 2) { *d = make_float4(0.f, 0.f, 0.f, 0.f); continue; }
       const float4 v = reinterpret_cast<const float4*>(r.src + i0 * r.ss[0] + i1 * r.ss[1] + i2 * r.ss[2])[i3];
       if (r.op == 1) { float4 o = *d; o.x += v.x; o.y += v.y; o.z += v.z; o.w += v.w; *d = o; }
       else *d = v;
     } else {
-      float* d = r.dst + i0 * r.ds[0] + i1 * r.ds[1] + i2 * r.ds[2] + i3 * r.ds[3];
-      if (r.op == 2) { *d = 0.f; continue; }
-      const float v = r.src[i0 * r.ss[0] + i1 * r.ss[1] + i2 * r.ss[2] + i3 * r.ss[3]];
-      *d = r.op == 1 ? *d + v : v;
+      T* d = r.dst + i0 * r.ds[0] + i1 * r.ds[1] + i2 * r.ds[2] + i3 * r.ds[3];
+      if (r.op == 2) { *d = (T)0.f; continue; }
+      const T v = r.src[i0 * r.ss[0] + i1 * r.ss[1] + i2 * r.ss[2] + i3 * r.ss[3]];
+      if (r.op == 1) pnsfm_stf(d, pnsfm_ldf(d) + pnsfm_ldf(&v));
+      else *d = v;
     }
   }
 }
@@ -223,18 +228,19 @@ __global__ void __launch_bounds__(256) region_ops_kernel(RegionOps ops) {
 // brought to full resolution, models/model_utils.py:163-180 via utils/image.py:148-176, and the inverse depth handed to the next
 // iconv block, nn.Upsample in networks/depth/PackNet01.py:87-89,150,159,168): y[n, oy, ox] = x[n, oy / s, ox / s].  One thread per FOUR output columns
 // (the host only takes maps whose output width is a multiple of 4).
-__global__ void __launch_bounds__(256) upsample_nearest_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int h, int w,
+template <class T>      // float, or pnsfm_h16 (fp16 forward)
+__global__ void __launch_bounds__(256) upsample_nearest_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, int h, int w,
                                                                    int s, unsigned total4) {
   const unsigned i = blockIdx.x * 256u + threadIdx.x;
   if (i >= total4) return;
   const unsigned W4 = (unsigned)(w * s) >> 2, Ho = (unsigned)(h * s);
   const unsigned q = i % W4, t = i / W4;
   const unsigned oy = t % Ho, n = t / Ho;
-  const float* row = x + ((size_t)n * h + oy / s) * w;
+  const T* row = x + ((size_t)n * h + oy / s) * w;
   const unsigned ox = 4u * q;
   float4 v;
-  v.x = row[ox / s]; v.y = row[(ox + 1) / s]; v.z = row[(ox + 2) / s]; v.w = row[(ox + 3) / s];
-  reinterpret_cast<float4*>(y)[i] = v;
+  v.x = pnsfm_ldf(row + ox / s); v.y = pnsfm_ldf(row + (ox + 1) / s); v.z = pnsfm_ldf(row + (ox + 2) / s); v.w = pnsfm_ldf(row + (ox + 3) / s);
+  pnsfm_st4(y + 4 * (size_t)i, v);
 }
 
 // its gradient: dx[n, iy, ix] = sum of the s x s block of dy, rows then columns in ascending order (one thread per input element)
@@ -453,7 +459,7 @@ int pnsfm_region_ops(const void* ops_host, int n_ops, void* stream) {
   }
   long long gx = (most + 255) / 256;
   if (gx > 2048) gx = 2048;
-  PNSFM_LAUNCH(region_ops_kernel, dim3((unsigned)gx, (unsigned)n_ops), dim3(256), 0, (hipStream_t)stream, ops);
+  PNSFM_LAUNCH(region_ops_kernel<float>, dim3((unsigned)gx, (unsigned)n_ops), dim3(256), 0, (hipStream_t)stream, ops);
   return check_launch("region_ops");
 }
 
@@ -462,8 +468,43 @@ int pnsfm_upsample_nearest_forward(const float* x, float* y, int N, int h, int w
   const size_t total = (size_t)N * h * s * w * s;
   if (total >= (1ull << 32)) { set_error("upsample_nearest_forward: >= 2^32 output elements"); return -1; }
   const unsigned total4 = (unsigned)(total / 4);
-  PNSFM_LAUNCH(upsample_nearest_fwd_kernel, dim3((total4 + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, y, h, w, s, total4);
+  PNSFM_LAUNCH(upsample_nearest_fwd_kernel<float>, dim3((total4 + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, y, h, w, s, total4);
   return check_launch("upsample_nearest_forward");
+}
+
+// ---- fp16 forward (evaluation / inference): the same kernels on 2-byte elements
+int pnsfm_region_ops_h16(const void* ops_host, int n_ops, void* stream) {
+  if (n_ops < 1 || n_ops > PNSFM_MAX_REGION_OPS) { set_error("region_ops_h16: 1..%d operations per launch (got %d)", PNSFM_MAX_REGION_OPS, n_ops); return -1; }
+  RegionOpsT<pnsfm_h16> ops;
+  long long most = 0;
+  const pnsfm_region_op* in = static_cast<const pnsfm_region_op*>(ops_host);
+  for (int i = 0; i < n_ops; ++i) {
+    RegionOpT<pnsfm_h16>& r = ops.o[i];
+    r.src = (const pnsfm_h16*)in[i].src; r.dst = (pnsfm_h16*)in[i].dst; r.op = in[i].op; r.vec = 0;
+    long long total = 1;
+    for (int k = 0; k < 4; ++k) {
+      if (in[i].n[k] < 1) { set_error("region_ops_h16: empty extent in operation %d", i); return -1; }
+      r.n[k] = (unsigned)in[i].n[k]; r.ss[k] = in[i].src_stride[k]; r.ds[k] = in[i].dst_stride[k];
+      total *= in[i].n[k];
+    }
+    if (total >= (1LL << 31)) { set_error("region_ops_h16: window of operation %d has >= 2^31 elements", i); return -1; }
+    if (r.op < 0 || r.op > 2 || !r.dst || (r.op != 2 && !r.src)) { set_error("region_ops_h16: bad operation %d", i); return -1; }
+    if (total > most) most = total;
+  }
+  long long gx = (most + 255) / 256;
+  if (gx > 2048) gx = 2048;
+  PNSFM_LAUNCH(region_ops_kernel<pnsfm_h16>, dim3((unsigned)gx, (unsigned)n_ops), dim3(256), 0, (hipStream_t)stream, ops);
+  return check_launch("region_ops_h16");
+}
+
+int pnsfm_upsample_nearest_forward_h16(const void* x, void* y, int N, int h, int w, int s, void* stream) {
+  if (N < 1 || h < 1 || w < 1 || s < 1 || (w * s) % 4 != 0) { set_error("upsample_nearest_forward_h16: output width must be a multiple of 4 (N=%d h=%d w=%d s=%d)", N, h, w, s); return -1; }
+  const size_t total = (size_t)N * h * s * w * s;
+  if (total >= (1ull << 32)) { set_error("upsample_nearest_forward_h16: >= 2^32 output elements"); return -1; }
+  const unsigned total4 = (unsigned)(total / 4);
+  PNSFM_LAUNCH(upsample_nearest_fwd_kernel<pnsfm_h16>, dim3((total4 + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const pnsfm_h16*)x,
+               (pnsfm_h16*)y, h, w, s, total4);
+  return check_launch("upsample_nearest_forward_h16");
 }
 
 int pnsfm_upsample_nearest_backward(const float* dy, float* dx, int N, int h, int w, int s, void* stream) {

@@ -79,8 +79,8 @@ __device__ __forceinline__ double row_sum(double v, int T, double* red) {
 
 // ---- forward statistics: stats[((bg)*nslot + slot)*2 + {0,1}] = {sum, sumsq} of one (channel row, chunk) piece of group bg;
 //      nslot = cpg * nchunk (channels per group x chunks)
-template <bool VEC>
-__global__ void __launch_bounds__(256) gn_stats_kernel(const float* __restrict__ x, const float* __restrict__ res,
+template <bool VEC, class T = float>      // T: storage of x / res / gamma / beta / y (float, or pnsfm_h16 for the fp16 forward)
+__global__ void __launch_bounds__(256) gn_stats_kernel(const T* __restrict__ x, const T* __restrict__ res,
                                                         double* __restrict__ stats, int BC, int C, int HW, int G, GnGeom g) {
   __shared__ double red[4];
   const int tid = threadIdx.x;
@@ -91,19 +91,19 @@ __global__ void __launch_bounds__(256) gn_stats_kernel(const float* __restrict__
   if (end > HW) end = HW;
   double s1 = 0.0, s2 = 0.0;
   if (bc < BC) {
-    const float* xp = x + (size_t)bc * HW;
-    const float* rp = res ? res + (size_t)bc * HW : nullptr;
+    const T* xp = x + (size_t)bc * HW;
+    const T* rp = res ? res + (size_t)bc * HW : nullptr;
     if (VEC) {
       for (int i = beg + 4 * l; i < end; i += 4 * g.T) {
-        float4 v = *reinterpret_cast<const float4*>(xp + i);
-        if (rp) { const float4 q = *reinterpret_cast<const float4*>(rp + i); v.x += q.x; v.y += q.y; v.z += q.z; v.w += q.w; }
+        float4 v = pnsfm_ld4(xp + i);
+        if (rp) { const float4 q = pnsfm_ld4(rp + i); v.x += q.x; v.y += q.y; v.z += q.z; v.w += q.w; }
         s1 += ((double)v.x + (double)v.y) + ((double)v.z + (double)v.w);
         s2 += ((double)v.x * v.x + (double)v.y * v.y) + ((double)v.z * v.z + (double)v.w * v.w);
       }
     } else {
       for (int i = beg + l; i < end; i += g.T) {
-        float v = xp[i];
-        if (rp) v += rp[i];
+        float v = pnsfm_ldf(xp + i);
+        if (rp) v += pnsfm_ldf(rp + i);
         s1 += (double)v;
         s2 += (double)v * (double)v;
       }
@@ -124,11 +124,11 @@ __global__ void __launch_bounds__(256) gn_stats_kernel(const float* __restrict__
 // pass 2: every row adds the partial slots of its group (lanes of the row share the slots, fp64, fixed order), derives
 // mean / rstd exactly like every other row of that group, and normalises + activates its chunk.  The row of the group's first
 // channel in chunk 0 stores mean / rstd for the backward pass.
-template <bool VEC>
-__global__ void __launch_bounds__(256) gn_apply_kernel(const float* __restrict__ x, const float* __restrict__ res,
-                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
+template <bool VEC, class T = float>
+__global__ void __launch_bounds__(256) gn_apply_kernel(const T* __restrict__ x, const T* __restrict__ res,
+                                                        const T* __restrict__ gamma, const T* __restrict__ beta,
                                                         const double* __restrict__ stats, float* __restrict__ mean_out,
-                                                        float* __restrict__ rstd_out, float* __restrict__ y, int BC, int C, int HW,
+                                                        float* __restrict__ rstd_out, T* __restrict__ y, int BC, int C, int HW,
                                                         int G, int act, double n, float eps, GnGeom g, int nslot) {
   __shared__ double red[4];
   const int tid = threadIdx.x;
@@ -151,25 +151,25 @@ __global__ void __launch_bounds__(256) gn_apply_kernel(const float* __restrict__
   const float mu = (float)m, rs = (float)(1.0 / sqrt(var + (double)eps));
   if (!valid) return;
   if (l == 0 && c == gi * cpg && blockIdx.y == 0) { mean_out[b * G + gi] = mu; rstd_out[b * G + gi] = rs; }
-  const float sc = rs * gamma[c], sh = beta[c] - mu * sc;         // z = v * sc + sh
+  const float sc = rs * pnsfm_ldf(gamma + c), sh = pnsfm_ldf(beta + c) - mu * sc;         // z = v * sc + sh
   const size_t base = (size_t)bc * HW;
   const int beg = blockIdx.y * g.chunk;
   int end = beg + g.chunk;
   if (end > HW) end = HW;
   if (VEC) {
     for (int i = beg + 4 * l; i < end; i += 4 * g.T) {
-      float4 v = *reinterpret_cast<const float4*>(x + base + i);
-      if (res) { const float4 q = *reinterpret_cast<const float4*>(res + base + i); v.x += q.x; v.y += q.y; v.z += q.z; v.w += q.w; }
+      float4 v = pnsfm_ld4(x + base + i);
+      if (res) { const float4 q = pnsfm_ld4(res + base + i); v.x += q.x; v.y += q.y; v.z += q.z; v.w += q.w; }
       float4 o;
       o.x = act_fwd(fmaf(v.x, sc, sh), act); o.y = act_fwd(fmaf(v.y, sc, sh), act);
       o.z = act_fwd(fmaf(v.z, sc, sh), act); o.w = act_fwd(fmaf(v.w, sc, sh), act);
-      *reinterpret_cast<float4*>(y + base + i) = o;
+      pnsfm_st4(y + base + i, o);
     }
   } else {
     for (int i = beg + l; i < end; i += g.T) {
-      float v = x[base + i];
-      if (res) v += res[base + i];
-      y[base + i] = act_fwd(fmaf(v, sc, sh), act);
+      float v = pnsfm_ldf(x + base + i);
+      if (res) v += pnsfm_ldf(res + base + i);
+      pnsfm_stf(y + base + i, act_fwd(fmaf(v, sc, sh), act));
     }
   }
 }
@@ -351,11 +351,11 @@ __device__ __forceinline__ void gnf_slab_part(int blk, int S, int nslab, int& sl
 }
 
 // dq / dr: T / HW4 and T % HW4 (the float4 index advances by T per k: channel += dq, position += dr with one carry)
-template <int NV, int S>
-__global__ void __launch_bounds__(1024) gn_fused_fwd_kernel(const float* __restrict__ x, const float* __restrict__ res,
-                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
+template <int NV, int S, class TS = float>
+__global__ void __launch_bounds__(1024) gn_fused_fwd_kernel(const TS* __restrict__ x, const TS* __restrict__ res,
+                                                             const TS* __restrict__ gamma, const TS* __restrict__ beta,
                                                              float* __restrict__ mean_out, float* __restrict__ rstd_out,
-                                                             float* __restrict__ y, int C, int HW, int G, int act, float eps, int nslab,
+                                                             TS* __restrict__ y, int C, int HW, int G, int act, float eps, int nslab,
                                                              int dq, int dr) {
   __shared__ double red[2][16];
   __shared__ float lsc[GNF_MAXCPG], lsh[GNF_MAXCPG];
@@ -365,19 +365,19 @@ __global__ void __launch_bounds__(1024) gn_fused_fwd_kernel(const float* __restr
   const int cpg = C / G, gi = bg % G;
   const int HW4 = HW >> 2, n4 = cpg * HW4;
   const size_t base4 = (size_t)bg * n4;
-  const float4* xp = reinterpret_cast<const float4*>(x) + base4;
-  const float4* rp = res ? reinterpret_cast<const float4*>(res) + base4 : nullptr;
+  const TS* xp = x + 4 * base4;
+  const TS* rp = res ? res + 4 * base4 : nullptr;
   float4 v[NV];
 #pragma unroll
   for (int k = 0; k < NV; ++k) {
     const int i = tid + k * T;
-    v[k] = i < n4 ? xp[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    v[k] = i < n4 ? pnsfm_ld4(xp + 4 * (size_t)i) : make_float4(0.f, 0.f, 0.f, 0.f);
   }
   if (rp) {
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
       const int i = tid + k * T;
-      if (i < n4) { const float4 q = rp[i]; v[k].x += q.x; v[k].y += q.y; v[k].z += q.z; v[k].w += q.w; }
+      if (i < n4) { const float4 q = pnsfm_ld4(rp + 4 * (size_t)i); v[k].x += q.x; v[k].y += q.y; v[k].z += q.z; v[k].w += q.w; }
     }
   }
   double s1 = 0.0, s2 = 0.0;
@@ -398,12 +398,12 @@ __global__ void __launch_bounds__(1024) gn_fused_fwd_kernel(const float* __restr
   const float mu = (float)m, rs = (float)(1.0 / sqrt(var + (double)eps));
   if (tid == 0 && part == 0) { mean_out[bg] = mu; rstd_out[bg] = rs; }
   if (tid < cpg) {
-    const float sc = rs * gamma[gi * cpg + tid];
+    const float sc = rs * pnsfm_ldf(gamma + gi * cpg + tid);
     lsc[tid] = sc;
-    lsh[tid] = beta[gi * cpg + tid] - mu * sc;
+    lsh[tid] = pnsfm_ldf(beta + gi * cpg + tid) - mu * sc;
   }
   __syncthreads();
-  float4* yp = reinterpret_cast<float4*>(y) + base4;
+  TS* yp = y + 4 * base4;
   int ch = tid / HW4, pos = tid - ch * HW4;
 #pragma unroll
   for (int k = 0; k < NV; ++k) {
@@ -414,7 +414,7 @@ __global__ void __launch_bounds__(1024) gn_fused_fwd_kernel(const float* __restr
       float4 o;
       o.x = act_fwd(fmaf(v[k].x, sc, sh), act); o.y = act_fwd(fmaf(v[k].y, sc, sh), act);
       o.z = act_fwd(fmaf(v[k].z, sc, sh), act); o.w = act_fwd(fmaf(v[k].w, sc, sh), act);
-      yp[i] = o;
+      pnsfm_st4(yp + 4 * (size_t)i, o);
     }
     ch += dq; pos += dr;
     if (pos >= HW4) { pos -= HW4; ++ch; }
@@ -644,9 +644,11 @@ size_t pnsfm_groupnorm_ws_doubles(int B, int C, int G) {
   return (size_t)2 * B * C * PNSFM_GN_MAX_SPLIT + (size_t)2 * B * C + (size_t)B * G + 16;
 }
 
-int pnsfm_groupnorm_act_forward(const float* x, const float* res, const float* gamma, const float* beta, float* y,
-                                float* mean, float* rstd, double* stats_ws, int B, int C, int HW, int G, float eps,
-                                int act, void* stream) {
+}  // extern "C"
+
+template <class TS>
+static int gn_forward(const TS* x, const TS* res, const TS* gamma, const TS* beta, TS* y, float* mean, float* rstd, double* stats_ws, int B,
+                      int C, int HW, int G, float eps, int act, void* stream) {
   if (C % G != 0 || B <= 0 || HW <= 0) { set_error("groupnorm_forward: bad shape C=%d G=%d", C, G); return -1; }
   hipStream_t s = (hipStream_t)stream;
   const bool vec = (HW % 4 == 0);
@@ -658,7 +660,7 @@ int pnsfm_groupnorm_act_forward(const float* x, const float* res, const float* g
     const int S = gn_fused_parts(n4, T);
     const int HW4 = HW / 4, dq = T / HW4, dr = T % HW4, nslab = B * G;
     const dim3 grid(nslab * S), block(T);
-#define PNSFM_GNF(NVv, Sv) PNSFM_LAUNCH((gn_fused_fwd_kernel<NVv, Sv>), grid, block, 0, s, x, res, gamma, beta, mean, rstd, y, C, HW, G, act, eps, nslab, dq, dr)
+#define PNSFM_GNF(NVv, Sv) PNSFM_LAUNCH((gn_fused_fwd_kernel<NVv, Sv, TS>), grid, block, 0, s, x, res, gamma, beta, mean, rstd, y, C, HW, G, act, eps, nslab, dq, dr)
     if (nv <= 1) PNSFM_GNF(1, 1);
     else if (nv <= 2) PNSFM_GNF(2, 1);
     else if (nv <= 4) { if (S == 4) PNSFM_GNF(4, 4); else if (S == 2) PNSFM_GNF(4, 2); else PNSFM_GNF(4, 1); }
@@ -672,14 +674,30 @@ int pnsfm_groupnorm_act_forward(const float* x, const float* res, const float* g
   // stats_ws == null: the partial sums live in the stream's scratch buffer (they are dead when this call's second launch has run)
   ScratchLease lease(s, stats_ws ? 0 : pnsfm_groupnorm_ws_doubles(B, C, G) * sizeof(double));
   if (!stats_ws) { stats_ws = lease.as<double>(); if (!stats_ws) return -1; }
-  if (vec) PNSFM_LAUNCH((gn_stats_kernel<true>), grid, dim3(256), 0, s, x, res, stats_ws, BC, C, HW, G, g);
-  else PNSFM_LAUNCH((gn_stats_kernel<false>), grid, dim3(256), 0, s, x, res, stats_ws, BC, C, HW, G, g);
+  if (vec) PNSFM_LAUNCH((gn_stats_kernel<true, TS>), grid, dim3(256), 0, s, x, res, stats_ws, BC, C, HW, G, g);
+  else PNSFM_LAUNCH((gn_stats_kernel<false, TS>), grid, dim3(256), 0, s, x, res, stats_ws, BC, C, HW, G, g);
   int e = check_launch("gn_stats");
   if (e) return e;
   const double n = (double)cpg * (double)HW;
-  if (vec) PNSFM_LAUNCH((gn_apply_kernel<true>), grid, dim3(256), 0, s, x, res, gamma, beta, (const double*)stats_ws, mean, rstd, y, BC, C, HW, G, act, n, eps, g, cpg * g.nchunk);
-  else PNSFM_LAUNCH((gn_apply_kernel<false>), grid, dim3(256), 0, s, x, res, gamma, beta, (const double*)stats_ws, mean, rstd, y, BC, C, HW, G, act, n, eps, g, cpg * g.nchunk);
+  if (vec) PNSFM_LAUNCH((gn_apply_kernel<true, TS>), grid, dim3(256), 0, s, x, res, gamma, beta, (const double*)stats_ws, mean, rstd, y, BC, C, HW, G, act, n, eps, g, cpg * g.nchunk);
+  else PNSFM_LAUNCH((gn_apply_kernel<false, TS>), grid, dim3(256), 0, s, x, res, gamma, beta, (const double*)stats_ws, mean, rstd, y, BC, C, HW, G, act, n, eps, g, cpg * g.nchunk);
   return check_launch("gn_apply");
+}
+
+extern "C" {
+
+int pnsfm_groupnorm_act_forward(const float* x, const float* res, const float* gamma, const float* beta, float* y,
+                                float* mean, float* rstd, double* stats_ws, int B, int C, int HW, int G, float eps,
+                                int act, void* stream) {
+  return gn_forward<float>(x, res, gamma, beta, y, mean, rstd, stats_ws, B, C, HW, G, eps, act, stream);
+}
+
+// fp16 forward (evaluation / inference): x, res, gamma, beta, y in fp16; statistics in fp64, mean / rstd written as fp32
+int pnsfm_groupnorm_act_forward_h16(const void* x, const void* res, const void* gamma, const void* beta, void* y, float* mean, float* rstd,
+                                    int B, int C, int HW, int G, float eps, int act, void* stream) {
+  if ((((uintptr_t)x | (uintptr_t)res | (uintptr_t)y) & 7) != 0) { set_error("groupnorm_act_forward_h16: tensors must be 8-byte aligned"); return -1; }
+  return gn_forward<pnsfm_h16>((const pnsfm_h16*)x, (const pnsfm_h16*)res, (const pnsfm_h16*)gamma, (const pnsfm_h16*)beta, (pnsfm_h16*)y,
+                               mean, rstd, nullptr, B, C, HW, G, eps, act, stream);
 }
 
 int pnsfm_groupnorm_act_backward(const float* dy, const float* x, const float* res, const float* gamma,

@@ -20,8 +20,18 @@
 
 namespace pnsfm {
 
-__global__ void __launch_bounds__(256) invdepth_conv_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                                 const float* __restrict__ bias, float* __restrict__ y,
+// element loads of the streaming kernel: fp32 through the buffer descriptor (the range check is the zero padding); fp16 (the
+// evaluation / inference forward) with the same out-of-range offset marking a zero
+__device__ __forceinline__ float idc_load(const float* base, unsigned HW, unsigned off) {
+  return pnsfm_buf_load(pnsfm_make_buf(base, HW * 4u), off, 0u);
+}
+__device__ __forceinline__ float idc_load(const pnsfm_h16* base, unsigned HW, unsigned off) {
+  return off < HW * 4u ? (float)base[off >> 2] : 0.f;
+}
+
+template <class T = float>      // storage of x, w, bias, y: float, or pnsfm_h16 (fp32 arithmetic, one rounding of y)
+__global__ void __launch_bounds__(256) invdepth_conv_fwd_kernel(const T* __restrict__ x, const T* __restrict__ w,
+                                                                 const T* __restrict__ bias, T* __restrict__ y,
                                                                  int C, int H, int W, float inv_min_depth) {
   __shared__ float part[4][64];
   const int tid = threadIdx.x, lane = tid & 63, quarter = tid >> 6;
@@ -45,19 +55,19 @@ __global__ void __launch_bounds__(256) invdepth_conv_fwd_kernel(const float* __r
   float acc = 0.f;
   for (int c = c0; c < c1; ++c) {
     const int cu = PNSFM_UNIFORM(c);      // the channel is wave-uniform (one quarter per wave): scalar weight loads
-    const pnsfm_buf pb = pnsfm_make_buf(x + ((size_t)blockIdx.z * C + cu) * HW, (unsigned)HW * 4u);
-    const float* wc = w + cu * 9;
+    const T* xc = x + ((size_t)blockIdx.z * C + cu) * HW;
+    const T* wc = w + cu * 9;
     float v[9];
 #pragma unroll
-    for (int t = 0; t < 9; ++t) v[t] = pnsfm_buf_load(pb, off[t], 0u);
+    for (int t = 0; t < 9; ++t) v[t] = idc_load(xc, (unsigned)HW, off[t]);
 #pragma unroll
-    for (int t = 0; t < 9; ++t) acc = fmaf(wc[t], v[t], acc);
+    for (int t = 0; t < 9; ++t) acc = fmaf(pnsfm_ldf(wc + t), v[t], acc);
   }
   part[quarter][lane] = acc;
   __syncthreads();
   if (quarter == 0 && active) {
-    const float z = part[0][lane] + part[1][lane] + part[2][lane] + part[3][lane] + bias[0];
-    y[(size_t)blockIdx.z * HW + pix] = inv_min_depth / (1.f + expf(-z));
+    const float z = part[0][lane] + part[1][lane] + part[2][lane] + part[3][lane] + pnsfm_ldf(bias);
+    pnsfm_stf(y + (size_t)blockIdx.z * HW + pix, inv_min_depth / (1.f + expf(-z)));
   }
 }
 
@@ -262,10 +272,21 @@ int pnsfm_invdepth_conv_forward(const float* x, const float* w, const float* bia
       PNSFM_LAUNCH(invdepth_conv_fwd_strip_kernel<4>, dim3(sx_n * sy_n * B), dim3(256), 0, (hipStream_t)stream, x, w, bias, y, C, H, W,
                    sx_n, sy_n, 1.0f / min_depth);
   } else {
-    PNSFM_LAUNCH(invdepth_conv_fwd_kernel, dim3(ceil_div(H * W, 64), 1, B), dim3(256), 0, (hipStream_t)stream, x, w, bias, y,
+    PNSFM_LAUNCH(invdepth_conv_fwd_kernel<float>, dim3(ceil_div(H * W, 64), 1, B), dim3(256), 0, (hipStream_t)stream, x, w, bias, y,
                  C, H, W, 1.0f / min_depth);
   }
   return check_launch("invdepth_conv_forward");
+}
+
+// fp16 forward (evaluation / inference): x, w, bias, y in fp16, the per-pixel kernel above
+int pnsfm_invdepth_conv_forward_h16(const void* x, const void* w, const void* bias, void* y, int B, int C, int H, int W, float min_depth,
+                                    void* stream) {
+  if (B <= 0 || C <= 0 || H <= 0 || W <= 0) { set_error("invdepth_conv_forward_h16: bad shape"); return -1; }
+  if (min_depth <= 0.f) { set_error("invdepth_conv_forward_h16: min_depth must be > 0"); return -1; }
+  if ((size_t)H * W * 4 >= 0x7fffffffull) { set_error("invdepth_conv_forward_h16: plane too large"); return -1; }
+  PNSFM_LAUNCH(invdepth_conv_fwd_kernel<pnsfm_h16>, dim3(ceil_div(H * W, 64), 1, B), dim3(256), 0, (hipStream_t)stream,
+               (const pnsfm_h16*)x, (const pnsfm_h16*)w, (const pnsfm_h16*)bias, (pnsfm_h16*)y, C, H, W, 1.0f / min_depth);
+  return check_launch("invdepth_conv_forward_h16");
 }
 
 int pnsfm_invdepth_conv_backward(const float* x, const float* w, const float* dz, float* dx, float* dw, float* db, int B,

@@ -15,8 +15,9 @@ namespace pnsfm {
 // out-of-volume neighbours are read from here (pointer select keeps the loads unconditional, see conv2d.hip)
 __device__ __attribute__((aligned(16))) float pnsfm_zero_page3[64];
 
-// y[b][4c+2i+j][h][w] = x[b][c][2h+i][2w+j]; one thread per input 2x2 quad column pair
-__global__ void __launch_bounds__(256) s2d_kernel(const float* __restrict__ x, float* __restrict__ y,
+// y[b][4c+2i+j][h][w] = x[b][c][2h+i][2w+j]; one thread per input 2x2 quad column pair.  T: float, or pnsfm_h16 (fp16 forward)
+template <class T>
+__global__ void __launch_bounds__(256) s2d_kernel(const T* __restrict__ x, T* __restrict__ y,
                                                    int C, int H, int W, size_t total, size_t x_batch_stride) {
   // thread per OUTPUT element, w fastest (coalesced writes; reads are stride-2 but both parities are
   // consumed by neighbouring output channels of the same block row, i.e. served from L1/L2)
@@ -34,7 +35,8 @@ __global__ void __launch_bounds__(256) s2d_kernel(const float* __restrict__ x, f
 }
 
 // y[b][c][2h+i][2w+j] = x[b][4c+2i+j][h][w]; thread per OUTPUT element (x-fastest)
-__global__ void __launch_bounds__(256) d2s_kernel(const float* __restrict__ x, float* __restrict__ y,
+template <class T>
+__global__ void __launch_bounds__(256) d2s_kernel(const T* __restrict__ x, T* __restrict__ y,
                                                    int C, int H, int W, size_t total) {
   const int H2 = 2 * H, W2 = 2 * W;
   for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
@@ -93,12 +95,13 @@ __global__ void __launch_bounds__(256) d2s_v4_kernel(const float* __restrict__ x
 // grid: (ceil(D*HW/256), 1, B): one thread per voxel (d, y, x) -- flattened so that small planes (the 7x7 / 5x5 weight
 // volumes of the kernel composition, or 6x20 feature maps) still fill every lane -- produces all 8 features;
 // 27 branch-free neighbour loads (L1/L2 serve the overlap between neighbouring threads), 216 FMAs, 8 stores.
-template <int NF>   // number of 3-D feature maps: 8 (PackNet01) or 4 (PackNetSlim01 / PackNetSAN01, `d=num_3d_feat`)
-__global__ void __launch_bounds__(256) conv3d_fwd_kernel(const float* __restrict__ p, const float* __restrict__ w3,
-                                                          const float* __restrict__ b3, float* __restrict__ out,
+// T: storage of p, w3, b3 and out -- float, or pnsfm_h16 (fp16 forward: fp32 arithmetic, one rounding per output)
+template <int NF, class T = float>   // number of 3-D feature maps: 8 (PackNet01) or 4 (PackNetSlim01 / PackNetSAN01, `d=num_3d_feat`)
+__global__ void __launch_bounds__(256) conv3d_fwd_kernel(const T* __restrict__ p, const T* __restrict__ w3,
+                                                          const T* __restrict__ b3, T* __restrict__ out,
                                                           int D, int H, int W) {
   __shared__ float ws[NF * 27 + NF];
-  for (int i = threadIdx.x; i < NF * 27 + NF; i += 256) ws[i] = i < NF * 27 ? w3[i] : (b3 ? b3[i - NF * 27] : 0.f);
+  for (int i = threadIdx.x; i < NF * 27 + NF; i += 256) ws[i] = i < NF * 27 ? pnsfm_ldf(w3 + i) : (b3 ? pnsfm_ldf(b3 + (i - NF * 27)) : 0.f);
   __syncthreads();
   const int HW = H * W, DHW = D * HW;
   const int vox = blockIdx.x * 256 + threadIdx.x;
@@ -107,7 +110,7 @@ __global__ void __launch_bounds__(256) conv3d_fwd_kernel(const float* __restrict
   const int d = active ? vox / HW : 0;
   const int pix = active ? vox - d * HW : 0;
   const int y = pix / W, x = pix - y * W;
-  const float* pb = p + (size_t)b * DHW;
+  const T* pb = p + (size_t)b * DHW;
   float v[27];
 #pragma unroll
   for (int dz = 0; dz < 3; ++dz) {
@@ -119,8 +122,8 @@ __global__ void __launch_bounds__(256) conv3d_fwd_kernel(const float* __restrict
       for (int dx = 0; dx < 3; ++dx) {
         const int xx = x + dx - 1;
         const bool ok = active && dd >= 0 && dd < D && yy >= 0 && yy < H && xx >= 0 && xx < W;
-        const float* src = ok ? pb + (dd * HW + yy * W + xx) : pnsfm_zero_page3;
-        v[dz * 9 + dy * 3 + dx] = *src;
+        const T* src = ok ? pb + (dd * HW + yy * W + xx) : reinterpret_cast<const T*>(pnsfm_zero_page3);
+        v[dz * 9 + dy * 3 + dx] = pnsfm_ldf(src);
       }
     }
   }
@@ -132,9 +135,9 @@ __global__ void __launch_bounds__(256) conv3d_fwd_kernel(const float* __restrict
 #pragma unroll
     for (int f = 0; f < NF; ++f) acc[f] = fmaf(ws[f * 27 + tap], v[tap], acc[f]);
   if (active) {
-    float* ob = out + (size_t)b * NF * DHW + vox;
+    T* ob = out + (size_t)b * NF * DHW + vox;
 #pragma unroll
-    for (int f = 0; f < NF; ++f) ob[(size_t)f * DHW] = acc[f];
+    for (int f = 0; f < NF; ++f) pnsfm_stf(ob + (size_t)f * DHW, acc[f]);
   }
 }
 
@@ -641,7 +644,7 @@ int pnsfm_space_to_depth_strided(const float* x, float* y, int B, int C, int H, 
     const unsigned total_q = (unsigned)(total / 16);      // one thread per 2 x 8 input block
     PNSFM_LAUNCH(s2d_v4_kernel, dim3((total_q + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, y, C, H, W, total_q, x_batch_stride);
   } else {
-    PNSFM_LAUNCH(s2d_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, x, y, C, H, W, total, x_batch_stride);
+    PNSFM_LAUNCH(s2d_kernel<float>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, x, y, C, H, W, total, x_batch_stride);
   }
   return check_launch("space_to_depth");
 }
@@ -656,7 +659,7 @@ int pnsfm_depth_to_space(const float* x, float* y, int B, int C, int H, int W, v
     const unsigned total_q = (unsigned)(total / 16);      // one thread per four 4-wide channel rows
     PNSFM_LAUNCH(d2s_v4_kernel, dim3((total_q + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, y, C, H, W, total_q);
   } else {
-    PNSFM_LAUNCH(d2s_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, x, y, C, H, W, total);
+    PNSFM_LAUNCH(d2s_kernel<float>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, x, y, C, H, W, total);
   }
   return check_launch("depth_to_space");
 }
@@ -680,6 +683,31 @@ int pnsfm_conv3d_forward(const float* p, const float* w3, const float* b3, float
   if (NF == 8) PNSFM_LAUNCH((conv3d_fwd_kernel<8>), grid, dim3(256), 0, (hipStream_t)stream, p, w3, b3, out, D, H, W);
   else PNSFM_LAUNCH((conv3d_fwd_kernel<4>), grid, dim3(256), 0, (hipStream_t)stream, p, w3, b3, out, D, H, W);
   return check_launch("conv3d_forward");
+}
+
+// ---- fp16 forward (evaluation / inference): the per-element kernels above on 2-byte storage
+int pnsfm_space_to_depth_h16(const void* x, void* y, int B, int C, int H, int W, void* stream) {
+  if ((H & 1) || (W & 1)) { set_error("space_to_depth_h16: H, W must be even (got %d x %d)", H, W); return -1; }
+  const size_t total = (size_t)B * C * H * W;
+  PNSFM_LAUNCH(s2d_kernel<pnsfm_h16>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const pnsfm_h16*)x, (pnsfm_h16*)y, C, H,
+               W, total, (size_t)C * H * W);
+  return check_launch("space_to_depth_h16");
+}
+
+int pnsfm_depth_to_space_h16(const void* x, void* y, int B, int C, int H, int W, void* stream) {
+  const size_t total = (size_t)B * C * 4 * H * W;
+  PNSFM_LAUNCH(d2s_kernel<pnsfm_h16>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const pnsfm_h16*)x, (pnsfm_h16*)y, C, H,
+               W, total);
+  return check_launch("depth_to_space_h16");
+}
+
+int pnsfm_conv3d_forward_h16(const void* p, const void* w3, const void* b3, void* out, int B, int D, int H, int W, int NF, void* stream) {
+  if (!nf_ok(NF, "conv3d_forward_h16")) return -1;
+  const dim3 grid(ceil_div(D * H * W, 256), 1, B);
+  const pnsfm_h16 *ph = (const pnsfm_h16*)p, *wh = (const pnsfm_h16*)w3, *bh = (const pnsfm_h16*)b3;
+  if (NF == 8) PNSFM_LAUNCH((conv3d_fwd_kernel<8, pnsfm_h16>), grid, dim3(256), 0, (hipStream_t)stream, ph, wh, bh, (pnsfm_h16*)out, D, H, W);
+  else PNSFM_LAUNCH((conv3d_fwd_kernel<4, pnsfm_h16>), grid, dim3(256), 0, (hipStream_t)stream, ph, wh, bh, (pnsfm_h16*)out, D, H, W);
+  return check_launch("conv3d_forward_h16");
 }
 
 int pnsfm_conv3d_backward_data(const float* dout, const float* w3, float* dp, int B, int D, int H, int W, int NF, void* stream) {

@@ -51,6 +51,26 @@ static inline void pnsfm_dma16(const pnsfm_dma_buf& b, unsigned voff, float* lds
 }
 #define PNSFM_UNIFORM(i) (i)
 static inline void pnsfm_dma_wait() {}
+// fp16 forward (conv2d_h16.h): v_mfma_f32_32x32x16_f16 has the bf16 form's fragment layout (lane l: A[m = l&31][k = 8*(l>>5) + i],
+// B[k = 8*(l>>5) + i][n = l&31], i = 0..7); modelled like hipemu's bf16 form -- exact products, summed in double, rounded once
+typedef _Float16 pnsfm_h16x8 __attribute__((ext_vector_type(8)));
+static inline f32x16 pnsfm_mfma_f16(pnsfm_h16x8 a, pnsfm_h16x8 b, f32x16 c) {
+  hipemu::WaveState& W = hipemu::my_wave();
+  const int l = hipemu::my_lane();
+  for (int i = 0; i < 8; ++i) { W.a8[l][i] = (float)a[i]; W.b8[l][i] = (float)b[i]; }
+  hipemu::wave_barrier(W);
+  const int col = l & 31;
+  for (int r = 0; r < 16; ++r) {
+    const int row = (r & 3) + 8 * (r >> 2) + 4 * (l >> 5);
+    double acc = c[r];
+    for (int h = 0; h < 2; ++h)
+      for (int i = 0; i < 8; ++i) acc += (double)W.a8[row + 32 * h][i] * (double)W.b8[col + 32 * h][i];
+    c[r] = (float)acc;
+  }
+  hipemu::wave_barrier(W);
+  return c;
+}
+
 // workgroup barriers with explicit counter waits (conv2d_bx3pp.h): the emulator's barrier is a full one either way
 #define PNSFM_BARRIER_ALL() __syncthreads()
 #define PNSFM_BARRIER_LDS() __syncthreads()
@@ -85,6 +105,11 @@ __device__ __forceinline__ f32x16 pnsfm_mfma_bf16(pnsfm_u32x4 a, pnsfm_u32x4 b, 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ f32x4 pnsfm_mfma_bf16_16(pnsfm_u32x4 a, pnsfm_u32x4 b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(pnsfm_bf16x8, a), __builtin_bit_cast(pnsfm_bf16x8, b), c, 0, 0, 0);
+}
+// v_mfma_f32_32x32x16_f16: the bf16 form's fragment layout and cycle count with fp16 operands (fp16 x fp16 products are exact in fp32)
+typedef _Float16 pnsfm_h16x8 __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ f32x16 pnsfm_mfma_f16(pnsfm_h16x8 a, pnsfm_h16x8 b, f32x16 c) {
+  return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
 }
 __device__ __forceinline__ unsigned pnsfm_f2u(float v) { return __float_as_uint(v); }
 __device__ __forceinline__ float pnsfm_u2f(unsigned u) { return __uint_as_float(u); }
@@ -163,6 +188,28 @@ __device__ __forceinline__ float pnsfm_buf_load(const pnsfm_buf& b, unsigned vof
 
 #include <cstddef>
 #include <cstdint>
+
+// ---- fp16 storage (evaluation / inference forward, include/pnsfm.h "fp16 forward").  Activations and parameters are stored as IEEE
+// half; every kernel computes in fp32 and rounds its output ONCE to nearest-even ((_Float16)v is v_cvt_f16_f32 in the default
+// round-to-nearest mode, never the round-toward-zero v_cvt_pkrtz form).  The storage-templated kernels load / store through these
+// helpers; the float overloads are the plain accesses the fp32 kernels always made.
+typedef _Float16 pnsfm_h16;
+typedef _Float16 pnsfm_h16x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float pnsfm_ldf(const float* p) { return *p; }
+__device__ __forceinline__ float pnsfm_ldf(const pnsfm_h16* p) { return (float)*p; }
+__device__ __forceinline__ void pnsfm_stf(float* p, float v) { *p = v; }
+__device__ __forceinline__ void pnsfm_stf(pnsfm_h16* p, float v) { *p = (pnsfm_h16)v; }
+__device__ __forceinline__ float4 pnsfm_ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ float4 pnsfm_ld4(const pnsfm_h16* p) {
+  const pnsfm_h16x4 v = *reinterpret_cast<const pnsfm_h16x4*>(p);
+  return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
+}
+__device__ __forceinline__ void pnsfm_st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
+__device__ __forceinline__ void pnsfm_st4(pnsfm_h16* p, float4 v) {
+  pnsfm_h16x4 h;
+  h[0] = (pnsfm_h16)v.x; h[1] = (pnsfm_h16)v.y; h[2] = (pnsfm_h16)v.z; h[3] = (pnsfm_h16)v.w;
+  *reinterpret_cast<pnsfm_h16x4*>(p) = h;
+}
 
 namespace pnsfm {
 

@@ -78,6 +78,18 @@ SIGNATURES = {
     "pnsfm_smoothness_norm_forward": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
     "pnsfm_smoothness_norm_backward": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "pnsfm_region_ops": (_i, [_p, _i, _p]),
+    # fp16 forward (evaluation / inference)
+    "pnsfm_conv2d_packed_elems_h16": (_sz, [_i, _i, _i]),
+    "pnsfm_set_h16_max_split": (_i, [_i]),
+    "pnsfm_conv2d_pack_weights_h16": (_i, [_p, _i, _p, _i, _i, _i, _p]),
+    "pnsfm_conv2d_forward_h16": (_i, [_p, _i, _p, _i, _p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "pnsfm_groupnorm_act_forward_h16": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _i, _p]),
+    "pnsfm_conv3d_forward_h16": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "pnsfm_space_to_depth_h16": (_i, [_p, _p, _i, _i, _i, _i, _p]),
+    "pnsfm_depth_to_space_h16": (_i, [_p, _p, _i, _i, _i, _i, _p]),
+    "pnsfm_upsample_nearest_forward_h16": (_i, [_p, _p, _i, _i, _i, _i, _p]),
+    "pnsfm_invdepth_conv_forward_h16": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _f, _p]),
+    "pnsfm_region_ops_h16": (_i, [_p, _i, _p]),
     "pnsfm_photometric_l1_forward": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p]),
     "pnsfm_photometric_l1_backward": (_i, [_p, _p, _p, _p, _f, _p, _i, _i, _i, _i, _i, _i, _p]),
     "pnsfm_smoothness_forward": (_i, [_p, _p, _p, _i, _i, _i, _p]),

@@ -56,8 +56,12 @@ except ImportError:      # older torch: callers must invalidate themselves (Flat
 class PackedConvWeight:
     """Per-layer cache of the MFMA-friendly weight layouts ([k*k][K][M], see csrc/conv2d.hip).
 
-    Re-packed only when the parameter changed (tensor version / storage / optimizer epoch), so eval loops and the
+    Re-packed only when the parameter changed (tensor version / storage / optimizer epoch / dtype), so eval loops and the
     backward pass of the same step reuse the buffers.  Cost when stale: one read + two writes of the weight.
+    The cache keeps an alias of the tensor it packed (`_src_*`): the key names that tensor's storage by its address, and an address
+    is only unique while the storage is alive.  `module.half().float()` swaps a parameter's `.data` without touching its version
+    counter; without the alias the freed fp32 storage could be handed back to the new fp32 tensor, giving an identical key over
+    different (fp16-rounded) values.  In training the alias shares the parameter's storage: no extra memory.
     """
 
     def __init__(self, volatile=False):
@@ -65,9 +69,16 @@ class PackedConvWeight:
         self.wp_bwd = None
         self.key_fwd = None
         self.key_bwd = None
+        self._src_f = None            # alias of the tensor behind key_fwd / key_bwd / key_h16 (see the class comment)
+        self._src_b = None
+        self._src_h16 = None
         self.volatile = volatile      # weight is a freshly computed tensor every call (e.g. a composed kernel): always repack
         self._serial = 0
         self._weight_ref = None       # the parameter this cache last packed (repack_all re-packs it in the batched launch)
+        self.wp_h16 = None            # fp16 forward (evaluation / inference): packed fp16 image + fp32 copy of the bias
+        self.bias_h16 = None
+        self.key_h16 = None
+        self.shape_h16 = None
 
     def get(self, weight, need_bwd):
         if self.volatile:
@@ -75,7 +86,7 @@ class PackedConvWeight:
             key = ('volatile', self._serial)
         else:
             # (torch.Size and torch.device compare and hash natively: no tuple() / str() per call -- ~300 calls per step)
-            key = (weight._version, weight.data_ptr(), _WEIGHT_EPOCH[0], weight.shape, weight.device)
+            key = (weight._version, weight.data_ptr(), _WEIGHT_EPOCH[0], weight.shape, weight.device, weight.dtype)
         do_f = self.key_fwd != key
         do_b = need_bwd and self.key_bwd != key
         if do_f or do_b:
@@ -86,17 +97,33 @@ class PackedConvWeight:
                 self.wp_bwd = None
             f, b = ops.conv2d_pack(w.contiguous(), self.wp_fwd if do_f else None, self.wp_bwd if do_b else None,
                                    want_fwd=do_f, want_bwd=do_b)
+            held = None if self.volatile else w
             if do_f:
-                self.wp_fwd, self.key_fwd = f, key
+                self.wp_fwd, self.key_fwd, self._src_f = f, key, held
             if do_b:
-                self.wp_bwd, self.key_bwd = b, key
+                self.wp_bwd, self.key_bwd, self._src_b = b, key, held
             if not self.volatile and weight.is_leaf and weight.requires_grad:
                 _register_packed(self, weight)
         return self.wp_fwd, (self.wp_bwd if need_bwd else None)
 
     @staticmethod
     def key_of(weight):
-        return (weight._version, weight.data_ptr(), _WEIGHT_EPOCH[0], weight.shape, weight.device)
+        return (weight._version, weight.data_ptr(), _WEIGHT_EPOCH[0], weight.shape, weight.device, weight.dtype)
+
+    def get_h16(self, weight, bias, key=None, hold=None):
+        """(packed fp16 weight, fp32 bias or None) of the fp16 forward.  `weight` is fp16 (a layer's parameter) or fp32 (a composed
+        weight: then `key` names the parameters it was built from and `hold` is those parameters, kept alive with the key).  Never
+        registered for the optimizer's batched repack."""
+        if key is None:
+            key = (self.key_of(weight), None if bias is None else self.key_of(bias))
+            hold = (weight, bias)
+        if self.key_h16 != key:
+            self._src_h16 = tuple(None if t is None else t.detach() for t in hold)
+            self.wp_h16 = ops.conv2d_pack_h16(weight.detach().contiguous(), self.wp_h16)
+            self.bias_h16 = None if bias is None else bias.detach().float().contiguous()
+            self.shape_h16 = tuple(weight.shape)
+            self.key_h16 = key
+        return self.wp_h16, self.bias_h16
 
 
 # ---- batched re-pack: every conv weight of the model in ONE launch, right after the optimizer step ----------------------------
@@ -172,7 +199,9 @@ def repack_all(exclude=None):
 
 def stamp_packed(pairs):
     for c, w in pairs:
-        c.key_fwd = c.key_bwd = PackedConvWeight.key_of(w)
+        k = c.key_fwd = c.key_bwd = PackedConvWeight.key_of(w)
+        if c._src_f is None or c._src_f.data_ptr() != k[1] or c._src_b is not c._src_f:
+            c._src_f = c._src_b = w.detach()
 
 
 class _nullctx:
@@ -449,6 +478,71 @@ def branch_stream(t):
     return st
 
 
+# ---- fp16 forward (evaluation / inference; include/pnsfm.h "fp16 forward") ---------------------------------------------------------
+# fp16 activations dispatch to the _h16 kernels here, before any fp32 code path runs (the block sequencer never sees fp16).  Forward
+# only: with grad disabled the ops are called directly; with grad enabled the result carries a node whose backward raises.
+_H16_ONLY_FWD = "fp16 is supported for the forward pass only (evaluation / inference); train in float32"
+
+
+class _H16ForwardOnlyFn(Function):
+    @staticmethod
+    def forward(ctx, fn, *args):
+        return fn(*args)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        raise NotImplementedError(_H16_ONLY_FWD)
+
+
+def _h16_run(fn, *args):
+    if torch.is_grad_enabled() and any(torch.is_tensor(a) and a.requires_grad for a in args):
+        return _H16ForwardOnlyFn.apply(fn, *args)
+    return fn(*args)
+
+
+def _h16_params(*params):
+    """Mixed precision is an error, as F.conv2d makes it one in the reference: fp16 activations need fp16 parameters."""
+    for p in params:
+        if p is not None and p.dtype != torch.float16:
+            raise RuntimeError("fp16 input into a %s layer: convert the network with .half() / .to(dtype=torch.float16)" % p.dtype)
+
+
+def _h16_input(x, *params):
+    """x is fp32 but a parameter is fp16: the reverse mix, named clearly instead of failing inside a kernel wrapper."""
+    for p in params:
+        if p is not None and p.dtype == torch.float16:
+            raise RuntimeError("%s input into a float16 network: cast the input with .half()" % x.dtype)
+
+
+def _conv2d_h16(xs, weight, bias, cache):
+    _h16_params(weight, bias)
+    Cout, Cin, ks, _ = weight.shape
+    if sum(t.shape[1] for t in xs) != Cin:
+        raise RuntimeError("conv2d: inputs have %d channels, weight expects %d" % (sum(t.shape[1] for t in xs), Cin))
+    wp, b32 = cache.get_h16(weight, bias)
+    return _h16_run(lambda *a: ops.conv2d_forward_h16(tuple(t.contiguous() for t in a[:len(xs)]), wp, b32, Cout, ks), *xs, weight, bias)
+
+
+def _groupnorm_act_h16(x, gamma, beta, G, eps, act, res=None):
+    _h16_params(gamma, beta)
+    if res is not None and res.dtype != torch.float16:
+        raise RuntimeError("groupnorm_act: fp16 input with a %s residual" % res.dtype)
+    return _h16_run(lambda x, r, g, b: ops.groupnorm_act_forward_h16(x.contiguous(), None if r is None else r.contiguous(), g.detach(),
+                                                                     b.detach(), G, eps, act), x, res, gamma, beta)
+
+
+def conv2d_h16_composed(P, W_eff, bias_eff, cache, key):
+    """fp16 forward of the collapsed packing convolution: W_eff / bias_eff are fp32 (composed from the upcast fp16 parameters); the
+    packed fp16 image and the fp32 bias are cached on `key` (the parameters' keys: eval weights do not change).  W_eff may be None
+    when the cache already holds `key`."""
+    if W_eff is not None:
+        cache.get_h16(W_eff, bias_eff, key=key)
+    if cache.key_h16 != key:
+        raise RuntimeError("conv2d_h16_composed: no packed weight for these parameters")
+    Cout, _, ks, _ = cache.shape_h16
+    return ops.conv2d_forward_h16((P.contiguous(),), cache.wp_h16, cache.bias_h16, Cout, ks)
+
+
 class Conv2dFn(Function):
     """y = conv2d(zero_pad_{k//2}(x), weight) + bias, stride 1 (fp32 implicit GEMM on the matrix pipe; arithmetic: set_conv_math)."""
 
@@ -512,6 +606,9 @@ class Conv2dFn(Function):
 
 
 def conv2d(x, weight, bias, cache):
+    if x.dtype == torch.float16:
+        return _conv2d_h16((x,), weight, bias, cache)
+    _h16_input(x, weight)
     return Conv2dFn.apply(x, weight, bias, cache, torch.is_grad_enabled())
 
 
@@ -551,6 +648,8 @@ def _tap_ok(weight):
 
 def conv2d_tap(x, weight, bias, cache):
     """(conv2d(x), x_tap)."""
+    if x.dtype == torch.float16:
+        return _conv2d_h16((x,), weight, bias, cache), x
     if not (_GRAD_TAPS and torch.is_grad_enabled() and x.requires_grad and _tap_ok(weight)):
         return conv2d(x, weight, bias, cache), x
     return Conv2dFn.apply(x, weight, bias, cache, True, True)
@@ -649,6 +748,8 @@ def conv2d_cat(xs, weight, bias, cache):
     """xs: tuple of 2 or 3 NCHW tensors.  Falls back to torch.cat + conv2d when the shape is outside the multi-source FORWARD
     kernel's envelope (first / second tensor not ending on a 16-channel boundary, < 16 channels, f32 arithmetic mode); a shape
     the forward takes but the multi-source weight-gradient kernels do not concatenates for that one kernel only."""
+    if xs[0].dtype == torch.float16:
+        return _conv2d_h16(tuple(xs), weight, bias, cache)
     import os
     C0 = xs[0].shape[1]
     ok = os.environ.get('PNSFM_CAT_FOLD', '1') != '0' and len(xs) in (2, 3) and C0 % 16 == 0 and (len(xs) == 2 or (C0 + xs[1].shape[1]) % 16 == 0) and get_conv_math() == 'bx3' \
@@ -770,6 +871,9 @@ def set_conv_gn_fuse(on):
 def conv2d_gn_act(x, weight, bias, gamma, beta, cache, G=16, eps=1e-5, act=ops.ACT_ELU):
     """The Conv2D block: x a tensor or a tuple of 2-3 tensors standing for their channel concatenation."""
     xs = tuple(x) if isinstance(x, (tuple, list)) else (x,)
+    if xs[0].dtype == torch.float16:
+        return _groupnorm_act_h16(_conv2d_h16(xs, weight, bias, cache), gamma, beta, G, eps, act)
+    _h16_input(xs[0], weight)
     if len(xs) > 1:
         C0 = xs[0].shape[1]
         fold = os.environ.get('PNSFM_CAT_FOLD', '1') != '0' and len(xs) in (2, 3) and C0 % 16 == 0 and \
@@ -785,6 +889,8 @@ def conv2d_gn_act(x, weight, bias, gamma, beta, cache, G=16, eps=1e-5, act=ops.A
 
 def conv2d_gn_act_tap(x, weight, bias, gamma, beta, cache, G=16, eps=1e-5, act=ops.ACT_ELU):
     """The Conv2D block with a gradient tap on its (single-tensor) input: (out, x_tap) -- see conv2d_tap."""
+    if torch.is_tensor(x) and x.dtype == torch.float16:
+        return conv2d_gn_act(x, weight, bias, gamma, beta, cache, G, eps, act), x
     if not (_GRAD_TAPS and _CONV_GN_FUSE and torch.is_grad_enabled() and torch.is_tensor(x) and x.requires_grad and _tap_ok(weight)):
         return conv2d_gn_act(x, weight, bias, gamma, beta, cache, G, eps, act), x
     return ConvGnActFn.apply(weight, bias, gamma, beta, cache, True, False, G, eps, act, True, x)
@@ -870,6 +976,8 @@ class GroupNormActFn(Function):
 
 
 def groupnorm_act(x, gamma, beta, G=16, eps=1e-5, act=ops.ACT_ELU, res=None):
+    if x.dtype == torch.float16:
+        return _groupnorm_act_h16(x, gamma, beta, G, eps, act, res)
     return GroupNormActFn.apply(x, res, gamma, beta, G, eps, act)
 
 
@@ -896,10 +1004,14 @@ class DepthToSpaceFn(Function):
 
 
 def space_to_depth(x):
+    if x.dtype == torch.float16:
+        return _h16_run(ops.space_to_depth_h16, x)
     return SpaceToDepthFn.apply(x)
 
 
 def depth_to_space(x):
+    if x.dtype == torch.float16:
+        return _h16_run(lambda t: ops.depth_to_space_h16(t.contiguous()), x)
     return DepthToSpaceFn.apply(x)
 
 
@@ -939,6 +1051,11 @@ class Conv3d1to8Fn(Function):
 
 
 def conv3d_1to8(p, w3, b3):
+    if p.dtype == torch.float16:
+        _h16_params(w3, b3)
+        return _h16_run(lambda p, w, b: ops.conv3d_forward_h16(p.contiguous(), w.detach().contiguous(), None if b is None else b.detach()),
+                        p, w3, b3)
+    _h16_input(p, w3)
     return Conv3d1to8Fn.apply(p, w3, b3, torch.is_grad_enabled())
 
 
@@ -1030,6 +1147,43 @@ def _R(op, dst, src=None):
     return (op, dst, src)
 
 
+# Forward bodies of the collapsed packing block's three strip Functions, shared with the fp16 forward: `run` is ops.region_ops (fp32)
+# or ops.region_ops_h16 (fp16 windows) -- one list of windows for both.
+def _border_split_fwd(P, S, lr_t, run):
+    B, C, h, w = P.shape
+    tb = P.new_empty((2 * B, C, S, w))
+    # lr_t (round 6): the column strips are stored TRANSPOSED, [2B, C, S, h] -- rows of h pixels instead of rows of S = 3 / 5 --
+    # so that every kernel behind them (Conv3d stencil, convolution, weight gradient) sees a map as wide as the row strips'
+    lr = P.new_empty((2 * B, C, S, h)) if lr_t else P.new_empty((2 * B, C, h, S))
+    lrv = lr.transpose(2, 3) if lr_t else lr
+    run([_R(ops.REGION_COPY, tb[:B], P[:, :, :S]), _R(ops.REGION_COPY, tb[B:], P[:, :, h - S:]),
+         _R(ops.REGION_COPY, lrv[:B], P[:, :, :, :S]), _R(ops.REGION_COPY, lrv[B:], P[:, :, :, w - S:])])
+    return tb, lr
+
+
+def _strip_select_fwd(z, B, r, dim, run):
+    n2 = 2 * r
+    if dim == 2:
+        out = z.new_empty((z.shape[0], z.shape[1], n2, z.shape[3]))
+        run([_R(ops.REGION_COPY, out[:B], z[:B, :, :n2]), _R(ops.REGION_COPY, out[B:], z[B:, :, 1:])])
+    else:
+        out = z.new_empty((z.shape[0], z.shape[1], z.shape[2], n2))
+        run([_R(ops.REGION_COPY, out[:B], z[:B, :, :, :n2]), _R(ops.REGION_COPY, out[B:], z[B:, :, :, 1:])])
+    return out
+
+
+def _border_paste_fwd(y, o_tb, o_lr, r, lr_t, run):
+    """Pastes in place into y; o_tb / o_lr contiguous.  Returns y."""
+    B, h, w = y.shape[0], y.shape[2], y.shape[3]
+    if lr_t:                     # [2B, C, 2r, h] holds the column strips transposed
+        o_lr = o_lr.transpose(2, 3)
+    run([_R(ops.REGION_COPY, y[:, :, r:h - r, :r], o_lr[:B, :, r:h - r, :r]),
+         _R(ops.REGION_COPY, y[:, :, r:h - r, w - r:], o_lr[B:, :, r:h - r, r:]),
+         _R(ops.REGION_COPY, y[:, :, :r], o_tb[:B, :, :r]),
+         _R(ops.REGION_COPY, y[:, :, h - r:], o_tb[B:, :, r:])])
+    return y
+
+
 class PackBorderSplitFn(Function):
     """Collapsed packing block, input side: P -> (P itself for the interior convolution, the top+bottom row strips,
     the left+right column strips; strips batched along dim 0).  Plain slicing would make autograd zero-fill and add a
@@ -1038,15 +1192,8 @@ class PackBorderSplitFn(Function):
 
     @staticmethod
     def forward(ctx, P, S, lr_t=False):
-        B, C, h, w = P.shape
         ctx.S, ctx.lr_t = S, lr_t
-        tb = P.new_empty((2 * B, C, S, w))
-        # lr_t (round 6): the column strips are stored TRANSPOSED, [2B, C, S, h] -- rows of h pixels instead of rows of S = 3 / 5 --
-        # so that every kernel behind them (Conv3d stencil, convolution, weight gradient) sees a map as wide as the row strips'
-        lr = P.new_empty((2 * B, C, S, h)) if lr_t else P.new_empty((2 * B, C, h, S))
-        lrv = lr.transpose(2, 3) if lr_t else lr
-        ops.region_ops([_R(ops.REGION_COPY, tb[:B], P[:, :, :S]), _R(ops.REGION_COPY, tb[B:], P[:, :, h - S:]),
-                        _R(ops.REGION_COPY, lrv[:B], P[:, :, :, :S]), _R(ops.REGION_COPY, lrv[B:], P[:, :, :, w - S:])])
+        tb, lr = _border_split_fwd(P, S, lr_t, ops.region_ops)
         return P.view_as(P), tb, lr
 
     @staticmethod
@@ -1078,6 +1225,8 @@ class PackBorderSplitFn(Function):
 
 
 def pack_border_split(P, S, lr_t=False):
+    if P.dtype == torch.float16:
+        return (P,) + tuple(_h16_run(lambda P: _border_split_fwd(P, S, lr_t, ops.region_ops_h16), P))
     return PackBorderSplitFn.apply(P, S, lr_t)
 
 
@@ -1089,14 +1238,7 @@ class StripSelectFn(Function):
     @staticmethod
     def forward(ctx, z, B, r, dim):
         ctx.meta = (B, r, dim, tuple(z.shape))
-        n2 = 2 * r
-        if dim == 2:
-            out = z.new_empty((z.shape[0], z.shape[1], n2, z.shape[3]))
-            ops.region_ops([_R(ops.REGION_COPY, out[:B], z[:B, :, :n2]), _R(ops.REGION_COPY, out[B:], z[B:, :, 1:])])
-        else:
-            out = z.new_empty((z.shape[0], z.shape[1], z.shape[2], n2))
-            ops.region_ops([_R(ops.REGION_COPY, out[:B], z[:B, :, :, :n2]), _R(ops.REGION_COPY, out[B:], z[B:, :, :, 1:])])
-        return out
+        return _strip_select_fwd(z, B, r, dim, ops.region_ops)
 
     @staticmethod
     @once_differentiable
@@ -1115,6 +1257,8 @@ class StripSelectFn(Function):
 
 
 def strip_select(z, B, r, dim):
+    if z.dtype == torch.float16:
+        return _h16_run(lambda z: _strip_select_fwd(z, B, r, dim, ops.region_ops_h16), z)
     return StripSelectFn.apply(z, B, r, dim)
 
 
@@ -1126,16 +1270,10 @@ class PackBorderPasteFn(Function):
 
     @staticmethod
     def forward(ctx, y, o_tb, o_lr, r, lr_t=False):
-        B, h, w = y.shape[0], y.shape[2], y.shape[3]
         ctx.r, ctx.lr_t = r, lr_t
         o_tb, o_lr = o_tb.contiguous(), o_lr.contiguous()
         s_lr = tuple(o_lr.shape)
-        if lr_t:                     # [2B, C, 2r, h] holds the column strips transposed
-            o_lr = o_lr.transpose(2, 3)
-        ops.region_ops([_R(ops.REGION_COPY, y[:, :, r:h - r, :r], o_lr[:B, :, r:h - r, :r]),
-                        _R(ops.REGION_COPY, y[:, :, r:h - r, w - r:], o_lr[B:, :, r:h - r, r:]),
-                        _R(ops.REGION_COPY, y[:, :, :r], o_tb[:B, :, :r]),
-                        _R(ops.REGION_COPY, y[:, :, h - r:], o_tb[B:, :, r:])])
+        _border_paste_fwd(y, o_tb, o_lr, r, lr_t, ops.region_ops)
         ctx.mark_dirty(y)
         ctx.shapes = (tuple(o_tb.shape), s_lr)
         return y
@@ -1166,6 +1304,10 @@ class PackBorderPasteFn(Function):
 
 
 def pack_border_paste(y, o_tb, o_lr, r, lr_t=False):
+    if y.dtype == torch.float16:
+        if torch.is_grad_enabled() and any(t.requires_grad for t in (y, o_tb, o_lr)):
+            raise NotImplementedError(_H16_ONLY_FWD)      # (in place into y: the collapsed fp16 block runs it inside its forward-only node)
+        return _border_paste_fwd(y, o_tb.contiguous(), o_lr.contiguous(), r, lr_t, ops.region_ops_h16)
     return PackBorderPasteFn.apply(y, o_tb, o_lr, r, lr_t)
 
 
@@ -1210,6 +1352,11 @@ class InvDepthConvFn(Function):
 
 
 def invdepth_conv(x, weight, bias, min_depth):
+    if x.dtype == torch.float16:
+        _h16_params(weight, bias)
+        return _h16_run(lambda x, w, b: ops.invdepth_conv_forward_h16(x.contiguous(), w.detach().contiguous(), b.detach(), min_depth),
+                        x, weight, bias)
+    _h16_input(x, weight)
     return InvDepthConvFn.apply(x, weight, bias, min_depth)
 
 
@@ -1258,6 +1405,8 @@ def upsample_nearest(x, size=None, scale_factor=None):
         H, W = int(h * scale_factor), int(w * scale_factor)
     s = H // h if h else 0
     from . import _lib
+    if x.dtype == torch.float16 and s >= 1 and (H, W) == (h * s, w * s) and (W % 4) == 0:
+        return x if s == 1 else _h16_run(lambda t: ops.upsample_nearest_forward_h16(t.contiguous(), s), x)
     if s >= 1 and (H, W) == (h * s, w * s) and (x.is_cuda or not _lib.REQUIRE_CUDA) and ops.upsample_nearest_ok(x, s):
         return x if s == 1 else UpsampleNearestFn.apply(x, s)
     if size is not None:

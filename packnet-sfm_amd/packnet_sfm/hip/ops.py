@@ -971,6 +971,142 @@ def region_ops(items):
         _lib.check(_lib.get().pnsfm_region_ops(ctypes.byref(arr), len(chunk), _stream(ref)), "region_ops")
 
 
+
+# ------------------------------------------------------------------------- fp16 forward (evaluation / inference)
+# include/pnsfm.h "fp16 forward": fp16 storage, fp32 arithmetic, one round-to-nearest-even per kernel output.  Forward only.
+def _h16(*tensors):
+    for t in tensors:
+        if t is not None and t.dtype != torch.float16:
+            raise RuntimeError("packnet_sfm fp16 HIP op needs float16 tensors, got %s" % t.dtype)
+
+
+def conv2d_pack_h16(w, out=None):
+    """w [Cout, Cin, k, k] fp16 (a plain layer) or fp32 (the composed weight of a collapsed packing layer) -> packed fp16 operand image
+    of the fp16 forward kernel."""
+    _chk(w, out)
+    if w.dtype not in (torch.float16, torch.float32):
+        raise RuntimeError("conv2d_pack_h16: weight must be float16 or float32, got %s" % w.dtype)
+    Cout, Cin, ks, _ = w.shape
+    n = int(_lib.get().pnsfm_conv2d_packed_elems_h16(Cin, Cout, ks))
+    if out is None or out.numel() != n or out.device != w.device:
+        out = torch.empty(n, dtype=torch.float16, device=w.device)
+    _h16(out)
+    _lib.check(_lib.get().pnsfm_conv2d_pack_weights_h16(_ptr(w), 1 if w.dtype == torch.float32 else 0, _ptr(out), Cin, Cout, ks,
+                                                         _stream(w)), "conv2d_pack_weights_h16")
+    return out
+
+
+def conv2d_forward_h16(xs, wp, bias, Cout, ks):
+    """xs: 1..3 fp16 NCHW tensors (their channel concatenation is the input); wp from conv2d_pack_h16; bias fp32 [Cout] or None."""
+    xs = tuple(xs)
+    if not 1 <= len(xs) <= 3:
+        raise RuntimeError("conv2d_forward_h16: 1 to 3 input tensors")
+    _chk(*xs, wp, bias); _h16(*xs, wp); _f32(bias)
+    B, _, H, W = xs[0].shape
+    for t in xs[1:]:
+        if t.shape[0] != B or tuple(t.shape[2:]) != (H, W):
+            raise RuntimeError("conv2d_forward_h16: inputs of different batch / spatial sizes")
+    C = [t.shape[1] for t in xs] + [0] * (3 - len(xs))
+    P = [xs[i] if i < len(xs) else None for i in range(3)]
+    y = torch.empty((B, Cout, H, W), dtype=torch.float16, device=xs[0].device)
+    rc = _lib.get().pnsfm_conv2d_forward_h16(_ptr(P[0]), C[0], _ptr(P[1]), C[1], _ptr(P[2]), C[2], _ptr(wp), _ptr(bias), _ptr(y), B,
+                                             Cout, H, W, ks, _stream(xs[0]))
+    _lib.check(rc, "conv2d_forward_h16")
+    return y
+
+
+def groupnorm_act_forward_h16(x, res, gamma, beta, G, eps, act):
+    _chk(x, res, gamma, beta); _h16(x, res, gamma, beta)
+    B, C = x.shape[0], x.shape[1]
+    HW = x.numel() // (B * C)
+    y = torch.empty_like(x)
+    ms = torch.empty((2, B * G), dtype=torch.float32, device=x.device)
+    rc = _lib.get().pnsfm_groupnorm_act_forward_h16(_ptr(x), _ptr(res), _ptr(gamma), _ptr(beta), _ptr(y), _ptr(ms[0]), _ptr(ms[1]), B, C,
+                                                    HW, G, float(eps), act, _stream(x))
+    _lib.check(rc, "groupnorm_act_forward_h16")
+    return y
+
+
+def conv3d_forward_h16(p, w3, b3):
+    _chk(p, w3, b3); _h16(p, w3, b3)
+    B, D, H, W = p.shape
+    nf = _nf_of(w3)
+    out = torch.empty((B, nf * D, H, W), dtype=torch.float16, device=p.device)
+    _lib.check(_lib.get().pnsfm_conv3d_forward_h16(_ptr(p), _ptr(w3), _ptr(b3), _ptr(out), B, D, H, W, nf, _stream(p)), "conv3d_forward_h16")
+    return out
+
+
+def space_to_depth_h16(x):
+    x = x.contiguous()
+    _chk(x); _h16(x)
+    B, C, H, W = x.shape
+    y = torch.empty((B, 4 * C, H // 2, W // 2), dtype=torch.float16, device=x.device)
+    _lib.check(_lib.get().pnsfm_space_to_depth_h16(_ptr(x), _ptr(y), B, C, H, W, _stream(x)), "space_to_depth_h16")
+    return y
+
+
+def depth_to_space_h16(x):
+    _chk(x); _h16(x)
+    B, C4, H, W = x.shape
+    assert C4 % 4 == 0
+    y = torch.empty((B, C4 // 4, 2 * H, 2 * W), dtype=torch.float16, device=x.device)
+    _lib.check(_lib.get().pnsfm_depth_to_space_h16(_ptr(x), _ptr(y), B, C4 // 4, H, W, _stream(x)), "depth_to_space_h16")
+    return y
+
+
+def upsample_nearest_forward_h16(x, s):
+    _chk(x); _h16(x)
+    B, C, h, w = x.shape
+    y = torch.empty((B, C, h * s, w * s), dtype=torch.float16, device=x.device)
+    _lib.check(_lib.get().pnsfm_upsample_nearest_forward_h16(_ptr(x), _ptr(y), B * C, h, w, s, _stream(x)), "upsample_nearest_forward_h16")
+    return y
+
+
+def invdepth_conv_forward_h16(x, w, bias, min_depth):
+    _chk(x, w, bias); _h16(x, w, bias)
+    B, C, H, W = x.shape
+    if tuple(w.shape) != (1, C, 3, 3) or bias is None or bias.numel() != 1:
+        raise RuntimeError("invdepth_conv: weight must be [1,%d,3,3] with a bias of one element" % C)
+    y = torch.empty((B, 1, H, W), dtype=torch.float16, device=x.device)
+    _lib.check(_lib.get().pnsfm_invdepth_conv_forward_h16(_ptr(x), _ptr(w), _ptr(bias), _ptr(y), B, C, H, W, float(min_depth), _stream(x)),
+               "invdepth_conv_forward_h16")
+    return y
+
+
+def region_ops_h16(items):
+    """region_ops on fp16 windows (one launch per MAX_REGION_OPS items)."""
+    if not items:
+        return
+    ref = items[0][1]
+    for i0 in range(0, len(items), MAX_REGION_OPS):
+        chunk = items[i0:i0 + MAX_REGION_OPS]
+        arr = (_RegionOp * len(chunk))()
+        for k, (op, dst, src) in enumerate(chunk):
+            _h16(dst, src)
+            if _lib.REQUIRE_CUDA and not dst.is_cuda:
+                raise RuntimeError("packnet_sfm HIP op got a %s tensor: the HIP kernels run on MI355X only, there is no CPU fallback" % dst.device)
+            if dst.dim() > 4 or (src is not None and tuple(src.shape) != tuple(dst.shape)) or dst.device != ref.device:
+                raise RuntimeError("region_ops: windows must be <= 4-D, of equal shape, on one device")
+            pad = 4 - dst.dim()
+            shape = (1,) * pad + tuple(dst.shape)
+            if 0 in shape:
+                raise RuntimeError("region_ops: empty window")
+            arr[k].dst = dst.data_ptr()
+            arr[k].src = src.data_ptr() if src is not None else None
+            arr[k].op = int(op)
+            for d in range(4):
+                arr[k].n[d] = shape[d]
+                arr[k].dst_stride[d] = 0 if d < pad else dst.stride(d - pad)
+                arr[k].src_stride[d] = 0 if (src is None or d < pad) else src.stride(d - pad)
+        _lib.check(_lib.get().pnsfm_region_ops_h16(ctypes.byref(arr), len(chunk), _stream(ref)), "region_ops_h16")
+
+
+def conv2d_last_config():
+    out = (ctypes.c_int * 8)()
+    _lib.get().pnsfm_conv2d_last_config(out)
+    return list(out)
+
+
 # ---------------------------------------------------------------------------------------------- prof
 def calib_mfma(sink, blocks, iters):
     """The bare six-product bf16 MFMA stream (csrc/calib.hip); returns the bf16 flops of the launch."""

@@ -72,6 +72,9 @@ class SfmModel(BaseModel):
 
     def forward(self, batch, return_logs=False, force_flip=False):
         has_contexts = 'rgb_context' in batch and self.pose_net is not None
+        if has_contexts and any(t.dtype == torch.float16 for t in batch['rgb_context']):
+            raise NotImplementedError('SfmModel: fp16 rgb_context needs PoseNet in fp16, which has no kernels; the fp16 forward covers '
+                                      'the depth network only (evaluate without context images, or in float32)')
         side = _branch_stream(batch['rgb']) if has_contexts else None
         if side is not None:
             main = torch.cuda.current_stream(batch['rgb'].device)

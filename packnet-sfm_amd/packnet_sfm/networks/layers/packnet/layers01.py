@@ -216,7 +216,40 @@ class PackLayerConv3d(nn.Module):
         feats = HF.conv3d_1to8(P, self.conv3d.weight, self.conv3d.bias)
         return self.conv.conv_base(feats)
 
+    def _conv_collapsed_h16(self, P):
+        """fp16 forward of the collapsed form: W_eff / bias_eff composed in fp32 from the upcast fp16 parameters by the fp32 kernels,
+        packed once to fp16 and cached on the parameters' keys; the border strips run through the fp16 ops.  Forward only: with grad
+        enabled the result carries a node whose backward raises, like every other fp16 op."""
+        base = self.conv.conv_base
+        W2, b2, W3, b3 = base.weight, base.bias, self.conv3d.weight, self.conv3d.bias
+        HF._h16_params(W2, b2, W3, b3)
+        return HF._h16_run(lambda P, *params: self._collapsed_h16_body(P), P, W2, b2, W3, b3)
+
+    def _collapsed_h16_body(self, P):
+        base = self.conv.conv_base
+        W2, b2, W3, b3 = base.weight, base.bias, self.conv3d.weight, self.conv3d.bias
+        key = tuple(None if t is None else HF.PackedConvWeight.key_of(t) for t in (W2, b2, W3, b3))
+        with torch.no_grad():
+            if self._eff_packed.key_h16 != key:
+                W_eff, bias_eff = HF.compose_pack_params(W2.float(), None if b2 is None else b2.float(), W3.float(), b3.float())
+                self._eff_packed.get_h16(W_eff, bias_eff, key=key, hold=(W2, b2, W3, b3))
+            k = self.conv.kernel_size
+            r, S = k // 2, 2 * (k // 2) + 1
+            B = P.shape[0]
+            lr_t = bool(self.lr_transposed)
+            P_main, tb, lr = HF.pack_border_split(P, S, lr_t)
+            y = HF.conv2d_h16_composed(P_main, None, None, self._eff_packed, key)
+            o_tb = base(HF.strip_select(HF.conv3d_1to8(tb, W3, b3), B, r, 2))
+            if lr_t:
+                z = HF.conv3d_1to8(lr, W3.transpose(3, 4), b3)
+                o_lr = HF.conv2d(HF.strip_select(z, B, r, 2), W2.transpose(2, 3), b2, self._lr_packed)
+            else:
+                o_lr = base(HF.strip_select(HF.conv3d_1to8(lr, W3, b3), B, r, 3))
+            return HF.pack_border_paste(y, o_tb, o_lr, r, lr_t)
+
     def _conv_collapsed(self, P):
+        if P.dtype == torch.float16:
+            return self._conv_collapsed_h16(P)
         base = self.conv.conv_base
         W2, b2, W3, b3 = base.weight, base.bias, self.conv3d.weight, self.conv3d.bias
         k = self.conv.kernel_size

@@ -1,0 +1,175 @@
+"""Evaluation / inference throughput of PackNet01 ('1A', eval mode, no grad): fp32 HIP, fp16 HIP and fp16 PyTorch eager (the reference's
+`--half` path: oracle.packnet01_forward on an fp16 state dict, MIOpen convolutions) on the same device, alternated in one process.
+
+    python tools/eval_bench.py [--sizes 192x640x1,192x640x4,384x1280x1] [--window 1.0] [--reps 3]
+
+    python tools/eval_bench.py --layers          # the fp16 conv kernel alone, per layer class of PackNet01 at 192x640 batch 4
+
+Prints ONE JSON line: per size and path images/s, ms per forward (device events over windows of >= `window` s), host-issue ms per forward,
+conv GFLOP from shapes (as executed, i.e. with the collapsed packing layers, and reference-algorithmic) and achieved conv TFLOP/s."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, 'packnet-sfm_amd')):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import torch  # noqa: E402
+
+
+def conv_gflop(B, H, W):
+    """(executed, reference) conv GFLOP (2 x MACs, Conv3d included) of PackNet01 1A's forward at [B, 3, H, W], counted from the layer
+    shapes by running oracle.packnet01_forward on meta tensors.  `executed` replaces each packing layer's Conv3d + Conv2d by what the
+    collapsed form runs where PackLayerConv3d.collapse='auto' takes it: the composed (k+2)^2 convolution plus the border strips."""
+    from oracle import packnet_oracle as O
+    from packnet_sfm.networks.layers.packnet.layers01 import PackLayerConv3d
+    F = O.F
+    recs = []
+    c2, c3 = F.conv2d, F.conv3d
+
+    def conv2d(x, w, b=None, *a, **k):
+        y = c2(x, w, b, *a, **k)
+        recs.append(('2d', 2.0 * y.numel() * w.shape[1] * w.shape[2] * w.shape[3]))
+        return y
+
+    def conv3d(x, w, b=None, *a, **k):
+        y = c3(x, w, b, *a, **k)
+        recs.append(('3d', 2.0 * y.numel() * 27))
+        return y
+    sd = {k: torch.empty(v, device='meta') for k, v in O.packnet01_param_shapes('1A').items()}
+    F.conv2d, F.conv3d = conv2d, conv3d
+    try:
+        O.packnet01_forward(sd, torch.empty((B, 3, H, W), device='meta'), version='1A', training=False)
+    finally:
+        F.conv2d, F.conv3d = c2, c3
+    ref = sum(f for _, f in recs)
+    ex = ref
+    widths, ks = (64, 64, 128, 256, 512), (5, 3, 3, 3, 3)
+    h, w = H, W
+    for C, k in zip(widths, ks):
+        h, w, C4, d = h // 2, w // 2, 4 * C, 8
+        probe = PackLayerConv3d(C, k, d=d)
+        if not probe._use_collapsed(h, w):
+            continue
+        r, S = k // 2, 2 * (k // 2) + 1
+        orig = 2.0 * B * C * C4 * d * k * k * h * w + 2.0 * B * d * C4 * 27 * h * w
+        coll = 2.0 * B * C * C4 * (k + 2) ** 2 * h * w
+        coll += 2.0 * (2 * B) * C * C4 * d * k * k * (2 * r) * (w + h) + 2.0 * (2 * B) * d * C4 * 27 * S * (w + h)
+        ex += coll - orig
+    return ex / 1e9, ref / 1e9
+
+
+# (class, Cin, Cout, H, W, ks) at 192 x 640: every distinct fp16 convolution of PackNet01 1A's eval forward (packs collapsed)
+LAYER_CLASSES = [
+    ('stem 5x5', 3, 64, 192, 640, 5), ('7x7 conv1', 64, 64, 192, 640, 7), ('pack1 collapsed 7x7', 256, 64, 96, 320, 7),
+    ('pack2 collapsed 5x5', 256, 64, 48, 160, 5), ('pack3 collapsed 5x5', 512, 128, 24, 80, 5),
+    ('pack4 collapsed 5x5', 1024, 256, 12, 40, 5), ('pack5 collapsed 5x5', 2048, 512, 6, 20, 5),
+    ('3x3 96x320', 64, 64, 96, 320, 3), ('3x3 48x160', 128, 128, 48, 160, 3), ('3x3 24x80', 256, 256, 24, 80, 3),
+    ('3x3 12x40', 512, 512, 12, 40, 3), ('3x3 6x20', 512, 512, 6, 20, 3), ('iconv1 3x3 cat', 129, 64, 192, 640, 3),
+    ('1x1 48x160', 64, 128, 48, 160, 1), ('1x1 24x80', 128, 256, 24, 80, 1), ('1x1 12x40', 256, 512, 12, 40, 1)]
+
+
+def layer_classes(B, window):
+    """TFLOP/s of the fp16 convolution (pnsfm_conv2d_forward_h16, K-split stage included) per layer class, device events."""
+    from packnet_sfm.hip import ops
+    dev = torch.device('cuda:0')
+    out = {}
+    for name, Cin, Cout, H, W, ks in LAYER_CLASSES:
+        x = torch.randn((B, Cin, H, W), device=dev).half()
+        w = (torch.randn((Cout, Cin, ks, ks), device=dev) * (1.0 / (Cin * ks * ks)) ** 0.5).half()
+        b = torch.zeros(Cout, device=dev)
+        wp = ops.conv2d_pack_h16(w)
+        xs = (x[:, :128].contiguous(), x[:, 128:].contiguous()) if 'cat' in name else (x,)
+        fn = lambda: ops.conv2d_forward_h16(xs, wp, b, Cout, ks)       # noqa: E731
+        for _ in range(3):
+            fn()
+        cfg = ops.conv2d_last_config()
+        ms, _ = time_path(fn, window)
+        gf = 2.0 * B * Cout * H * W * Cin * ks * ks / 1e9
+        out[name] = {'shape': [B, Cin, Cout, H, W, ks], 'gflop': round(gf, 2), 'ms': round(ms, 4), 'tflops': round(gf / ms, 1),
+                     'config': {'NT': cfg[1], 'MT': cfg[2], 'WM': cfg[3], 'ksplit': cfg[4], 'tile_w': cfg[5], 'workgroups': cfg[6]}}
+    return out
+
+
+def time_path(fn, window, ev_only=False):
+    torch.cuda.synchronize()
+    n, t_host, ms_dev = 0, 0.0, 0.0
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    t0 = time.perf_counter()
+    while True:
+        h0 = time.perf_counter()
+        fn()
+        t_host += time.perf_counter() - h0
+        n += 1
+        if time.perf_counter() - t0 >= window and n >= 3:
+            break
+        if n % 4 == 0:
+            torch.cuda.synchronize()
+    e1.record()
+    torch.cuda.synchronize()
+    ms_dev = e0.elapsed_time(e1)
+    return ms_dev / n, 1e3 * t_host / n
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--sizes', default='192x640x1,192x640x4,384x1280x1')
+    ap.add_argument('--window', type=float, default=1.0)
+    ap.add_argument('--reps', type=int, default=3)
+    ap.add_argument('--paths', default='hip32,hip16,eager16')
+    ap.add_argument('--layers', action='store_true', help='per-layer-class TFLOP/s of the fp16 conv kernel (192x640, --batch)')
+    ap.add_argument('--batch', type=int, default=4)
+    a = ap.parse_args()
+    if a.layers:
+        with torch.no_grad():
+            print(json.dumps({'tool': 'eval_bench --layers', 'device': torch.cuda.get_device_name(0), 'batch': a.batch,
+                              'kernel': 'conv2d_h16 (variant 9)', 'layers': layer_classes(a.batch, a.window)}))
+        return
+    from oracle import packnet_oracle as O
+    from packnet_sfm.networks.depth.PackNet01 import PackNet01
+    dev = torch.device('cuda:0')
+    sd = O.init_params(O.packnet01_param_shapes('1A'), seed=0)
+    n32 = PackNet01(dropout=0.0, version='1A')
+    n32.load_state_dict(sd)
+    n32 = n32.to(dev).eval()
+    n16 = PackNet01(dropout=0.0, version='1A')
+    n16.load_state_dict(sd)
+    n16 = n16.to(dev, dtype=torch.float16).eval()
+    sd16 = {k: v.to(dev).half() for k, v in sd.items()}
+    result = {'tool': 'eval_bench', 'device': torch.cuda.get_device_name(0), 'net': 'PackNet01 1A eval, torch.no_grad', 'sizes': {}}
+    for spec in a.sizes.split(','):
+        H, W, B = (int(v) for v in spec.split('x'))
+        x32 = torch.rand((B, 3, H, W), device=dev, generator=torch.Generator(device=dev).manual_seed(0))
+        x16 = x32.half()
+        paths = {'hip32': lambda: n32(rgb=x32), 'hip16': lambda: n16(rgb=x16),
+                 'eager16': lambda: O.packnet01_forward(sd16, x16, version='1A', training=False)}
+        paths = {k: v for k, v in paths.items() if k in a.paths.split(',')}
+        with torch.no_grad():
+            gf_exec, gf_ref = conv_gflop(B, H, W)
+            for fn in paths.values():        # warm-up: packing, allocator, MIOpen find
+                for _ in range(3):
+                    fn()
+            torch.cuda.synchronize()
+            samples = {k: [] for k in paths}
+            for _ in range(a.reps):          # alternate the paths, best window of each
+                for k, fn in paths.items():
+                    samples[k].append(time_path(fn, a.window))
+        entry = {'gflop_conv_executed': round(gf_exec, 2), 'gflop_conv_reference': round(gf_ref, 2)}
+        for k, v in samples.items():
+            ms, host = min(v)
+            gf = gf_ref if k == 'eager16' else gf_exec
+            entry[k] = {'ms_per_forward': round(ms, 3), 'images_per_s': round(1e3 * B / ms, 2), 'host_issue_ms': round(host, 3),
+                        'conv_tflops': round(gf / ms, 1), 'ms_all_windows': [round(s[0], 3) for s in v]}
+        if 'hip16' in entry and 'hip32' in entry:
+            entry['speedup_hip16_vs_hip32'] = round(entry['hip32']['ms_per_forward'] / entry['hip16']['ms_per_forward'], 3)
+        result['sizes']['%dx%d_b%d' % (H, W, B)] = entry
+    print(json.dumps(result))
+
+
+if __name__ == '__main__':
+    main()
