@@ -1,22 +1,29 @@
-// conv2d.hip -- stride-1, zero-padded KxK convolution as an exact-fp32 MFMA implicit GEMM for gfx950.
+// conv2d.hip -- zero-padded KxK convolution (stride 1 | 2) as an MFMA implicit GEMM for gfx950: forward, backward-data
+// (the same kernels on a tap-flipped / transposed packed weight) and weight gradient, behind the C entry points of pnsfm.h.
 //
-// Replaces nn.ConstantPad2d(k//2) + nn.Conv2d(stride=1) of the reference's Conv2D / ResidualConv /
-// InvDepth / PackLayerConv3d / UnpackLayerConv3d blocks
-//   (/root/reference/packnet_sfm/networks/layers/packnet/layers01.py:28-36, 57-60, 115-121, 235-246, 274-281)
-// and their autograd (dgrad = same kernel on a tap-flipped / transposed packed weight; wgrad below).
+// GEMM view (forward):  Y[M = co][N = pixel] = sum_{tap, ci} Wp[tap][ci][co] * X[ci][pixel + off(tap)]; one workgroup computes
+// (32*MT output channels) x (4 waves * NT * 32 pixels) from an input halo patch staged in LDS; K (= taps x channels) can be split
+// across workgroups, the partial outputs are then summed in a fixed order by conv_splitk_reduce_kernel.
 //
-// GEMM view (forward):  Y[M = co][N = pixel] = sum_{tap, ci} Wp[tap][ci][co] * X[ci][pixel + off(tap)]
-//   * one workgroup = 4 wave64; block tile = (32*MT output channels) x (4 waves * NT * 32 pixels);
-//   * the input halo patch for CI (<=16) channels is staged ONCE in LDS and reused by all k*k taps
-//     (and by every output channel of the tile) -- NCHW rows are read as coalesced row segments;
-//   * per tap, a [CI][BM] weight slab (M fastest -> conflict-free ds_read_b32 for the MFMA A operand)
-//     is double-buffered through registers while the previous tap's MFMAs run;
-//   * v_mfma_f32_32x32x2_f32 (A: lane l holds W[m = l&31][k = l>>5], B: lane l holds X[k = l>>5][n = l&31]),
-//     i.e. two input channels per instruction, exact fp32 (bitwise an fmaf chain) -- no TF32/bf16 shortcut;
-//   * K (= taps x channels) can be split across blockIdx.z for the low-resolution layers whose pixel
-//     count cannot fill 256 CUs (pack4/pack5: 480 pixels, K = 147456); the splits' partial outputs are summed in a
-//     fixed order by a second kernel (conv_splitk_reduce_kernel; round 4 -- fp32 atomics before).
-// Roofline: MFMA-bound. 2*Cout*Cin*k*k*B*H*W flop per launch against the 157.3 TFLOP/s fp32 matrix peak.
+// Map of the file, in order:
+//   policy        conv_geom_fixed / conv_geom (tile, K-split and LDS plan of a launch), the tuning database and the decision
+//                 codec (ConvDecision / WgradDecision: the layout table of the two ints of a tuning decision is there)
+//   kernels       forward / backward-data, by variant number (ConvGeom::DMA, the `variant` field of a decision):
+//                   0  f32 MFMA, register-staged patch   conv2d_mfma_kernel<.., false> (the 3-channel 5x5 stem: conv2d_stem5_kernel)
+//                   1  f32 MFMA, patch by LDS-DMA        conv2d_mfma_kernel<.., true>
+//                   2  f32 MFMA, pipelined, <= 160 KB    conv2d_pipe_kernel
+//                   3  split-bf16, one patch buffer      conv2d_bx3_kernel<.., 2>   (conv2d_bx3.h; 3..5 differ in the LDS plan only)
+//                   4  split-bf16, two patch buffers
+//                   5  split-bf16, two patch buffers, a whole kernel row per weight stage
+//                   6  split-bf16, three workgroups/CU   conv2d_bx3_kernel<.., 3>
+//                   7  split-bf16, ping-pong workgroup   conv2d_bx3pp_kernel        (conv2d_bx3pp.h)
+//                   8  split-bf16, 1x1 without LDS       conv1x1_bx3_kernel         (conv2d_bx3_1x1.h)
+//                   9  fp16 forward (inference)          conv2d_h16.h, included at the end
+//   dispatch      enqueue_conv (one launch of a given geometry), launch_conv (decision -> geometry -> launch) and its autotuner
+//   packers       pack_weights_kernel and the batched pack tables
+//   weight grad   sum_slabs_kernel, the stem and the generic f32 kernels; the tap-major, split-bf16 and nine-taps kernels live in
+//                 conv2d_wgrad{2,3,4}.hip.  WgradPlan and the wgrad_* steps choose among them (wgrad_impl)
+//   C entry points
 #include "pnsfm_common.h"
 #include <cstring>
 #include "../../include/pnsfm.h"
@@ -29,6 +36,7 @@
 #include <mutex>
 #include <string>
 #include <cstdio>
+#include <type_traits>
 
 namespace pnsfm {
 
@@ -153,9 +161,7 @@ static bool conv_geom_fixed(int B, int Cin, int Cout, int H, int W, int ks, int 
     const int cand[6] = {KK <= 9 ? KK : ks, ks, 4, 3, 2, 1};
     g.G = 0;
     if (DMA == 7) {
-      // stages of <= 4 taps: the two groups alternate per stage, and a staging half-step (patch split + DMA issue) should not be
-      // much shorter than the compute half-step it hides under; PNSFM_PP_G overrides (lab)
-      // taps per stage: a compute half-step should not be shorter than the staging half-step it hides (patch split + DMA issue +
+      // taps per stage: the two groups alternate per stage, and a compute half-step should not be shorter than the staging half-step it hides (patch split + DMA issue +
       // loads: 1 000 - 2 000 cycles, tools/pp_trace.py) -- 2 300 cycles are 3 taps of the (2,2) tile, 6 of (2,1) / (1,2), 12 of (1,1).
       // Built for G in {1, 2, 3, 4, 6, 9}; PNSFM_PP_G overrides the first choice (lab).
       static const int ppG = [] { const char* e = getenv("PNSFM_PP_G"); return e && e[0] ? atoi(e) : 0; }();
@@ -288,7 +294,7 @@ static std::mutex g_tune_mu;
 
 // Tuning database (the analogue of MIOpen's user find-db): PNSFM_TUNE_DB=<file> loads earlier decisions at start-up
 // and appends new ones, so that a later process (a profiling run, a resumed training job) launches no candidates.
-// One text line per decision: kind B Cin Cout H W ks  cfg split.
+// One text line per decision: kind B Cin Cout H W ks  v0 v1  (the two ints of ConvDecision / WgradDecision::encode below).
 static std::string g_tune_db;
 static int g_shipped_entries = 0;   // entries read from the shipped tuned_gfx950.db (0: none / user database in use)
 
@@ -316,17 +322,60 @@ static void tune_db_append(const std::array<int, 7>& k, const std::array<int, 2>
   fclose(f);
 }
 
+// ---- decision codec ---------------------------------------------------------------------------------------------------
+// A tuning decision is two ints {v0, v1}: the value of g_tuned / g_pinned, the last two columns of a database line and the
+// arguments of pnsfm_tune_set.  This is the only place that knows their layout:
+//
+//   key kind            v0                                                      v1
+//   x0 / x1  forward,   NT | variant << 4 | forceMT << 8 | tm << 9              K-split
+//     backward-data       NT 1 | 2: 32-pixel tiles per wave; variant 0..8: the kernel (file header); forceMT 1: 32-row M
+//                         tiles where 64 would fit; tm 0 | 1 | 2: classic tiles, 16-wide rectangles, row bands
+//   x2  weight gradient pixel split                                             kernel | parameters << 4
+//                         kernel 0  generic f32 (the stem's own kernel where it applies)    0
+//                         kernel 1  tap-major (conv2d_wgrad2.hip)                           1
+//                         kernel 2  split-bf16 (conv2d_wgrad3.hip)                          2 | NT << 4 | wm << 6
+//                                     NT 1 | 2; wm 4 bits: co tiles per workgroup (0: the most), + 8: the three-workgroups build
+//                         kernel 3  nine-taps (conv2d_wgrad4.hip)                           3 | (WCI | TG << 4 | TR << 8) << 4
+//                                     WCI 1 | 2 ci tiles per workgroup; TG, TR: tile width in 8-pixel groups / rows (0: library choice)
+//
+// decode() masks every field to its width and accepts anything (tests and tools write raw ints); whether a decision fits the shape
+// is decided where it is applied (launch_conv, wgrad_apply).
+struct ConvDecision {
+  int NT = 1, variant = 0, forceMT = 0, tm = 0, split = 1;
+  std::array<int, 2> encode() const { return {NT | (variant << 4) | (forceMT << 8) | (tm << 9), split}; }
+  static ConvDecision decode(const std::array<int, 2>& v) {
+    return {v[0] & 15, (v[0] >> 4) & 15, (v[0] >> 8) & 1, (v[0] >> 9) & 3, v[1]};
+  }
+};
+
+struct WgradDecision {
+  int kernel = 0, split = 1;
+  int NT = 1, wm = 0;             // kernel 2
+  int WCI = 2, TG = 0, TR = 0;    // kernel 3
+  int cfg4() const { return WCI | (TG << 4) | (TR << 8); }         // the `cfg` argument of enqueue_wgrad4
+  std::array<int, 2> encode() const {
+    return {split, kernel == 2 ? 2 | (NT << 4) | (wm << 6) : (kernel == 3 ? 3 | (cfg4() << 4) : kernel)};
+  }
+  static WgradDecision decode(const std::array<int, 2>& v) {
+    WgradDecision d;
+    d.split = v[0];
+    d.kernel = v[1] & 15;
+    if (d.kernel == 2) { d.NT = ((v[1] >> 4) & 3) == 2 ? 2 : 1; d.wm = (v[1] >> 6) & 15; }
+    if (d.kernel == 3) { d.WCI = (v[1] >> 4) & 15; d.TG = (v[1] >> 8) & 15; d.TR = (v[1] >> 12) & 15; }
+    return d;
+  }
+};
+
 // PNSFM_TUNE_LOG=<file>: every candidate the autotuner times is appended as
-//   kind B Cin Cout H W ks | variant/config split ms       (kind 0/1 forward/backward-data (+10*stride), 2 weight gradient)
+//   kind B Cin Cout H W ks | cfg split ms       (cfg: v0 of a forward / backward-data decision, v1 of a weight-gradient one)
 // -- the whole configuration landscape of a training step from one ordinary run.
 static std::string g_tune_log;
-static void tune_log(int kind, const std::array<int, 7>& k, int cfg, int split, float ms) {
+static void tune_log(const std::array<int, 7>& k, int cfg, int split, float ms) {
   if (g_tune_log.empty()) return;
   FILE* f = fopen(g_tune_log.c_str(), "a");
   if (!f) return;
   fprintf(f, "%d %d %d %d %d %d %d | %d %d %.4f\n", k[0], k[1], k[2], k[3], k[4], k[5], k[6], cfg, split, ms);
   fclose(f);
-  (void)kind;
 }
 
 static int g_wgrad_variant = -1;  // un-tuned weight-gradient kernel: -1 library default (split-bf16 where the arithmetic mode and the
@@ -1047,6 +1096,38 @@ extern "C" int pnsfm_debug_set_trace(void* p) { g_trace_buf = (long long*)p; ret
 extern "C" int pnsfm_debug_set_trace_flags(int f) { g_trace_flags = f; return 0; }
 #endif
 
+// ---- kernel dispatch: run-time tile / stage sizes -> template arguments ---------------------------------------------------
+// f(integral_constant<MT>, integral_constant<NT>) for the (32*MT) x (4 * 32*NT) block tile of a geometry; returns what f returns.
+template <class F>
+static inline int with_conv_tile(int MT, int NT, F&& f) {
+  using One = std::integral_constant<int, 1>;
+  using Two = std::integral_constant<int, 2>;
+  if (MT == 2 && NT == 2) return f(Two{}, Two{});
+  if (MT == 2 && NT == 1) return f(Two{}, One{});
+  if (MT == 1 && NT == 2) return f(One{}, Two{});
+  return f(One{}, One{});
+}
+
+// f(integral_constant<G>) for the taps per weight stage the ping-pong kernel is built for (anything else: 1; enqueue_conv checks)
+template <class F>
+static inline int with_pp_taps(int G, F&& f) {
+  if (G == 9) return f(std::integral_constant<int, 9>{});
+  if (G == 6) return f(std::integral_constant<int, 6>{});
+  if (G == 4) return f(std::integral_constant<int, 4>{});
+  if (G == 3) return f(std::integral_constant<int, 3>{});
+  if (G == 2) return f(std::integral_constant<int, 2>{});
+  return f(std::integral_constant<int, 1>{});
+}
+
+// more than 64 KB of dynamic LDS needs an explicit opt-in per kernel and device, once (ensure_lds_limit, api.hip: nothing to do on
+// the emulator); 0 on success
+template <void (*Kernel)(ConvArgs)>
+static inline int allow_wide_lds(size_t smem_bytes, const char* what) {
+  static unsigned long long done = 0;     // one bit per device
+  if (smem_bytes <= 64 * 1024) return 0;
+  return ensure_lds_limit(reinterpret_cast<const void*>(Kernel), &done, (int)kMaxSmemPipe, what);
+}
+
 // extras of a launch's epilogue: the addend of ConvArgs (round 5; null: none).  (The GroupNorm statistics that rode along here in round 5
 // -- pnsfm_conv2d_forward_gn -- were measured neutral twice and removed in round 6.)
 struct ConvGnOut {
@@ -1104,100 +1185,41 @@ static int enqueue_conv(const ConvGeom& g, const float* x, const float* wp, cons
   a.ablate = g_ablate;
 #endif
   const dim3 grid1(grid.x * grid.y * grid.z);      // split-bf16 kernels: 1-D launch, block order decoded in the kernel
-#define PNSFM_CONV_DISPATCH(DMAv)                                                                                 \
-  do {                                                                                                             \
-    if (g.MT == 2 && g.NT == 2) PNSFM_LAUNCH((conv2d_mfma_kernel<2, 2, DMAv>), grid, dim3(256), g.smem_bytes, stream, a);      \
-    else if (g.MT == 2 && g.NT == 1) PNSFM_LAUNCH((conv2d_mfma_kernel<2, 1, DMAv>), grid, dim3(256), g.smem_bytes, stream, a); \
-    else if (g.MT == 1 && g.NT == 2) PNSFM_LAUNCH((conv2d_mfma_kernel<1, 2, DMAv>), grid, dim3(256), g.smem_bytes, stream, a); \
-    else PNSFM_LAUNCH((conv2d_mfma_kernel<1, 1, DMAv>), grid, dim3(256), g.smem_bytes, stream, a);                 \
-  } while (0)
-  if (g.DMA >= 3) {
-#ifndef PNSFM_EMU
-#define PNSFM_BX3_ATTR(MTv, NTv)                                                                                   \
-    do {                                                                                                           \
-      static unsigned long long done = 0; /* one bit per device */                                                 \
-      if (g.smem_bytes > 64 * 1024 &&                                                                              \
-          ensure_lds_limit(reinterpret_cast<const void*>(&conv2d_bx3_kernel<MTv, NTv, 2>), &done, (int)kMaxSmemPipe, what)) \
-        return -1;                                                                                                 \
-    } while (0)
-#else
-#define PNSFM_BX3_ATTR(MTv, NTv) do {} while (0)
-#endif
-    if (g.DMA == 8) {         // 1x1 without LDS (conv2d_bx3_1x1.h)
-      if (g.MT == 2 && g.NT == 2) PNSFM_LAUNCH((conv1x1_bx3_kernel<2, 2>), grid1, dim3(256), 0, stream, a);
-      else if (g.MT == 2 && g.NT == 1) PNSFM_LAUNCH((conv1x1_bx3_kernel<2, 1>), grid1, dim3(256), 0, stream, a);
-      else if (g.MT == 1 && g.NT == 2) PNSFM_LAUNCH((conv1x1_bx3_kernel<1, 2>), grid1, dim3(256), 0, stream, a);
-      else PNSFM_LAUNCH((conv1x1_bx3_kernel<1, 1>), grid1, dim3(256), 0, stream, a);
-    }
-    else if (g.DMA == 7) {         // ping-pong workgroup: 512 threads, up to 160 KB of LDS, taps per stage a template parameter (conv2d_bx3pp.h)
-#ifndef PNSFM_EMU
-#define PNSFM_PP_ATTR(MTv, NTv, Gv)                                                                                \
-      do {                                                                                                         \
-        static unsigned long long done = 0; /* one bit per device */                                               \
-        if (g.smem_bytes > 64 * 1024 &&                                                                            \
-            ensure_lds_limit(reinterpret_cast<const void*>(&conv2d_bx3pp_kernel<MTv, NTv, Gv>), &done, (int)kMaxSmemPipe, what)) \
-          return -1;                                                                                               \
-      } while (0)
-#else
-#define PNSFM_PP_ATTR(MTv, NTv, Gv) do {} while (0)
-#endif
-#define PNSFM_PP_LAUNCH(MTv, NTv, Gv) do { PNSFM_PP_ATTR(MTv, NTv, Gv); PNSFM_LAUNCH((conv2d_bx3pp_kernel<MTv, NTv, Gv>), grid1, dim3(512), g.smem_bytes, stream, a); } while (0)
-#define PNSFM_PP_G(MTv, NTv)                                                                                       \
-      do {                                                                                                         \
-        if (g.G == 9) PNSFM_PP_LAUNCH(MTv, NTv, 9);                                                                \
-        else if (g.G == 6) PNSFM_PP_LAUNCH(MTv, NTv, 6);                                                           \
-        else if (g.G == 4) PNSFM_PP_LAUNCH(MTv, NTv, 4);                                                           \
-        else if (g.G == 3) PNSFM_PP_LAUNCH(MTv, NTv, 3);                                                           \
-        else if (g.G == 2) PNSFM_PP_LAUNCH(MTv, NTv, 2);                                                           \
-        else PNSFM_PP_LAUNCH(MTv, NTv, 1);                                                                         \
-      } while (0)
-      if (a.playout == 0) { set_error("%s: the ping-pong kernel needs the half-plane patch layout", what); return -1; }
-      if (g.G != 1 && g.G != 2 && g.G != 3 && g.G != 4 && g.G != 6 && g.G != 9) { set_error("%s: the ping-pong kernel is built for 1, 2, 3, 4, 6 or 9 taps per stage", what); return -1; }
-      if (g.MT == 2 && g.NT == 2) PNSFM_PP_G(2, 2);
-      else if (g.MT == 2 && g.NT == 1) PNSFM_PP_G(2, 1);
-      else if (g.MT == 1 && g.NT == 2) PNSFM_PP_G(1, 2);
-      else PNSFM_PP_G(1, 1);
-#undef PNSFM_PP_G
-#undef PNSFM_PP_LAUNCH
-#undef PNSFM_PP_ATTR
-    }
-    else if (g.DMA == 6) {         // three workgroups per CU (<= 53 KB of LDS each: no opt-in needed)
-      if (g.MT == 2) PNSFM_LAUNCH((conv2d_bx3_kernel<2, 1, 3>), grid1, dim3(256), g.smem_bytes, stream, a);
-      else if (g.NT == 2) PNSFM_LAUNCH((conv2d_bx3_kernel<1, 2, 3>), grid1, dim3(256), g.smem_bytes, stream, a);
-      else PNSFM_LAUNCH((conv2d_bx3_kernel<1, 1, 3>), grid1, dim3(256), g.smem_bytes, stream, a);
-    }
-    else if (g.MT == 2 && g.NT == 2) { PNSFM_BX3_ATTR(2, 2); PNSFM_LAUNCH((conv2d_bx3_kernel<2, 2, 2>), grid1, dim3(256), g.smem_bytes, stream, a); }
-    else if (g.MT == 2 && g.NT == 1) { PNSFM_BX3_ATTR(2, 1); PNSFM_LAUNCH((conv2d_bx3_kernel<2, 1, 2>), grid1, dim3(256), g.smem_bytes, stream, a); }
-    else if (g.MT == 1 && g.NT == 2) { PNSFM_BX3_ATTR(1, 2); PNSFM_LAUNCH((conv2d_bx3_kernel<1, 2, 2>), grid1, dim3(256), g.smem_bytes, stream, a); }
-    else { PNSFM_BX3_ATTR(1, 1); PNSFM_LAUNCH((conv2d_bx3_kernel<1, 1, 2>), grid1, dim3(256), g.smem_bytes, stream, a); }
-#undef PNSFM_BX3_ATTR
-  } else if (g.DMA == 2) {
-#ifndef PNSFM_EMU
-    // more than 64 KB of dynamic LDS needs an explicit opt-in per kernel (once)
-#define PNSFM_PIPE_ATTR(MTv, NTv)                                                                                  \
-    do {                                                                                                           \
-      static unsigned long long done = 0; /* one bit per device */                                                 \
-      if (g.smem_bytes > 64 * 1024 &&                                                                              \
-          ensure_lds_limit(reinterpret_cast<const void*>(&conv2d_pipe_kernel<MTv, NTv>), &done, (int)kMaxSmemPipe, what)) \
-        return -1;                                                                                                 \
-    } while (0)
-#else
-#define PNSFM_PIPE_ATTR(MTv, NTv) do {} while (0)
-#endif
-    if (g.MT == 2 && g.NT == 2) { PNSFM_PIPE_ATTR(2, 2); PNSFM_LAUNCH((conv2d_pipe_kernel<2, 2>), grid, dim3(256), g.smem_bytes, stream, a); }
-    else if (g.MT == 2 && g.NT == 1) { PNSFM_PIPE_ATTR(2, 1); PNSFM_LAUNCH((conv2d_pipe_kernel<2, 1>), grid, dim3(256), g.smem_bytes, stream, a); }
-    else if (g.MT == 1 && g.NT == 2) { PNSFM_PIPE_ATTR(1, 2); PNSFM_LAUNCH((conv2d_pipe_kernel<1, 2>), grid, dim3(256), g.smem_bytes, stream, a); }
-    else { PNSFM_PIPE_ATTR(1, 1); PNSFM_LAUNCH((conv2d_pipe_kernel<1, 1>), grid, dim3(256), g.smem_bytes, stream, a); }
-#undef PNSFM_PIPE_ATTR
-  } else if (g.DMA) PNSFM_CONV_DISPATCH(true);
-  else if (g.stem) {
-    if (g.MT == 2 && g.NT == 2) PNSFM_LAUNCH((conv2d_stem5_kernel<2, 2>), grid, dim3(256), g.smem_bytes, stream, a);
-    else if (g.MT == 2 && g.NT == 1) PNSFM_LAUNCH((conv2d_stem5_kernel<2, 1>), grid, dim3(256), g.smem_bytes, stream, a);
-    else if (g.MT == 1 && g.NT == 2) PNSFM_LAUNCH((conv2d_stem5_kernel<1, 2>), grid, dim3(256), g.smem_bytes, stream, a);
-    else PNSFM_LAUNCH((conv2d_stem5_kernel<1, 1>), grid, dim3(256), g.smem_bytes, stream, a);
+  if (g.DMA == 7) {
+    if (a.playout == 0) { set_error("%s: the ping-pong kernel needs the half-plane patch layout", what); return -1; }
+    if (g.G != 1 && g.G != 2 && g.G != 3 && g.G != 4 && g.G != 6 && g.G != 9) { set_error("%s: the ping-pong kernel is built for 1, 2, 3, 4, 6 or 9 taps per stage", what); return -1; }
   }
-  else PNSFM_CONV_DISPATCH(false);
-#undef PNSFM_CONV_DISPATCH
+  const dim3 wg(256);
+  const int refused = with_conv_tile(g.MT, g.NT, [&](auto mt, auto nt) -> int {
+    constexpr int MT = decltype(mt)::value, NT = decltype(nt)::value;
+    if (g.DMA == 8) {            // 1x1 without LDS (conv2d_bx3_1x1.h)
+      PNSFM_LAUNCH((conv1x1_bx3_kernel<MT, NT>), grid1, wg, 0, stream, a);
+    } else if (g.DMA == 7) {     // ping-pong workgroup: 512 threads, up to 160 KB of LDS, taps per stage a template parameter (conv2d_bx3pp.h)
+      return with_pp_taps(g.G, [&](auto taps) -> int {
+        constexpr int G = decltype(taps)::value;
+        if (allow_wide_lds<&conv2d_bx3pp_kernel<MT, NT, G>>(g.smem_bytes, what)) return -1;
+        PNSFM_LAUNCH((conv2d_bx3pp_kernel<MT, NT, G>), grid1, dim3(512), g.smem_bytes, stream, a);
+        return 0;
+      });
+    } else if (g.DMA == 6) {     // three workgroups per CU (<= 53 KB of LDS each: no opt-in needed); conv_geom_fixed admits no (2,2) tile
+      constexpr int NT6 = MT == 2 ? 1 : NT;
+      PNSFM_LAUNCH((conv2d_bx3_kernel<MT, NT6, 3>), grid1, wg, g.smem_bytes, stream, a);
+    } else if (g.DMA >= 3) {
+      if (allow_wide_lds<&conv2d_bx3_kernel<MT, NT, 2>>(g.smem_bytes, what)) return -1;
+      PNSFM_LAUNCH((conv2d_bx3_kernel<MT, NT, 2>), grid1, wg, g.smem_bytes, stream, a);
+    } else if (g.DMA == 2) {
+      if (allow_wide_lds<&conv2d_pipe_kernel<MT, NT>>(g.smem_bytes, what)) return -1;
+      PNSFM_LAUNCH((conv2d_pipe_kernel<MT, NT>), grid, wg, g.smem_bytes, stream, a);
+    } else if (g.DMA) {
+      PNSFM_LAUNCH((conv2d_mfma_kernel<MT, NT, true>), grid, wg, g.smem_bytes, stream, a);
+    } else if (g.stem) {
+      PNSFM_LAUNCH((conv2d_stem5_kernel<MT, NT>), grid, wg, g.smem_bytes, stream, a);
+    } else {
+      PNSFM_LAUNCH((conv2d_mfma_kernel<MT, NT, false>), grid, wg, g.smem_bytes, stream, a);
+    }
+    return 0;
+  });
+  if (refused) return -1;
   int rc = check_launch(what);
   if (!rc && g.splitK > 1) {
     PNSFM_LAUNCH(conv_splitk_reduce_kernel, dim3((unsigned)ceil_div_sz(out_elems, 1024)), dim3(256), 0, stream, (const float*)a.ws, bias, y,
@@ -1233,6 +1255,50 @@ static float time_on_stream(hipStream_t stream, int reps, F fn) {
 }
 #endif
 
+#ifndef PNSFM_EMU
+// The autotuner of a forward / backward-data shape: times every (variant, NT, M tile, tile mode, K-split) that fits on the caller's
+// stream and returns the fastest (`g`, the heuristic geometry, when nothing could be timed).  (g_tune_mu held)
+static ConvDecision conv_tune(const ConvGeom& g, const std::array<int, 7>& key, bool bx3, const float* x, const float* wp,
+                              const float* bias, float* y, int B, int Cin, int Cout, int H, int W, int ks, hipStream_t stream,
+                              const char* what, int kind_tag, int S, int Hi, int Wi, const ConvSrc* ms) {
+  static const int kSplits[] = {1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 48, 64};
+  float best_ms = 1e30f;
+  ConvDecision best = {g.NT, g.DMA, 0, 0, g.splitK};
+  const int nMT = (conv_pick_MT(Cout) == 2) ? 2 : 1;
+  const int nTM = (bx3 && (W % 32 != 0 || ks >= 5)) ? (W % 32 != 0 ? 3 : 2) : 1;       // tile modes (rectangles / row bands) exist for the split-bf16 kernels
+  // PNSFM_PP: which launches may take the ping-pong workgroup (variant 7): bit 0 forward, bit 1 backward-data (default 3: both)
+  static const int pp_mask = [] { const char* e = getenv("PNSFM_PP"); return (e && e[0]) ? atoi(e) : 3; }();
+  const bool pp_on = ((pp_mask >> (kind_tag & 1)) & 1) != 0;
+  // variants (file header): f32 0..2, split-bf16 3..8
+  int vars[6], nVar = 0;
+  if (bx3) {
+    for (int v = 3; v <= 6; ++v) vars[nVar++] = v;
+    if (pp_on) vars[nVar++] = 7;
+    if (ks == 1 && S == 1 && !ms) vars[nVar++] = 8;
+  } else {
+    for (int v = 0; v <= 2; ++v) vars[nVar++] = v;
+  }
+  for (int cfgt = 0; cfgt < 2 * nVar * nMT * nTM; ++cfgt) {
+    const int cfg = cfgt % (2 * nVar * nMT), tm = cfgt / (2 * nVar * nMT);
+    const int NT = 2 - (cfg & 1), DA = vars[(cfg >> 1) % nVar], fMT = cfg / (2 * nVar);
+    int last_split = -1;
+    for (int want : kSplits) {
+      ConvGeom c;
+      if (!conv_geom_fixed(B, Cin, Cout, H, W, ks, NT, want, c, DA, S, fMT, tm)) break;
+      if (c.splitK == last_split) continue;
+      last_split = c.splitK;
+      const long blocks = (long)B * c.tiles_per_img * (c.MP / (32 * c.MT)) * c.splitK;
+      if (c.splitK > 1 && blocks > 24L * 256 * 4) break;      // already far more blocks than the chip holds
+      const float tms = time_on_stream(stream, 2, [&]() { return enqueue_conv(c, x, wp, bias, y, B, Cin, Cout, H, W, ks, stream, what, S, Hi, Wi, ms); });
+      const ConvDecision cand = {NT, DA, fMT, tm, c.splitK};
+      tune_log(key, cand.encode()[0], cand.split, tms);
+      if (tms > 0.f && tms < best_ms) { best_ms = tms; best = cand; }
+    }
+  }
+  return best;
+}
+#endif
+
 // configuration of the calling thread's most recent forward / backward-data launch (pnsfm_conv2d_last_config)
 static thread_local std::array<int, 8> g_last_conv = {-1, 0, 0, 0, 0, 0, 0, 0};
 
@@ -1261,48 +1327,18 @@ static int launch_conv(const float* x, const float* wp, const float* bias, float
 #ifndef PNSFM_EMU
     // (a shape first seen inside a hipGraph capture cannot be timed -- timing synchronises: un-tuned default, not cached)
     if (!dec && tune && !stream_capturing(stream)) {
-      static const int kSplits[] = {1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 48, 64};
-      float best_ms = 1e30f;
-      std::array<int, 2> best = {g.NT | (g.DMA << 4), g.splitK};
-      const int nMT = (conv_pick_MT(Cout) == 2) ? 2 : 1;
-      const int nTM = (bx3 && (W % 32 != 0 || ks >= 5)) ? (W % 32 != 0 ? 3 : 2) : 1;       // tile modes (rectangles / row bands) exist for the split-bf16 kernels
-      // PNSFM_PP: which launches may take the ping-pong workgroup (variant 7): bit 0 forward, bit 1 backward-data (default 3: both)
-      static const int pp_mask = [] { const char* e = getenv("PNSFM_PP"); return (e && e[0]) ? atoi(e) : 3; }();
-      const bool pp_on = ((pp_mask >> (kind_tag & 1)) & 1) != 0;
-      // LDS plans: f32 0..2, split-bf16 3..8 (6 = three workgroups per CU, 7 = ping-pong workgroup, 8 = 1x1 without LDS)
-      int vars[6], nVar = 0;
-      if (bx3) {
-        for (int v = 3; v <= 6; ++v) vars[nVar++] = v;
-        if (pp_on) vars[nVar++] = 7;
-        if (ks == 1 && S == 1 && !ms) vars[nVar++] = 8;
-      } else {
-        for (int v = 0; v <= 2; ++v) vars[nVar++] = v;
-      }
-      for (int cfgt = 0; cfgt < 2 * nVar * nMT * nTM; ++cfgt) {
-        const int cfg = cfgt % (2 * nVar * nMT), tm = cfgt / (2 * nVar * nMT);
-        const int NT = 2 - (cfg & 1), DA = vars[(cfg >> 1) % nVar], fMT = cfg / (2 * nVar);
-        int last_split = -1;
-        for (int want : kSplits) {
-          ConvGeom c;
-          if (!conv_geom_fixed(B, Cin, Cout, H, W, ks, NT, want, c, DA, S, fMT, tm)) break;
-          if (c.splitK == last_split) continue;
-          last_split = c.splitK;
-          const long blocks = (long)B * c.tiles_per_img * (c.MP / (32 * c.MT)) * c.splitK;
-          if (c.splitK > 1 && blocks > 24L * 256 * 4) break;      // already far more blocks than the chip holds
-          const float tms = time_on_stream(stream, 2, [&]() { return enqueue_conv(c, x, wp, bias, y, B, Cin, Cout, H, W, ks, stream, what, S, Hi, Wi, ms); });
-          tune_log(0, key, NT | (DA << 4) | (fMT << 8) | (tm << 9), c.splitK, tms);
-          if (tms > 0.f && tms < best_ms) { best_ms = tms; best = {NT | (DA << 4) | (fMT << 8) | (tm << 9), c.splitK}; }
-        }
-      }
-      dec = &g_tuned.emplace(key, best).first->second;
-      tune_db_append(key, best);
+      const ConvDecision best = conv_tune(g, key, bx3, x, wp, bias, y, B, Cin, Cout, H, W, ks, stream, what, kind_tag, S, Hi, Wi, ms);
+      dec = &g_tuned.emplace(key, best.encode()).first->second;
+      tune_db_append(key, *dec);
     }
 #endif
     if (dec) {
+      // a decision that does not fit this launch leaves the heuristic geometry in place: the other arithmetic's kernel, a geometry
+      // conv_geom_fixed rejects, or the LDS-free 1x1 kernel (one input tensor; the key does not tell a multi-source launch apart)
+      const ConvDecision d = ConvDecision::decode(*dec);
       ConvGeom t;
-      const int DA = ((*dec)[0] >> 4) & 15;
-      if ((DA >= 3) == bx3 &&
-          conv_geom_fixed(B, Cin, Cout, H, W, ks, (*dec)[0] & 15, (*dec)[1], t, DA, S, ((*dec)[0] >> 8) & 1, ((*dec)[0] >> 9) & 3))
+      if ((d.variant >= 3) == bx3 && !(ms && d.variant == 8) &&
+          conv_geom_fixed(B, Cin, Cout, H, W, ks, d.NT, d.split, t, d.variant, S, d.forceMT, d.tm))
         g = t;
     }
   }
@@ -2001,25 +2037,36 @@ int pnsfm_conv2d_forward_cat(const float* x0, int C0, const float* x1, int C1, c
   return launch_conv(x0, wp_fwd, bias, y, B, Cin, Cout, H, W, ks, (hipStream_t)stream, "conv2d_forward_cat", 0, 1, 0, 0, &ms);
 }
 
-// H, W: size of dY (the conv OUTPUT); x is [B, Cin, Hi, Wi] with Hi = H, Wi = W when S == 1
-static int wgrad_impl(const float* x, const float* dy, float* dw, float* dbias, int B, int Cin, int Cout, int H, int W,
-                      int ks, int S, int Hi, int Wi, void* stream, const ConvSrc* ms = nullptr) {
+// ---- weight gradient: one plan, chosen in steps ------------------------------------------------------------------------------
+// What a weight-gradient call needs to pick and launch one of the four kernels: the call itself, the shape facts every step reads
+// (computed once, wgrad_plan_init) and `run`, the kernel to launch with its parameters.
+struct WgradPlan {
+  const float* x; const float* dy; float* dw; float* dbias;
+  const ConvSrc* ms;               // several input tensors (null: one): only the split-bf16 kernels read them
+  hipStream_t s;
+  int B, Cin, Cout, ks, S;
+  int H0, W0;                      // true size of dY
+  int H3, W3;                      // ... as the split-bf16 kernel sees it (a 1x1 layer's map as 32-wide rows when that is exact)
+  bool v2_ok, v3_ok, v4_ok;        // tap-major / split-bf16 / nine-taps kernel supports the shape
+  bool stem_wg;                    // the 3-channel 5x5 stem: kernel 0 is its own kernel
+  int max_split_f32;               // most [dw | dbias] slabs a pixel split of the f32 kernels may keep in the stream's scratch
+  WgradArgs a;                     // generic kernel: geometry (a.splitP / a.tiles_per_split: its analytic pixel split)
+  size_t smem;
+  int MT, n_tiles, m_tiles;
+  WgradDecision run;
+};
+
+// (a) shape facts and the generic kernel's geometry.  H, W: size of dY (the conv OUTPUT); x is [B, Cin, Hi, Wi] with Hi = H, Wi = W
+// when S == 1
+static int wgrad_plan_init(WgradPlan& p, int H, int W, int Hi, int Wi) {
+  const int B = p.B, Cin = p.Cin, Cout = p.Cout, ks = p.ks, S = p.S;
   if (ks != 1 && ks != 3 && ks != 5 && ks != 7) { set_error("backward_weight: unsupported kernel size %d", ks); return -1; }
   if (S != 1 && S != 2) { set_error("backward_weight: unsupported stride %d", S); return -1; }
-  hipStream_t s = (hipStream_t)stream;
   const int KK = ks * ks, N = Cin * KK, HW = H * W;
-  const int H0 = H, W0 = W;                                  // true image size (the 1x1 path below re-tiles H, W)
-  const bool v2_ok = S == 1 && wgrad2_supported(Cin, Cout, H0, W0, ks);
-  // tap-major kernel: split the 64-pixel tiles so that ~every CU gets one workgroup
-  auto v2_default_split = [&]() -> int {
-    const int base = wgrad2_base_blocks(Cin, Cout, ks), tiles = wgrad2_total_tiles(B, H0, W0);
-    int sp = (256 + base / 2) / base;
-    if (sp < 1) sp = 1;
-    if (sp > tiles) sp = tiles;
-    return sp;
-  };
-  WgradArgs a;
-  a.x = x; a.dy = dy; a.dw = dw; a.dbias = dbias;
+  p.H0 = H; p.W0 = W;                                        // (the 1x1 path below re-tiles H, W)
+  p.v2_ok = S == 1 && wgrad2_supported(Cin, Cout, p.H0, p.W0, ks);
+  WgradArgs& a = p.a;
+  a.x = p.x; a.dy = p.dy; a.dw = p.dw; a.dbias = p.dbias;
   a.B = B; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W; a.KS = ks;
   a.cstride = HW;
   a.S = S;
@@ -2029,7 +2076,8 @@ static int wgrad_impl(const float* x, const float* dy, float* dw, float* dbias, 
     Hi = H; Wi = W;
   }
   a.Hi = Hi; a.Wi = Wi;
-  const int MT = conv_pick_MT(Cout), BM = 32 * MT;
+  p.MT = conv_pick_MT(Cout);
+  const int BM = 32 * p.MT;
   a.mode = (W % 32 == 0) ? 0 : 1;
   a.NCI = 127 / KK + 2;
   if (a.NCI > Cin) a.NCI = Cin;
@@ -2053,18 +2101,20 @@ static int wgrad_impl(const float* x, const float* dy, float* dw, float* dbias, 
     if (smem <= kMaxSmem) break;
   }
   if (smem > kMaxSmem) { set_error("backward_weight: image too wide for the LDS halo patch (W=%d)", W); return -1; }
+  p.smem = smem;
   a.invPW = 1.0f / (float)a.PW;
   a.invPS = 1.0f / (float)(a.PH * a.PW);
   a.vec4 = (HW % 4 == 0) ? 1 : 0;
   a.PTlog = a.PT == 128 ? 7 : (a.PT == 64 ? 6 : 5);
   a.total_tiles = B * a.tiles_per_img;
-  const int n_tiles = ceil_div(N, 128), m_tiles = ceil_div(Cout, BM);
+  p.n_tiles = ceil_div(N, 128);
+  p.m_tiles = ceil_div(Cout, BM);
   // pixel-tile split: minimise  rounds(blocks / resident slots) x (tiles per block + fixed per-block cost)
   {
     int occ = (int)((160 * 1024) / (smem + 512));
     if (occ > 4) occ = 4;                       // 67 VGPR + 32 AGPR -> 4 waves/SIMD
     if (occ < 1) occ = 1;
-    const long slots = 256L * occ, base = (long)n_tiles * m_tiles;
+    const long slots = 256L * occ, base = (long)p.n_tiles * p.m_tiles;
     double best = 1e30;
     a.splitP = 1;
     a.tiles_per_split = a.total_tiles;
@@ -2084,190 +2134,217 @@ static int wgrad_impl(const float* x, const float* dy, float* dw, float* dbias, 
   // allocator cannot see or reuse: 75 MB per slab for the pack5 weight.  Splits are capped so that the slabs of one launch stay under
   // kWgradScratchBudget (the split-bf16 kernels, the default arithmetic, keep far smaller partial tensors and are not affected).
   const size_t kWgradScratchBudget = (size_t)128 << 20;
-  const int max_split_f32 = (int)std::max<size_t>(1, kWgradScratchBudget / (((size_t)Cout * N + Cout) * sizeof(float)));
-  const bool stem_wg = !ms && wgrad_stem5_supported(B, Cin, Cout, H0, W0, ks, S);      // the 3-channel 5x5 stem: its own kernel
-  auto enqueue = [&](int split) -> int {
-    if (split > max_split_f32) split = max_split_f32;
-    if (stem_wg) return enqueue_wgrad_stem5(x, dy, dw, dbias, B, Cout, H0, W0, split, s);
-    WgradArgs c = a;
-    c.tiles_per_split = ceil_div(a.total_tiles, split);
-    c.splitP = ceil_div(a.total_tiles, c.tiles_per_split);
-    // un-split: every dw element and every dbias[co] has exactly one writer -> plain stores into dw / dbias.
-    // split over pixel tiles: every split writes a whole [dw | dbias] slab of the scratch buffer; sum_slabs_kernel adds them.
-    const size_t slab = (size_t)Cout * N + Cout;
-    ScratchLease lease(s, c.splitP > 1 ? (size_t)c.splitP * slab * sizeof(float) : 0);
-    c.zstride = 0;
-    if (c.splitP > 1) {
-      if (!lease.p) return -1;
-      c.dw = lease.as<float>();
-      c.dbias = dbias ? c.dw + (size_t)Cout * N : nullptr;
-      c.zstride = slab;
-    }
-    dim3 grid(n_tiles, m_tiles, c.splitP);
-    if (MT == 2) PNSFM_LAUNCH((conv2d_wgrad_kernel<2>), grid, dim3(256), smem, s, c);
-    else PNSFM_LAUNCH((conv2d_wgrad_kernel<1>), grid, dim3(256), smem, s, c);
-    int rc = check_launch("conv2d_backward_weight");
-    if (!rc && c.splitP > 1) rc = launch_sum_slabs(c.dw, slab, c.splitP, dw, (size_t)Cout * N, dbias, (size_t)Cout, s);
-    return rc;
-  };
-  // split-bf16 kernel (conv2d_wgrad3.hip): part of the split arithmetic mode (pnsfm_set_conv_math), the default there
-  // split-bf16 kernel: a 1x1 layer has no halo, so its map is handed over as 32-wide rows of the flattened image when that
-  // is exact (whole 16/32-column tiles instead of ragged ones for W = 40, 80)
-  const bool flat3 = ks == 1 && (H0 * W0) % 32 == 0;
-  const int H3 = flat3 ? (H0 * W0) / 32 : H0, W3 = flat3 ? 32 : W0;
-  const bool v3_ok = S == 1 && conv_math() == 1 && wgrad3_supported(Cin, Cout, H3, W3, ks) && wgrad3_fits(B, Cin, Cout, H3, W3);
-  auto v3_default_split = [&](int NT) -> int {
-    const int base = wgrad3_base_blocks(Cin, Cout, ks, NT, 0), tiles = wgrad3_total_tiles(B, H3, W3);
-    int split = (2 * 256 + base - 1) / base;            // two workgroups per CU
-    if (split > tiles) split = tiles;
-    return split < 1 ? 1 : split;
-  };
-  int variant = (g_wgrad_variant == 1 && v2_ok) ? 1 : 0;
-  int split2 = v2_ok ? v2_default_split() : 1;
-  int nt3 = wgrad3_nt2_ok(Cin, ks) ? 2 : 1, wm3 = 0;
-  int split3 = v3_ok ? v3_default_split(nt3) : 1;
-  // nine-taps kernel (conv2d_wgrad4.hip): 3x3 only; chosen by the autotuner / a pinned decision (variant 3)
-  const bool v4_ok = v3_ok && ks == 3 && wgrad4_supported(Cin, Cout, H0, W0, ks);
-  int split4 = 1, cfg4 = 2;
-  if (v3_ok && g_wgrad_variant != 0 && g_wgrad_variant != 1) variant = 2;     // -1 (library default) or 2 (pinned)
-  if (ms) {          // several input tensors (ConvSrc): only the split-bf16 kernel reads them
-    if (!v3_ok) { set_error("backward_weight: several input tensors need the split-bf16 weight-gradient kernel"); return -1; }
-    variant = 2;
+  p.max_split_f32 = (int)std::max<size_t>(1, kWgradScratchBudget / (((size_t)Cout * N + Cout) * sizeof(float)));
+  p.stem_wg = !p.ms && wgrad_stem5_supported(B, Cin, Cout, p.H0, p.W0, ks, S);      // the 3-channel 5x5 stem: its own kernel
+  // split-bf16 kernel (conv2d_wgrad3.hip): part of the split arithmetic mode (pnsfm_set_conv_math), the default there.  A 1x1 layer
+  // has no halo, so its map is handed over as 32-wide rows of the flattened image when that is exact (whole 16/32-column tiles
+  // instead of ragged ones for W = 40, 80)
+  const bool flat3 = ks == 1 && (p.H0 * p.W0) % 32 == 0;
+  p.H3 = flat3 ? (p.H0 * p.W0) / 32 : p.H0;
+  p.W3 = flat3 ? 32 : p.W0;
+  p.v3_ok = S == 1 && conv_math() == 1 && wgrad3_supported(Cin, Cout, p.H3, p.W3, ks) && wgrad3_fits(B, Cin, Cout, p.H3, p.W3);
+  // nine-taps kernel (conv2d_wgrad4.hip): 3x3 only; chosen by the autotuner / a pinned decision (kernel 3)
+  p.v4_ok = p.v3_ok && ks == 3 && wgrad4_supported(Cin, Cout, p.H0, p.W0, ks);
+  if (p.ms && !p.v3_ok) { set_error("backward_weight: several input tensors need the split-bf16 weight-gradient kernel"); return -1; }
+  return 0;
+}
+
+// (b) the un-tuned parameters of `kernel` (0, 1 or 2; the nine-taps kernel has none: it runs on a decision only)
+static WgradDecision wgrad_default(const WgradPlan& p, int kernel) {
+  WgradDecision d;
+  d.kernel = kernel;
+  if (kernel == 2) {            // two workgroups per CU
+    d.NT = wgrad3_nt2_ok(p.Cin, p.ks) ? 2 : 1;
+    const int base = wgrad3_base_blocks(p.Cin, p.Cout, p.ks, d.NT, 0), tiles = wgrad3_total_tiles(p.B, p.H3, p.W3);
+    d.split = std::max(1, std::min(tiles, (2 * 256 + base - 1) / base));
+  } else if (kernel == 1) {     // split the 64-pixel tiles so that ~every CU gets one workgroup
+    const int base = wgrad2_base_blocks(p.Cin, p.Cout, p.ks), tiles = wgrad2_total_tiles(p.B, p.H0, p.W0);
+    d.split = std::min(tiles, std::max(1, (256 + base / 2) / base));
+  } else {
+    d.split = p.a.splitP;
   }
+  return d;
+}
+
+// ... and the un-tuned kernel: split-bf16 where the arithmetic mode and the shape allow, unless pnsfm_set_wgrad_variant says otherwise
+static WgradDecision wgrad_default(const WgradPlan& p) {
+  int kernel = (g_wgrad_variant == 1 && p.v2_ok) ? 1 : 0;
+  if (p.v3_ok && g_wgrad_variant != 0 && g_wgrad_variant != 1) kernel = 2;     // -1 (library default) or 2 (pinned)
+  if (p.ms) kernel = 2;
+  return wgrad_default(p, kernel);
+}
+
+// (d) a tuned / pinned decision on this shape: a kernel the shape does not support falls to the generic one; several input tensors
+// force the split-bf16 kernel unless the nine-taps kernel was chosen -- with its defaults when the decision was made for another kernel
+static WgradDecision wgrad_apply(const WgradPlan& p, WgradDecision d) {
+  const bool ok = (d.kernel == 1 && p.v2_ok) || (d.kernel == 2 && p.v3_ok) || (d.kernel == 3 && p.v4_ok);
+  if (p.ms && !(ok && d.kernel >= 2)) return wgrad_default(p, 2);
+  if (!ok) {
+    d.kernel = 0;
+    d.split = std::min(std::max(d.split, 1), p.a.total_tiles);
+    d.split = ceil_div(p.a.total_tiles, ceil_div(p.a.total_tiles, d.split));
+  }
+  return d;
+}
+
+// generic f32 kernel (the stem's own kernel where it applies), pixel tiles split `split` ways
+static int enqueue_wgrad_generic(const WgradPlan& p, int split) {
+  if (split > p.max_split_f32) split = p.max_split_f32;
+  if (p.stem_wg) return enqueue_wgrad_stem5(p.x, p.dy, p.dw, p.dbias, p.B, p.Cout, p.H0, p.W0, split, p.s);
+  const int N = p.Cin * p.ks * p.ks;
+  WgradArgs c = p.a;
+  c.tiles_per_split = ceil_div(c.total_tiles, split);
+  c.splitP = ceil_div(c.total_tiles, c.tiles_per_split);
+  // un-split: every dw element and every dbias[co] has exactly one writer -> plain stores into dw / dbias.
+  // split over pixel tiles: every split writes a whole [dw | dbias] slab of the scratch buffer; sum_slabs_kernel adds them.
+  const size_t slab = (size_t)p.Cout * N + p.Cout;
+  ScratchLease lease(p.s, c.splitP > 1 ? (size_t)c.splitP * slab * sizeof(float) : 0);
+  c.zstride = 0;
+  if (c.splitP > 1) {
+    if (!lease.p) return -1;
+    c.dw = lease.as<float>();
+    c.dbias = p.dbias ? c.dw + (size_t)p.Cout * N : nullptr;
+    c.zstride = slab;
+  }
+  dim3 grid(p.n_tiles, p.m_tiles, c.splitP);
+  if (p.MT == 2) PNSFM_LAUNCH((conv2d_wgrad_kernel<2>), grid, dim3(256), p.smem, p.s, c);
+  else PNSFM_LAUNCH((conv2d_wgrad_kernel<1>), grid, dim3(256), p.smem, p.s, c);
+  int rc = check_launch("conv2d_backward_weight");
+  if (!rc && c.splitP > 1) rc = launch_sum_slabs(c.dw, slab, c.splitP, p.dw, (size_t)p.Cout * N, p.dbias, (size_t)p.Cout, p.s);
+  return rc;
+}
+
+// the launch of p.run: what the tuner times and what wgrad_run issues
+static int wgrad_enqueue(const WgradPlan& p) {
+  const WgradDecision& d = p.run;
+  switch (d.kernel) {
+    case 3: return enqueue_wgrad4(p.x, p.dy, p.dw, p.dbias, p.B, p.Cin, p.Cout, p.H0, p.W0, d.split, d.cfg4(), p.s, p.ms);
+    case 2: return enqueue_wgrad3(p.x, p.dy, p.dw, p.dbias, p.B, p.Cin, p.Cout, p.H3, p.W3, p.ks, d.split, d.NT, d.wm, p.s, p.ms);
+    case 1: return enqueue_wgrad2(p.x, p.dy, p.dw, p.dbias, p.B, p.Cin, p.Cout, p.H0, p.W0, p.ks, d.split, p.s);
+    default: return enqueue_wgrad_generic(p, d.split);
+  }
+}
+
+// (e) meta[8]: which kernel ran, as the profiling tools know them (0 generic / stem, 2 tap-major, 3 split-bf16, 4 nine-taps)
+static int wgrad_run(const WgradPlan& p) {
+  const WgradDecision& d = p.run;
+  const int blocks = d.kernel == 3 ? wgrad4_base_blocks(p.Cin, p.Cout, d.WCI == 1 ? 1 : 2)
+                   : d.kernel == 2 ? wgrad3_base_blocks(p.Cin, p.Cout, p.ks, d.NT, d.wm)
+                   : d.kernel == 1 ? wgrad2_base_blocks(p.Cin, p.Cout, p.ks) : p.n_tiles * p.m_tiles;
+  const int meta[9] = {p.B, p.Cin, p.Cout, p.a.cstride, d.kernel ? p.W0 : p.a.W, p.ks, d.split, blocks * d.split, d.kernel ? d.kernel + 1 : 0};
+  prof_begin(1, 2.0 * p.Cout * (double)p.Cin * p.ks * p.ks * (double)p.B * p.a.cstride, p.s, meta);
+  const int rc = wgrad_enqueue(p);
+  prof_end(1, p.s);
+  return rc;
+}
+
+#ifndef PNSFM_EMU
+// (c) the autotuner: times the pixel splits (and tile parameters) of every kernel the shape supports and returns the fastest
+// (g_tune_mu held).  The four searches are deliberately separate: their progressions, dedupe rules and thresholds differ.
+static WgradDecision wgrad_tune(const WgradPlan& p, const std::array<int, 7>& key) {
+  const int B = p.B, Cin = p.Cin, Cout = p.Cout, ks = p.ks, H0 = p.H0, W0 = p.W0, H3 = p.H3, W3 = p.W3;
+  const ConvSrc* ms = p.ms;
+  const WgradArgs& a = p.a;
+  float best_ms = 1e30f;
+  WgradDecision best = wgrad_default(p, 0);
+  WgradPlan c = p;                                // the candidate: p with another `run`
+  auto time_candidate = [&](const WgradDecision& d) {
+    c.run = d;
+    const float tms = time_on_stream(p.s, 2, [&]() { return wgrad_enqueue(c); });
+    tune_log(key, d.encode()[1], d.split, tms);
+    if (tms > 0.f && tms < best_ms) { best_ms = tms; best = d; }
+  };
+  int prev_tps = -1;
+  const long base = (long)p.n_tiles * p.m_tiles;
+  for (int want = 1; want <= a.total_tiles && !ms; want = want < 8 ? want + 1 : (want * 3 + 1) / 2) {
+    const int tps = ceil_div(a.total_tiles, want);
+    if (tps == prev_tps) continue;
+    prev_tps = tps;
+    const int split = ceil_div(a.total_tiles, tps);
+    if (base * split < 192 && split < a.total_tiles && split < p.max_split_f32) continue;   // cannot fill the chip: not worth timing
+    if ((base * split > 40L * 256 || split > p.max_split_f32) && split > 1) break;
+    time_candidate({0, split});
+  }
+  if (p.v2_ok && !ms) {     // tap-major kernel: pixel splits around one workgroup per CU
+    const int base2 = wgrad2_base_blocks(Cin, Cout, ks), tiles2 = wgrad2_total_tiles(B, H0, W0);
+    int prev = -1;
+    for (int want = 1; want <= tiles2; want = want < 4 ? want + 1 : (want * 3 + 1) / 2) {
+      const int tps = ceil_div(tiles2, want);
+      const int split = ceil_div(tiles2, tps);
+      if (split == prev) continue;
+      prev = split;
+      if ((long)base2 * split < 160 && split < tiles2) continue;      // cannot fill the chip
+      if ((long)base2 * split > 6L * 256 && split > 1) break;
+      time_candidate({1, split});
+    }
+  }
+  if (p.v3_ok) {     // split-bf16 kernel: NT in {1, 2} x co tiles per workgroup x pixel splits around two workgroups per CU
+    const int tiles3 = wgrad3_total_tiles(B, H3, W3);
+    const int wm_most = wgrad3_WM(Cout, 0);
+    for (int NT = 1; NT <= (wgrad3_nt2_ok(Cin, ks) ? 2 : 1); ++NT)
+      for (int WMv = wm_most; WMv >= 1; WMv >>= 1) {
+        const int base3 = wgrad3_base_blocks(Cin, Cout, ks, NT, WMv);
+        int prev = -1;
+        for (int want = 1; want <= tiles3; want = want < 4 ? want + 1 : (want * 3 + 1) / 2) {
+          const int tps = ceil_div(tiles3, want);
+          const int split = ceil_div(tiles3, tps);
+          if (split == prev) continue;
+          prev = split;
+          if ((long)base3 * split < 200 && split < tiles3) continue;      // cannot fill the chip
+          if ((long)base3 * split > 16L * 256 && split > 1) break;
+          if (WMv != wm_most && split > 2) break;     // fewer co tiles per workgroup only pays when it replaces the pixel split
+          if (ms && NT == 2 && !conv_src_aligned(*ms, Cin, 64)) continue;
+          for (int occ = 0; occ < ((ks == 3 && NT == 1 && W3 % 8 == 0) ? 2 : 1); ++occ)    // occ 1: the three-workgroups-per-CU build
+            time_candidate({2, split, NT, WMv | (occ ? 8 : 0)});
+        }
+      }
+  }
+  if (p.v4_ok) {     // nine-taps kernel: ci tiles per workgroup x tile width x pixel splits around two workgroups per CU
+    for (int WCI = 1; WCI <= 2; ++WCI)
+      for (int tgi = 0; tgi < (W0 > 24 ? 2 : 1); ++tgi) {
+        const int TG = W0 > 24 ? 4 + tgi : 3, TR = TG == 3 ? wgrad4_TR(H0, 0) : 4;
+        if (W0 > 24 && round_up(W0, 8 * TG) > round_up(W0, 8 * (9 - TG)) + 8) continue;      // clearly the more wasteful width
+        const int tiles4 = wgrad4_total_tiles(B, H0, W0, TG, TR), base4 = wgrad4_base_blocks(Cin, Cout, WCI);
+        int prev = -1;
+        for (int want = 1; want <= tiles4; want = want < 4 ? want + 1 : (want * 3 + 1) / 2) {
+          const int tps = ceil_div(tiles4, want);
+          const int split = ceil_div(tiles4, tps);
+          if (split == prev) continue;
+          prev = split;
+          if ((long)base4 * split < 200 && split < tiles4) continue;      // cannot fill the chip
+          if ((long)base4 * split > 16L * 256 && split > 1) break;
+          time_candidate({3, split, 1, 0, WCI, TG, TR});
+        }
+      }
+  }
+  return best;
+}
+#endif
+
+static int wgrad_impl(const float* x, const float* dy, float* dw, float* dbias, int B, int Cin, int Cout, int H, int W,
+                      int ks, int S, int Hi, int Wi, void* stream, const ConvSrc* ms = nullptr) {
+  WgradPlan p;
+  p.x = x; p.dy = dy; p.dw = dw; p.dbias = dbias; p.ms = ms; p.s = (hipStream_t)stream;
+  p.B = B; p.Cin = Cin; p.Cout = Cout; p.ks = ks; p.S = S;
+  if (wgrad_plan_init(p, H, W, Hi, Wi)) return -1;
+  p.run = wgrad_default(p);
   {
     // tuned / pinned decision of this shape (autotuner, PNSFM_TUNE_DB / shipped database, pnsfm_tune_set -- the latter in
     // every build, so tests can pin kernel, split, ci tiles per wave and co tiles per workgroup on the emulator too)
-    const std::array<int, 7> key = {2 + 10 * S + (v3_ok ? 100 : 0) + (ms ? 1000 : 0), B, Cin, Cout, a.cstride, W, ks};
+    const std::array<int, 7> key = {2 + 10 * S + (p.v3_ok ? 100 : 0) + (ms ? 1000 : 0), B, Cin, Cout, p.a.cstride, p.a.W, ks};
     const bool tune = autotune_enabled();
     std::lock_guard<std::mutex> lk(g_tune_mu);
     const std::array<int, 2>* dec = tune_lookup(key, tune);
 #ifndef PNSFM_EMU
     // (first seen inside a hipGraph capture: keep the analytic split -- timing would synchronise)
-    if (!dec && tune && !stream_capturing(s)) {
-      float best_ms = 1e30f;
-      int best_split = a.splitP, prev_tps = -1;
-      const long base = (long)n_tiles * m_tiles;
-      for (int want = 1; want <= a.total_tiles && !ms; want = want < 8 ? want + 1 : (want * 3 + 1) / 2) {
-        const int tps = ceil_div(a.total_tiles, want);
-        if (tps == prev_tps) continue;
-        prev_tps = tps;
-        const int split = ceil_div(a.total_tiles, tps);
-        if (base * split < 192 && split < a.total_tiles && split < max_split_f32) continue;   // cannot fill the chip: not worth timing
-        if ((base * split > 40L * 256 || split > max_split_f32) && split > 1) break;
-        const float ms = time_on_stream(s, 2, [&]() { return enqueue(split); });
-        tune_log(2, key, 0, split, ms);
-        if (ms > 0.f && ms < best_ms) { best_ms = ms; best_split = split; }
-      }
-      int best_variant = 0;
-      if (v2_ok && !ms) {     // tap-major kernel: pixel splits around one workgroup per CU
-        const int base2 = wgrad2_base_blocks(Cin, Cout, ks), tiles2 = wgrad2_total_tiles(B, H0, W0);
-        int prev = -1;
-        for (int want = 1; want <= tiles2; want = want < 4 ? want + 1 : (want * 3 + 1) / 2) {
-          const int tps = ceil_div(tiles2, want);
-          const int split = ceil_div(tiles2, tps);
-          if (split == prev) continue;
-          prev = split;
-          if ((long)base2 * split < 160 && split < tiles2) continue;      // cannot fill the chip
-          if ((long)base2 * split > 6L * 256 && split > 1) break;
-          const float ms = time_on_stream(s, 2, [&]() { return enqueue_wgrad2(x, dy, dw, dbias, B, Cin, Cout, H0, W0, ks, split, s); });
-          tune_log(2, key, 1, split, ms);
-          if (ms > 0.f && ms < best_ms) { best_ms = ms; best_split = split; best_variant = 1; }
-        }
-      }
-      if (v3_ok) {     // split-bf16 kernel: NT in {1, 2} x co tiles per workgroup x pixel splits around two workgroups per CU
-        const int tiles3 = wgrad3_total_tiles(B, H3, W3);
-        const int wm_most = wgrad3_WM(Cout, 0);
-        for (int NT = 1; NT <= (wgrad3_nt2_ok(Cin, ks) ? 2 : 1); ++NT)
-          for (int WMv = wm_most; WMv >= 1; WMv >>= 1) {
-            const int base3 = wgrad3_base_blocks(Cin, Cout, ks, NT, WMv);
-            int prev = -1;
-            for (int want = 1; want <= tiles3; want = want < 4 ? want + 1 : (want * 3 + 1) / 2) {
-              const int tps = ceil_div(tiles3, want);
-              const int split = ceil_div(tiles3, tps);
-              if (split == prev) continue;
-              prev = split;
-              if ((long)base3 * split < 200 && split < tiles3) continue;      // cannot fill the chip
-              if ((long)base3 * split > 16L * 256 && split > 1) break;
-              if (WMv != wm_most && split > 2) break;     // fewer co tiles per workgroup only pays when it replaces the pixel split
-              if (ms && NT == 2 && !conv_src_aligned(*ms, Cin, 64)) continue;
-              for (int occ = 0; occ < ((ks == 3 && NT == 1 && W3 % 8 == 0) ? 2 : 1); ++occ) {    // occ 1: the three-workgroups-per-CU build
-                const int wmv = WMv | (occ ? 8 : 0);
-                const float tms = time_on_stream(s, 2, [&]() { return enqueue_wgrad3(x, dy, dw, dbias, B, Cin, Cout, H3, W3, ks, split, NT, wmv, s, ms); });
-                tune_log(2, key, 2 | (NT << 4) | (wmv << 6), split, tms);
-                if (tms > 0.f && tms < best_ms) { best_ms = tms; best_split = split; best_variant = 2 | (NT << 4) | (wmv << 6); }
-              }
-            }
-          }
-      }
-      if (v4_ok) {     // nine-taps kernel: ci tiles per workgroup x tile width x pixel splits around two workgroups per CU
-        for (int WCI = 1; WCI <= 2; ++WCI)
-          for (int tgi = 0; tgi < (W0 > 24 ? 2 : 1); ++tgi) {
-            const int TG = W0 > 24 ? 4 + tgi : 3, TR = TG == 3 ? wgrad4_TR(H0, 0) : 4;
-            if (W0 > 24 && round_up(W0, 8 * TG) > round_up(W0, 8 * (9 - TG)) + 8) continue;      // clearly the more wasteful width
-            const int tiles4 = wgrad4_total_tiles(B, H0, W0, TG, TR), base4 = wgrad4_base_blocks(Cin, Cout, WCI);
-            const int cfg = WCI | (TG << 4) | (TR << 8);
-            int prev = -1;
-            for (int want = 1; want <= tiles4; want = want < 4 ? want + 1 : (want * 3 + 1) / 2) {
-              const int tps = ceil_div(tiles4, want);
-              const int split = ceil_div(tiles4, tps);
-              if (split == prev) continue;
-              prev = split;
-              if ((long)base4 * split < 200 && split < tiles4) continue;      // cannot fill the chip
-              if ((long)base4 * split > 16L * 256 && split > 1) break;
-              const float tms = time_on_stream(s, 2, [&]() { return enqueue_wgrad4(x, dy, dw, dbias, B, Cin, Cout, H0, W0, split, cfg, s, ms); });
-              tune_log(2, key, 3 | (cfg << 4), split, tms);
-              if (tms > 0.f && tms < best_ms) { best_ms = tms; best_split = split; best_variant = 3 | (cfg << 4); }
-            }
-          }
-      }
-      dec = &g_tuned.emplace(key, std::array<int, 2>{best_split, best_variant}).first->second;
+    if (!dec && tune && !stream_capturing(p.s)) {
+      dec = &g_tuned.emplace(key, wgrad_tune(p, key).encode()).first->second;
       tune_db_append(key, *dec);
     }
 #endif
-    if (dec) {
-      const int d0 = (*dec)[0], d1 = (*dec)[1];
-      variant = ((d1 & 15) == 1 && v2_ok) ? 1 : (((d1 & 15) == 2 && v3_ok) ? 2 : (((d1 & 15) == 3 && v4_ok) ? 3 : 0));
-      if (ms && variant != 3) variant = 2;
-      if (variant == 3) { split4 = d0; cfg4 = d1 >> 4; }
-      if (variant == 2 && (d1 & 15) != 2) { /* a pinned decision for another kernel: keep the split-bf16 defaults */ }
-      else if (variant == 2) { split3 = d0; nt3 = ((d1 >> 4) & 3) == 2 ? 2 : 1; wm3 = (d1 >> 6) & 15; }
-      else if (variant == 1) split2 = d0;
-      else {
-        int sp = d0;
-        if (sp < 1) sp = 1;
-        if (sp > a.total_tiles) sp = a.total_tiles;
-        a.tiles_per_split = ceil_div(a.total_tiles, sp);
-        a.splitP = ceil_div(a.total_tiles, a.tiles_per_split);
-      }
-    }
+    if (dec) p.run = wgrad_apply(p, WgradDecision::decode(*dec));
   }
-  const double flops = 2.0 * Cout * (double)Cin * KK * (double)B * HW;
-  if (variant == 3) {
-    const int meta[9] = {B, Cin, Cout, a.cstride, W0, ks, split4, wgrad4_base_blocks(Cin, Cout, (cfg4 & 15) == 1 ? 1 : 2) * split4, 4};
-    prof_begin(1, flops, s, meta);
-    const int rc = enqueue_wgrad4(x, dy, dw, dbias, B, Cin, Cout, H0, W0, split4, cfg4, s, ms);
-    prof_end(1, s);
-    return rc;
-  }
-  if (variant == 2) {
-    const int meta[9] = {B, Cin, Cout, a.cstride, W0, ks, split3, wgrad3_base_blocks(Cin, Cout, ks, nt3, wm3) * split3, 3};
-    prof_begin(1, flops, s, meta);
-    const int rc = enqueue_wgrad3(x, dy, dw, dbias, B, Cin, Cout, H3, W3, ks, split3, nt3, wm3, s, ms);
-    prof_end(1, s);
-    return rc;
-  }
-  if (variant == 1) {
-    const int meta[9] = {B, Cin, Cout, a.cstride, W0, ks, split2, wgrad2_base_blocks(Cin, Cout, ks) * split2, 2};
-    prof_begin(1, flops, s, meta);
-    const int rc = enqueue_wgrad2(x, dy, dw, dbias, B, Cin, Cout, H0, W0, ks, split2, s);
-    prof_end(1, s);
-    return rc;
-  }
-  const int meta[9] = {B, Cin, Cout, a.cstride, W, ks, a.splitP, (int)(n_tiles * m_tiles * a.splitP), 0};
-  prof_begin(1, flops, s, meta);
-  const int rc = enqueue(a.splitP);
-  prof_end(1, s);
-  return rc;
+  return wgrad_run(p);
 }
 
 int pnsfm_conv2d_backward_weight(const float* x, const float* dy, float* dw, float* dbias, int B, int Cin, int Cout,

@@ -333,6 +333,36 @@ def test_conv1x1_lds_free_kernel(emulated_kernels, shape, cfg):
     lib.pnsfm_set_conv_variant(0)      # clears the pinned entries
 
 
+def test_conv1x1_lds_free_pin_falls_back_for_several_sources(emulated_kernels):
+    """The forward key has no bit for 'several input tensors', so a variant-8 decision (the LDS-free 1x1 kernel reads ONE tensor) of a
+    single-source 1x1 shape is also looked up by a conv2d_forward_cat launch of that shape.  Such a launch keeps the
+    heuristic geometry, as for any decision that does not fit; the single-source launch still gets variant 8.  Before the decode step
+    had this check the cat call raised HipError ('the LDS-free 1x1 kernel reads one input tensor')."""
+    import ctypes
+    import torch.nn.functional as F
+    from packnet_sfm.hip import _lib, ops
+    lib = _lib.get()
+    lib.pnsfm_set_conv_math(1)
+    B, C0, C1, Cout, H, W, ks = 1, 16, 16, 32, 4, 32, 1
+    assert _flat32(H, W) == (H, W)           # 32-wide already: launch_conv does not re-tile, the key carries H x W as they are
+    key = (ctypes.c_int * 7)(110, 1, 32, 32, 4, 32, 1)
+    assert list(key) == [0 + 10 + 100, B, C0 + C1, Cout, H, W, ks]
+    assert lib.pnsfm_tune_set(key, 1 | (8 << 4), 1) == 0
+    g = torch.Generator().manual_seed(1632)
+    x0, x1 = torch.randn(B, C0, H, W, generator=g), torch.randn(B, C1, H, W, generator=g)
+    w = torch.randn(Cout, C0 + C1, ks, ks, generator=g) * 0.1
+    b = torch.randn(Cout, generator=g)
+    wf, _ = ops.conv2d_pack(w)
+    yr = F.conv2d(torch.cat([x0, x1], 1), w, b)
+    out = (ctypes.c_int * 8)()
+    y = ops.conv2d_forward_cat([x0, x1], wf, b, Cout, ks)
+    assert ops.conv2d_last_config()[0] != 8, ops.conv2d_last_config()
+    P.check(y, yr, 1e-5, 'fwd (1x1, two sources, variant-8 pin ignored)')
+    P.check(ops.conv2d_forward(torch.cat([x0, x1], 1), wf, b, Cout, ks), yr, 1e-5, 'fwd (1x1, no LDS)')
+    assert lib.pnsfm_conv2d_last_config(out) == 0 and out[0] == 8 and out[1] == 1, list(out)
+    lib.pnsfm_set_conv_variant(0)      # clears the pinned entry
+
+
 @pytest.mark.parametrize('shape', [(1, 64, 64, 4, 32, 3), (2, 33, 70, 5, 16, 3), (1, 130, 20, 9, 8, 3), (2, 16, 96, 3, 64, 1),
                                    (1, 40, 64, 6, 24, 5), (3, 17, 31, 7, 40, 1), (2, 64, 64, 8, 32, 3)])
 def test_conv2d_wgrad_tap_major(emulated_kernels, shape):
