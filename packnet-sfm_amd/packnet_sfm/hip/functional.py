@@ -4,7 +4,9 @@ These Functions are what the drop-in modules (networks/layers/packnet/layers01.p
 losses/multiview_photometric_loss.py) are made of.  Autograd only sequences the launches; every derivative
 is computed by a HIP kernel of libpnsfm_hip.so.
 """
+import contextlib
 import os
+import weakref
 
 import torch
 from torch.autograd import Function
@@ -136,7 +138,6 @@ _PACK_TABLES = {}       # device -> [signature, table tensor, n items, blocks, i
 
 
 def _register_packed(cache, weight):
-    import weakref
     ent = _PACK_REG.get(id(cache))
     if ent is not None and ent[0]() is cache and ent[1]() is weight:
         return
@@ -171,13 +172,12 @@ def _run_pack_table(slot, dev, pairs):
         tab = _PACK_TABLES[slot] = [sig, table, n, blocks, covered]      # (indices into `pairs`: no strong references kept)
     if not tab[2]:
         return []
-    with torch.cuda.device(dev) if dev.type == 'cuda' else _nullctx():
+    with torch.cuda.device(dev) if dev.type == 'cuda' else contextlib.nullcontext():
         ops.conv2d_pack_table_run(tab[1], tab[2], tab[3])
     return [pairs[i] for i in tab[4]]
 
 
 def _pack_batch_on():
-    import os
     if os.environ.get('PNSFM_PACK_BATCH', '1') == '0' or not _PACK_REG:
         return False
     return not (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing())
@@ -204,14 +204,6 @@ def stamp_packed(pairs):
             c._src_f = c._src_b = w.detach()
 
 
-class _nullctx:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
-
-
 class _WgradStream:
     """Weight gradients on a side HIP stream.  ON by default since round 5 (PNSFM_WGRAD_STREAM=0 switches it off): most launches of
     the backward pass are resident in ONE round of workgroups (tools/bx3_ablate.py: prologue -> matrix work -> store burst, all
@@ -235,8 +227,7 @@ class _WgradStream:
     accumulated by compute-stream kernels during the same backward pass: for those the weight gradient still runs on the
     side stream next to the node's own data gradient, but the compute stream waits for it before the node returns.
     """
-    import os as _os
-    _env = _os.environ.get('PNSFM_WGRAD_STREAM', '1')
+    _env = os.environ.get('PNSFM_WGRAD_STREAM', '1')
     enabled = _env not in ('0', '')
     # PNSFM_WGRAD_STREAM=<n> with n > 1: only layers whose gradient map has at most n pixels (batch x H x W) go to the side stream --
     # the low-resolution layers, whose launches are resident in one round and latency-bound (tools/bx3_ablate.py), overlap well;
@@ -344,6 +335,40 @@ class _WgradStream:
         return out
 
     @classmethod
+    def run_beside(cls, dy, want_w, detached, wgrad, dgrad, tensors, pure=True):
+        """(dx, dw, db) of one conv node, the weight gradient beside the data gradient: wgrad() -> (dw, db) goes to the side stream
+        first when `dy` qualifies (see run: `tensors` are what it reads, `detached` / `pure` as there), then dgrad() -> dx (or None: no
+        data gradient wanted) on the compute stream, then the weight gradient in line if it was not forked, then the wait of a
+        gradient that must not stay in flight."""
+        dx = dw = db = wait = None
+        if want_w and cls.use_for(dy):
+            r = cls.run(wgrad, *tensors, detached=detached, pure=pure)
+            (dw, db), wait = (r, None) if detached else r
+            want_w = False
+        if dgrad is not None:
+            dx = dgrad()
+        if want_w:
+            dw, db = wgrad()
+        if wait is not None:
+            wait()
+        return dx, dw, db
+
+    @classmethod
+    def seq_fork(cls, dy, want_w, detached):
+        """(main raw stream, side raw stream or 0, side torch Stream or None) for a block-sequencer backward body, which forks, launches
+        and joins by itself (csrc/seq/pnsfm_seq.cpp: conv_backward_tail, the order of run_beside with the one-call fork of run).  A
+        detached weight gradient is left in flight: the device is marked for the end-of-backward join here."""
+        if not dy.is_cuda:
+            return 0, 0, None
+        main_raw = ops.launch_stream_raw(dy.device)
+        if want_w and cls.use_for(dy):
+            side = cls.get(dy.device)
+            if detached:
+                cls._pending.add(dy.device)
+            return main_raw, side.cuda_stream, side
+        return main_raw, 0, None
+
+    @classmethod
     def _end_of_backward(cls):
         """Autograd-engine callback at the end of a backward pass: the compute streams wait for the weight gradients
         still in flight, and the per-pass use counts are dropped."""
@@ -359,18 +384,6 @@ class _WgradStream:
 
 
 _FAST_FORK = os.environ.get('PNSFM_FAST_FORK', '1') != '0'
-
-
-def _seq_streams(dy, want_w):
-    """(main raw stream, side raw stream or 0, side torch Stream or None) for a sequencer backward body: the weight gradient goes to the
-    side stream under exactly the conditions _WgradStream.run(pure=True) takes the one-call fork."""
-    if not dy.is_cuda:
-        return 0, 0, None
-    main_raw = ops.launch_stream_raw(dy.device)
-    if want_w and _FAST_FORK and _WgradStream.use_for(dy):
-        side = _WgradStream.get(dy.device)
-        return main_raw, side.cuda_stream, side
-    return main_raw, 0, None
 
 
 def set_wgrad_stream(on):
@@ -394,7 +407,6 @@ def _drop_slot(key, ref):
 def register_grad_slots(pairs):
     """pairs: iterable of (parameter, view).  Returns a handle whose .remove() unregisters them (also done automatically when a
     parameter is garbage-collected, and when a newer optimizer registers the same parameter: the newer registration wins)."""
-    import weakref
     mine = []
     for p, v in pairs:
         key = id(p)
@@ -543,73 +555,124 @@ def conv2d_h16_composed(P, W_eff, bias_eff, cache, key):
     return ops.conv2d_forward_h16((P.contiguous(),), cache.wp_h16, cache.bias_h16, Cout, ks)
 
 
+# ---- the stride-1 conv nodes (Conv2dFn, ConvGnActFn): what their backward bodies share once dy exists ---------------------------------
+def _seq_takes(dy, xs, want_w, cat_wgrad, g_tap):
+    """May the block sequencer run this conv backward as its one call?  Its weight gradient is the multi-source kernel or nothing (no
+    concatenating fallback), its tap is the addend of the split-bf16 backward-data kernels, and it forks to the side stream with the
+    one C call only: under PNSFM_FAST_FORK=0 a weight gradient bound for the side stream takes the Python body, whose
+    _WgradStream.run forks the torch way."""
+    if want_w and not _FAST_FORK and _WgradStream.use_for(dy):
+        return False
+    return (not want_w or len(xs) == 1 or (cat_wgrad and get_conv_math() == 'bx3')) and (g_tap is None or get_conv_math() == 'bx3')
+
+
+def _conv_bwd_plan(ctx, dy, xs, g_tap, x0):
+    """What a stride-1 conv backward decides before it enqueues anything: ((sequencer, main raw stream, side raw stream, side Stream) or
+    None for the Python body, need_dx, want_w, detached, weight slot, bias slot).  x0: position of the first source among the
+    node's inputs (weight and bias are inputs 0 and 1 of both nodes)."""
+    need_dx = any(ctx.needs_input_grad[x0:])
+    want_w = bool(ctx.needs_input_grad[0] or (ctx.meta[3] and ctx.needs_input_grad[1]))
+    detached = _WgradStream.side_ok(*ctx.params)
+    sw, sb = _slots_for(ctx.params[0], ctx.params[1], detached and ctx.needs_input_grad[0])
+    sq = _seq.get()
+    seq = None
+    if sq is not None and _seq_takes(dy, xs, want_w, ctx.cat_wgrad, g_tap):
+        seq = (sq,) + _WgradStream.seq_fork(dy, want_w, detached)
+    return seq, need_dx, want_w, detached, sw, sb
+
+
+def _conv_bwd_python(ctx, dy, xs, wp_bwd, g_tap, need_dx, want_w, detached, sw, sb):
+    """The Python body of a stride-1 conv backward from dy on: (gradient of the whole concatenation or None, dw, db)."""
+    Cin, _, ks, has_bias = ctx.meta[:4]
+    # (the multi-source envelope was decided at forward time under the arithmetic mode in force THEN; a set_conv_math('f32') between
+    # forward and backward takes the multi-source kernel away -- ADVICE r04 -- so the mode is re-checked here)
+    direct = len(xs) == 1 or (ctx.cat_wgrad and get_conv_math() == 'bx3')
+
+    def wgrad():
+        if len(xs) == 1:
+            return ops.conv2d_backward_weight(xs[0], dy, ks, want_bias=has_bias, dw_out=sw, db_out=sb)
+        if direct:
+            return ops.conv2d_backward_weight_cat(xs, dy, ks, want_bias=has_bias, dw_out=sw, db_out=sb)
+        # outside the multi-source weight-gradient kernel's envelope (decided once, in _cat_wgrad_ok): concatenate for this kernel
+        return ops.conv2d_backward_weight(torch.cat(xs, 1), dy, ks, want_bias=has_bias, dw_out=sw, db_out=sb)
+
+    # (pure: the closure launches kernels only -- the concatenating fallback calls torch.cat and takes the stream-context path)
+    return _WgradStream.run_beside(dy, want_w, detached, wgrad, (lambda: _dgrad_tap(dy, wp_bwd, Cin, ks, g_tap)) if need_dx else None,
+                                   (dy, *xs), pure=direct)
+
+
+def _split_dx(dx, xs, needs):
+    """The gradient of the whole concatenation as one channel slice (a view) per source that wants its gradient."""
+    if dx is None:
+        return (None,) * len(xs)
+    if len(xs) == 1:
+        return (dx,)
+    dxs, c0 = [], 0
+    for t, need in zip(xs, needs):
+        dxs.append(dx[:, c0:c0 + t.shape[1]] if need else None)
+        c0 += t.shape[1]
+    return tuple(dxs)
+
+
 class Conv2dFn(Function):
-    """y = conv2d(zero_pad_{k//2}(x), weight) + bias, stride 1 (fp32 implicit GEMM on the matrix pipe; arithmetic: set_conv_math)."""
+    """y = conv2d(zero_pad_{k//2}(cat(xs, 1)), weight) + bias, stride 1 (fp32 implicit GEMM on the matrix pipe; arithmetic: set_conv_math).
+    xs: 1..3 tensors.  With several, the concatenation is folded into the K loop of the split-bf16 kernels (the decoder's skip
+    connections, reference PackNet01.py:138-174): the concatenated tensor -- 254 MB for iconv1 at 192x640 batch 4 -- is neither written
+    nor read.  Backward-data produces the gradient of the whole concatenation in one tensor; the inputs receive channel slices of it
+    (views)."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, cache, recording=True, tap=False):
-        x = x.contiguous()
-        need_dx = ctx.needs_input_grad[0]
+    def forward(ctx, weight, bias, cache, recording, cat_wgrad, tap, *xs):
+        xs = tuple(t.contiguous() for t in xs)
+        ctx.cat_wgrad = cat_wgrad
+        need_dx = any(ctx.needs_input_grad[6:])
         wp_fwd, wp_bwd = cache.get(weight, need_dx)
         Cout, Cin, ks, _ = weight.shape
-        if x.shape[1] != Cin:
-            raise RuntimeError("conv2d: input has %d channels, weight expects %d" % (x.shape[1], Cin))
+        if sum(t.shape[1] for t in xs) != Cin:
+            if len(xs) == 1:
+                raise RuntimeError("conv2d: input has %d channels, weight expects %d" % (xs[0].shape[1], Cin))
+            raise RuntimeError("conv2d_cat: inputs have %d channels, weight expects %d" % (sum(t.shape[1] for t in xs), Cin))
         sq = _seq.get()
         if sq is not None:
-            y = sq.conv2d_forward([x], wp_fwd, bias, Cin, Cout, ks, ops.launch_stream_raw(x.device))
+            y = sq.conv2d_forward(list(xs), wp_fwd, bias, Cin, Cout, ks, ops.launch_stream_raw(xs[0].device))
+        elif len(xs) == 1:
+            y = ops.conv2d_forward(xs[0], wp_fwd, bias.detach() if bias is not None else None, Cout, ks)
         else:
-            y = ops.conv2d_forward(x, wp_fwd, bias.detach() if bias is not None else None, Cout, ks)
-        ctx.save_for_backward(x, wp_bwd if wp_bwd is not None else x.new_empty(0))
+            y = ops.conv2d_forward_cat(xs, wp_fwd, bias.detach() if bias is not None else None, Cout, ks)
+        ctx.save_for_backward(wp_bwd if wp_bwd is not None else y.new_empty(0), *xs)
         ctx.meta = (Cin, Cout, ks, bias is not None)
         ctx.params = (weight, bias)
         _WgradStream.note_use(recording, weight, bias)
-        # tap (see conv2d_tap): the input comes back as a second output; what its other consumers send back arrives here as g_tap
-        # (None when nobody read the tap: no zero tensor is materialised) and is added inside the backward-data launch
+        # tap (single input only, see conv2d_tap): the input comes back as a second output; what its other consumers send back arrives
+        # in backward as g_tap (None when nobody read the tap: no zero tensor is materialised) and is added inside the backward-data launch
         if tap:
             ctx.set_materialize_grads(False)
-            return y, x.view_as(x)
+            return y, xs[0].view_as(xs[0])
         return y
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dy, g_tap=None):
         if dy is None:         # only the tap was used: its gradient passes straight through
-            return g_tap, None, None, None, None, None
-        x, wp_bwd = ctx.saved_tensors
+            return (None,) * 6 + (g_tap,)
+        wp_bwd, *xs = ctx.saved_tensors
         Cin, Cout, ks, has_bias = ctx.meta
         dy = dy.contiguous()
-        dx = dw = db = None
-        want_w = ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2])
-        detached = _WgradStream.side_ok(*ctx.params)
-        sw, sb = _slots_for(ctx.params[0], ctx.params[1], detached and ctx.needs_input_grad[1])
-        sq = _seq.get()
-        if sq is not None and (g_tap is None or get_conv_math() == 'bx3'):
-            main_raw, side_raw, side = _seq_streams(dy, want_w)
-            dx, dw, db = sq.conv2d_backward(dy, [x], wp_bwd, Cin, Cout, ks, has_bias, bool(ctx.needs_input_grad[0]), bool(want_w), sw, sb, g_tap,
-                                            main_raw, side_raw, bool(detached), side)
-            if side is not None and detached:
-                _WgradStream._pending.add(dy.device)
-            return dx, dw, db, None, None, None
-        wait = None
-        if want_w and _WgradStream.use_for(dy):
-            r = _WgradStream.run(lambda: ops.conv2d_backward_weight(x, dy, ks, want_bias=has_bias, dw_out=sw, db_out=sb), x, dy,
-                                 detached=detached)
-            (dw, db), wait = (r, None) if detached else r
-            want_w = False
-        if ctx.needs_input_grad[0]:
-            dx = _dgrad_tap(dy, wp_bwd, Cin, ks, g_tap)
-        if want_w:
-            dw, db = ops.conv2d_backward_weight(x, dy, ks, want_bias=has_bias, dw_out=sw, db_out=sb)
-        if wait is not None:
-            wait()
-        return dx, dw, db, None, None, None
+        seq, need_dx, want_w, detached, sw, sb = _conv_bwd_plan(ctx, dy, xs, g_tap, 6)
+        if seq is not None:
+            sq, main_raw, side_raw, side = seq
+            dx, dw, db = sq.conv2d_backward(dy, xs, wp_bwd, Cin, Cout, ks, has_bias, need_dx, want_w, sw, sb, g_tap, main_raw, side_raw,
+                                            detached, side)
+        else:
+            dx, dw, db = _conv_bwd_python(ctx, dy, xs, wp_bwd, g_tap, need_dx, want_w, detached, sw, sb)
+        return (dw, db, None, None, None, None) + _split_dx(dx, xs, ctx.needs_input_grad[6:])
 
 
 def conv2d(x, weight, bias, cache):
     if x.dtype == torch.float16:
         return _conv2d_h16((x,), weight, bias, cache)
     _h16_input(x, weight)
-    return Conv2dFn.apply(x, weight, bias, cache, torch.is_grad_enabled())
+    return Conv2dFn.apply(weight, bias, cache, torch.is_grad_enabled(), False, False, x)
 
 
 # Round 5: gradient taps.  A tensor read by a convolution AND by something else (the encoder feature that is also a decoder skip input;
@@ -652,88 +715,16 @@ def conv2d_tap(x, weight, bias, cache):
         return _conv2d_h16((x,), weight, bias, cache), x
     if not (_GRAD_TAPS and torch.is_grad_enabled() and x.requires_grad and _tap_ok(weight)):
         return conv2d(x, weight, bias, cache), x
-    return Conv2dFn.apply(x, weight, bias, cache, True, True)
+    return Conv2dFn.apply(weight, bias, cache, True, False, True, x)
 
 
-class Conv2dCatFn(Function):
-    """y = conv2d(zero_pad(cat((x0, x1[, x2]), 1)), weight) + bias with the concatenation folded into the K loop of the split-bf16
-    kernels (the decoder's skip connections, reference PackNet01.py:138-174): the concatenated tensor -- 254 MB for iconv1 at
-    192x640 batch 4 -- is neither written nor read.  Backward-data produces the gradient of the whole concatenation in one tensor;
-    the inputs receive channel slices of it (views)."""
-
-    @staticmethod
-    def forward(ctx, weight, bias, cache, recording, cat_wgrad, *xs):
-        xs = tuple(t.contiguous() for t in xs)
-        ctx.cat_wgrad = cat_wgrad
-        need_dx = any(ctx.needs_input_grad[5:])
-        wp_fwd, wp_bwd = cache.get(weight, need_dx)
-        Cout, Cin, ks, _ = weight.shape
-        if sum(t.shape[1] for t in xs) != Cin:
-            raise RuntimeError("conv2d_cat: inputs have %d channels, weight expects %d" % (sum(t.shape[1] for t in xs), Cin))
-        sq = _seq.get()
-        if sq is not None:
-            y = sq.conv2d_forward(list(xs), wp_fwd, bias, Cin, Cout, ks, ops.launch_stream_raw(xs[0].device))
-        else:
-            y = ops.conv2d_forward_cat(xs, wp_fwd, bias.detach() if bias is not None else None, Cout, ks)
-        ctx.save_for_backward(wp_bwd if wp_bwd is not None else xs[0].new_empty(0), *xs)
-        ctx.meta = (Cin, Cout, ks, bias is not None)
-        ctx.params = (weight, bias)
-        _WgradStream.note_use(recording, weight, bias)
-        return y
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, dy):
-        wp_bwd, *xs = ctx.saved_tensors
-        Cin, Cout, ks, has_bias = ctx.meta
-        dy = dy.contiguous()
-        dxs = [None] * len(xs)
-        dw = db = None
-        detached = _WgradStream.side_ok(*ctx.params)
-        sw, sb = _slots_for(ctx.params[0], ctx.params[1], detached and ctx.needs_input_grad[0])
-        want_w = ctx.needs_input_grad[0] or (has_bias and ctx.needs_input_grad[1])
-        sq = _seq.get()
-        if sq is not None and (not want_w or (ctx.cat_wgrad and get_conv_math() == 'bx3')):
-            need_dx = any(ctx.needs_input_grad[5:])
-            main_raw, side_raw, side = _seq_streams(dy, want_w)
-            dx, dw, db = sq.conv2d_backward(dy, list(xs), wp_bwd, Cin, Cout, ks, has_bias, need_dx, bool(want_w), sw, sb, None, main_raw, side_raw,
-                                            bool(detached), side)
-            if side is not None and detached:
-                _WgradStream._pending.add(dy.device)
-            if need_dx:
-                c0 = 0
-                for i, t in enumerate(xs):
-                    if ctx.needs_input_grad[5 + i]:
-                        dxs[i] = dx[:, c0:c0 + t.shape[1]]
-                    c0 += t.shape[1]
-            return (dw, db, None, None, None) + tuple(dxs)
-
-        def wgrad():
-            # (the envelope was decided at forward time under the arithmetic mode in force THEN; a set_conv_math('f32') between
-            # forward and backward takes the multi-source kernel away -- ADVICE r04 -- so the mode is re-checked here)
-            if ctx.cat_wgrad and get_conv_math() == 'bx3':
-                return ops.conv2d_backward_weight_cat(xs, dy, ks, want_bias=has_bias, dw_out=sw, db_out=sb)
-            # outside the multi-source weight-gradient kernel's envelope (decided once, in conv2d_cat): concatenate for this kernel
-            return ops.conv2d_backward_weight(torch.cat(xs, 1), dy, ks, want_bias=has_bias, dw_out=sw, db_out=sb)
-
-        wait = None
-        if want_w and _WgradStream.use_for(dy):
-            # (pure: the closure launches kernels only -- the concatenating fallback calls torch.cat and takes the stream-context path)
-            r = _WgradStream.run(wgrad, dy, *xs, detached=detached, pure=(len(xs) == 1 or (ctx.cat_wgrad and get_conv_math() == 'bx3')))
-            (dw, db), wait = (r, None) if detached else r
-            want_w = False
-        if any(ctx.needs_input_grad[5:]):
-            dx = ops.conv2d_backward_data(dy, wp_bwd, Cin, ks)
-            c0 = 0
-            for i, t in enumerate(xs):
-                if ctx.needs_input_grad[5 + i]:
-                    dxs[i] = dx[:, c0:c0 + t.shape[1]]
-                c0 += t.shape[1]
-        if want_w:
-            dw, db = wgrad()
-        if wait is not None:
-            wait()
-        return (dw, db, None, None, None) + tuple(dxs)
+def _cat_fold_ok(xs):
+    """May the concatenation of `xs` be folded into the K loop?  The envelope of the multi-source FORWARD kernel: 2 or 3 tensors, every
+    one but the last ending on a 16-channel boundary, at least 16 channels in all, the split-bf16 arithmetic; the environment
+    switch read here materialises every concatenation instead."""
+    C0 = xs[0].shape[1]
+    return os.environ.get('PNSFM_CAT_FOLD', '1') != '0' and len(xs) in (2, 3) and C0 % 16 == 0 and \
+        (len(xs) == 2 or (C0 + xs[1].shape[1]) % 16 == 0) and get_conv_math() == 'bx3' and sum(t.shape[1] for t in xs) >= 16
 
 
 def _cat_wgrad_ok(xs, weight):
@@ -746,17 +737,13 @@ def _cat_wgrad_ok(xs, weight):
 
 def conv2d_cat(xs, weight, bias, cache):
     """xs: tuple of 2 or 3 NCHW tensors.  Falls back to torch.cat + conv2d when the shape is outside the multi-source FORWARD
-    kernel's envelope (first / second tensor not ending on a 16-channel boundary, < 16 channels, f32 arithmetic mode); a shape
-    the forward takes but the multi-source weight-gradient kernels do not concatenates for that one kernel only."""
+    kernel's envelope (_cat_fold_ok); a shape the forward takes but the multi-source weight-gradient kernels do not concatenates for
+    that one kernel only."""
     if xs[0].dtype == torch.float16:
         return _conv2d_h16(tuple(xs), weight, bias, cache)
-    import os
-    C0 = xs[0].shape[1]
-    ok = os.environ.get('PNSFM_CAT_FOLD', '1') != '0' and len(xs) in (2, 3) and C0 % 16 == 0 and (len(xs) == 2 or (C0 + xs[1].shape[1]) % 16 == 0) and get_conv_math() == 'bx3' \
-        and sum(t.shape[1] for t in xs) >= 16
-    if not ok:
+    if not _cat_fold_ok(xs):
         return conv2d(torch.cat(xs, 1), weight, bias, cache)
-    return Conv2dCatFn.apply(weight, bias, cache, torch.is_grad_enabled(), _cat_wgrad_ok(xs, weight), *xs)
+    return Conv2dFn.apply(weight, bias, cache, torch.is_grad_enabled(), _cat_wgrad_ok(xs, weight), False, *xs)
 
 
 class ConvGnActFn(Function):
@@ -765,7 +752,8 @@ class ConvGnActFn(Function):
     the autograd / Python overhead of the block (profiles/r05_host_profile.txt: ~35 us per Function.apply, the host needs 16-18 ms
     to enqueue a 24 ms step).
     Round 6: both bodies are ONE call into the block sequencer (csrc/seq/pnsfm_seq.cpp) when it is loaded.  (The conv epilogue that
-    also left the GroupNorm statistics behind -- round 5, measured neutral twice, profiles/r05_ab_conv_gn_stats.txt -- is gone.)"""
+    also left the GroupNorm statistics behind -- round 5, measured neutral twice, profiles/r05_ab_conv_gn_stats.txt -- is gone.)
+    From the GroupNorm backward on, the backward is Conv2dFn's."""
 
     @staticmethod
     def forward(ctx, weight, bias, gamma, beta, cache, recording, cat_wgrad, G, eps, act, tap, *xs):
@@ -803,62 +791,16 @@ class ConvGnActFn(Function):
             return (None,) * 11 + (g_tap,)
         wp_bwd, y, gamma, beta, ms, *xs = ctx.saved_tensors
         Cin, Cout, ks, has_bias, G, act = ctx.meta
-        dxs = [None] * len(xs)
-        dw = db = None
-        detached = _WgradStream.side_ok(*ctx.params)
-        sw, sb = _slots_for(ctx.params[0], ctx.params[1], detached and ctx.needs_input_grad[0])
-        want_w = ctx.needs_input_grad[0] or (has_bias and ctx.needs_input_grad[1])
-        sq = _seq.get()
-        if sq is not None and (not want_w or len(xs) == 1 or (ctx.cat_wgrad and get_conv_math() == 'bx3')) and \
-                (g_tap is None or get_conv_math() == 'bx3'):
+        seq, need_dx, want_w, detached, sw, sb = _conv_bwd_plan(ctx, dout, xs, g_tap, 11)
+        if seq is not None:
             # ONE call: GroupNorm backward -> fork -> weight gradient (side stream) -> backward-data (+ tap) [-> join]
-            need_dx = any(ctx.needs_input_grad[11:])
-            main_raw, side_raw, side = _seq_streams(dout, want_w)
-            dx, dw, db, dgamma, dbeta = sq.conv_gn_act_backward(dout, y, gamma, beta, ms, list(xs), wp_bwd, Cin, Cout, ks, G, act, has_bias, need_dx,
-                                                                bool(want_w), sw, sb, g_tap if len(xs) == 1 else None, main_raw, side_raw,
-                                                                bool(detached), side)
-            if side is not None and detached:
-                _WgradStream._pending.add(dout.device)
-            if need_dx:
-                if len(xs) == 1:
-                    dxs[0] = dx
-                else:
-                    c0 = 0
-                    for i, t in enumerate(xs):
-                        if ctx.needs_input_grad[11 + i]:
-                            dxs[i] = dx[:, c0:c0 + t.shape[1]]
-                        c0 += t.shape[1]
-            return (dw, db, dgamma, dbeta, None, None, None, None, None, None, None) + tuple(dxs)
-        dy, dgamma, dbeta = ops.groupnorm_act_backward(dout.contiguous(), y, None, gamma.detach(), beta.detach(), ms[0], ms[1], G, act)
-
-        def wgrad():
-            if len(xs) == 1:
-                return ops.conv2d_backward_weight(xs[0], dy, ks, want_bias=has_bias, dw_out=sw, db_out=sb)
-            if ctx.cat_wgrad and get_conv_math() == 'bx3':
-                return ops.conv2d_backward_weight_cat(xs, dy, ks, want_bias=has_bias, dw_out=sw, db_out=sb)
-            return ops.conv2d_backward_weight(torch.cat(xs, 1), dy, ks, want_bias=has_bias, dw_out=sw, db_out=sb)
-
-        wait = None
-        if want_w and _WgradStream.use_for(dy):
-            # (pure: the closure launches kernels only -- the concatenating fallback calls torch.cat and takes the stream-context path)
-            r = _WgradStream.run(wgrad, dy, *xs, detached=detached, pure=(len(xs) == 1 or (ctx.cat_wgrad and get_conv_math() == 'bx3')))
-            (dw, db), wait = (r, None) if detached else r
-            want_w = False
-        if any(ctx.needs_input_grad[11:]):
-            dx = _dgrad_tap(dy, wp_bwd, Cin, ks, g_tap if len(xs) == 1 else None)
-            if len(xs) == 1:
-                dxs[0] = dx
-            else:
-                c0 = 0
-                for i, t in enumerate(xs):
-                    if ctx.needs_input_grad[11 + i]:
-                        dxs[i] = dx[:, c0:c0 + t.shape[1]]
-                    c0 += t.shape[1]
-        if want_w:
-            dw, db = wgrad()
-        if wait is not None:
-            wait()
-        return (dw, db, dgamma, dbeta, None, None, None, None, None, None, None) + tuple(dxs)
+            sq, main_raw, side_raw, side = seq
+            dx, dw, db, dgamma, dbeta = sq.conv_gn_act_backward(dout, y, gamma, beta, ms, xs, wp_bwd, Cin, Cout, ks, G, act, has_bias, need_dx,
+                                                                want_w, sw, sb, g_tap, main_raw, side_raw, detached, side)
+        else:
+            dy, dgamma, dbeta = ops.groupnorm_act_backward(dout.contiguous(), y, None, gamma.detach(), beta.detach(), ms[0], ms[1], G, act)
+            dx, dw, db = _conv_bwd_python(ctx, dy, xs, wp_bwd, g_tap, need_dx, want_w, detached, sw, sb)
+        return (dw, db, dgamma, dbeta, None, None, None, None, None, None, None) + _split_dx(dx, xs, ctx.needs_input_grad[11:])
 
 
 _CONV_GN_FUSE = os.environ.get('PNSFM_CONV_GN_FUSE', '1') != '0'
@@ -874,12 +816,8 @@ def conv2d_gn_act(x, weight, bias, gamma, beta, cache, G=16, eps=1e-5, act=ops.A
     if xs[0].dtype == torch.float16:
         return _groupnorm_act_h16(_conv2d_h16(xs, weight, bias, cache), gamma, beta, G, eps, act)
     _h16_input(xs[0], weight)
-    if len(xs) > 1:
-        C0 = xs[0].shape[1]
-        fold = os.environ.get('PNSFM_CAT_FOLD', '1') != '0' and len(xs) in (2, 3) and C0 % 16 == 0 and \
-            (len(xs) == 2 or (C0 + xs[1].shape[1]) % 16 == 0) and get_conv_math() == 'bx3' and sum(t.shape[1] for t in xs) >= 16
-        if not fold:
-            xs = (torch.cat(xs, 1),)
+    if len(xs) > 1 and not _cat_fold_ok(xs):
+        xs = (torch.cat(xs, 1),)
     if not _CONV_GN_FUSE:
         y = conv2d(xs[0], weight, bias, cache) if len(xs) == 1 else conv2d_cat(xs, weight, bias, cache)
         return groupnorm_act(y, gamma, beta, G, eps, act)
@@ -919,24 +857,17 @@ class Conv2dStride2Fn(Function):
         x, wp_bwd = ctx.saved_tensors
         Cin, Cout, ks, has_bias = ctx.meta
         dy = dy.contiguous()
-        dx = dw = db = None
         want_w = ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2])
         detached = _WgradStream.side_ok(*ctx.params)
-        wait = None
-        if want_w and _WgradStream.use_for(dy):
-            r = _WgradStream.run(lambda: ops.conv2d_backward_weight_strided(x, dy, ks, 2, want_bias=has_bias), x, dy,
-                                 detached=detached)
-            (dw, db), wait = (r, None) if detached else r
-            want_w = False
-        if ctx.needs_input_grad[0]:
+
+        def dgrad():
             B, _, H, W = x.shape
             up = dy.new_zeros((B, Cout, H, W))
             up[:, :, ::2, ::2] = dy                      # dy[y][x] sits at (2y, 2x) of the input grid
-            dx = ops.conv2d_backward_data(up, wp_bwd, Cin, ks)
-        if want_w:
-            dw, db = ops.conv2d_backward_weight_strided(x, dy, ks, 2, want_bias=has_bias)
-        if wait is not None:
-            wait()
+            return ops.conv2d_backward_data(up, wp_bwd, Cin, ks)
+
+        dx, dw, db = _WgradStream.run_beside(dy, want_w, detached, lambda: ops.conv2d_backward_weight_strided(x, dy, ks, 2, want_bias=has_bias),
+                                             dgrad if ctx.needs_input_grad[0] else None, (x, dy))
         return dx, dw, db, None, None
 
 
@@ -1033,20 +964,11 @@ class Conv3d1to8Fn(Function):
     def backward(ctx, dout):
         p, w3 = ctx.saved_tensors
         dout = dout.contiguous()
-        dp = dw3 = db3 = None
         want_w = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
         detached = _WgradStream.side_ok(*ctx.params)
-        wait = None
-        if want_w and _WgradStream.use_for(dout):
-            r = _WgradStream.run(lambda: ops.conv3d_backward_weight(p, dout), p, dout, detached=detached)
-            (dw3, db3), wait = (r, None) if detached else r
-            want_w = False
-        if ctx.needs_input_grad[0]:
-            dp = ops.conv3d_backward_data(dout, w3.detach().contiguous())
-        if want_w:
-            dw3, db3 = ops.conv3d_backward_weight(p, dout)
-        if wait is not None:
-            wait()
+        dp, dw3, db3 = _WgradStream.run_beside(dout, want_w, detached, lambda: ops.conv3d_backward_weight(p, dout),
+                                               (lambda: ops.conv3d_backward_data(dout, w3.detach().contiguous())) if ctx.needs_input_grad[0] else None,
+                                               (p, dout))
         return dp, dw3, db3, None
 
 

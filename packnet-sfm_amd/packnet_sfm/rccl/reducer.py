@@ -22,6 +22,7 @@ MI355X-first choices (not a translation of horovod's tensor-fusion queue):
     (post-accumulate-grad hooks), while the compute stream keeps running backward; `synchronize()` joins the side
     stream before the optimizer reads the gradients and applies the 1/world_size averaging.
 """
+import contextlib
 import os
 import time as _time
 
@@ -201,7 +202,7 @@ class GradBucketReducer:
                     comm.wait_stream(st)
         else:
             HF.join_wgrad_stream(bucket.flat.device)
-        with (torch.cuda.stream(comm) if comm is not None else HF._nullctx()):
+        with (torch.cuda.stream(comm) if comm is not None else contextlib.nullcontext()):
             src, dst = [], []
             for p, v in zip(bucket.params, bucket.views):
                 g = p.grad

@@ -1255,3 +1255,97 @@ def test_block_sequencer_equals_python_bodies(emulated_kernels):
     assert len(res[False]) == len(res[True])
     for i, (u, v) in enumerate(zip(res[False], res[True])):
         assert torch.equal(u, v), 'tensor %d differs between the Python bodies and the sequencer (max |d| %.3e)' % (i, float((u - v).abs().max()))
+
+
+# Source configurations of the stride-1 conv nodes (hip.functional.Conv2dFn / ConvGnActFn), B = 1, 6 x 8 pixels, Cout = 32, 3 x 3:
+# (channels per source, gradient tap on the input).  With 32 output channels the multi-source weight-gradient kernels take (32, 16) and
+# (32, 32, 16) and refuse (16, 16), whose forward still folds (the weight gradient concatenates); (8, 24) is outside the forward's
+# envelope as well (torch.cat in front of a one-source node).
+CONV_NODE_SOURCES = [((32,), False), ((32,), True), ((32, 16), False), ((16, 16), False), ((32, 32, 16), False), ((8, 24), False)]
+
+
+def _conv_node_data(Cs, seed):
+    g = torch.Generator().manual_seed(seed)
+    xs = [torch.randn(1, c, 6, 8, generator=g) for c in Cs]
+    params = [torch.randn(32, sum(Cs), 3, 3, generator=g) * 0.1, torch.randn(32, generator=g),                  # weight, bias
+              torch.rand(32, generator=g) + 0.5, torch.randn(32, generator=g) * 0.1]                            # gamma, beta
+    return xs, params, torch.randn(1, 32, 6, 8, generator=g)
+
+
+def _conv_node_reference(data, tap, gn):
+    """[output, gradient of every source, dw, db(, dgamma, dbeta)] of torch's conv2d on the concatenation (+ GroupNorm + ELU)."""
+    import torch.nn.functional as F
+    xs, params, dy = data
+    xr = [t.clone().requires_grad_(True) for t in xs]
+    pr = [p.clone().requires_grad_(True) for p in params[:4 if gn else 2]]
+    y = F.conv2d(torch.cat(xr, 1), pr[0], pr[1], padding=1)
+    if gn:
+        y = F.elu(F.group_norm(y, 16, pr[2], pr[3], 1e-5))
+    loss = (y * dy).sum()
+    if tap:
+        loss = loss + (xr[0] * xr[0]).sum() * 0.1          # the input's second consumer
+    loss.backward()
+    return [y.detach()] + [t.grad for t in xr] + [p.grad for p in pr]
+
+
+def _conv_node_run(device, data, tap, gn, module_twice=False):
+    """The same through hip.functional: conv2d / conv2d_cat / conv2d_tap, or conv2d_gn_act / conv2d_gn_act_tap with gn.  module_twice:
+    the node is applied a second time with the same parameters (to the first source doubled): their gradients are accumulated by
+    compute-stream kernels, so neither node may leave its weight gradient in flight."""
+    from packnet_sfm.hip import functional as HF
+    xs, params, dy = data
+    xh = [t.clone().to(device).requires_grad_(True) for t in xs]
+    ph = [p.clone().to(device).requires_grad_(True) for p in params[:4 if gn else 2]]
+    cache = HF.PackedConvWeight()
+
+    def node(src):
+        if tap:
+            return HF.conv2d_gn_act_tap(src[0], *ph, cache) if gn else HF.conv2d_tap(src[0], *ph, cache)
+        x = src[0] if len(src) == 1 else tuple(src)
+        if gn:
+            return HF.conv2d_gn_act(x, *ph, cache)
+        return HF.conv2d(x, *ph, cache) if len(src) == 1 else HF.conv2d_cat(x, *ph, cache)
+    dy = dy.to(device)
+    if tap:
+        y, x_tap = node(xh)
+        assert x_tap is not xh[0], 'the tap was not granted'
+        loss = (y * dy).sum() + (x_tap * x_tap).sum() * 0.1
+    else:
+        y = node(xh)
+        loss = (y * dy).sum()
+    if module_twice:
+        y2 = node([2.0 * xh[0]] + xh[1:])
+        loss = loss + ((y2[0] if tap else y2) * dy).sum()
+    loss.backward()
+    return [y.detach()] + [t.grad for t in xh] + [p.grad for p in ph]
+
+
+@pytest.mark.parametrize('gn', [False, True])
+@pytest.mark.parametrize('Cs,tap', CONV_NODE_SOURCES)
+def test_conv_nodes_sequencer_and_python_bodies(emulated_kernels, Cs, tap, gn):
+    """Conv2dFn (1..3 sources, optional tap) and ConvGnActFn over every source configuration of CONV_NODE_SOURCES: the block sequencer
+    and the Python bodies give the same bits (output and every gradient), and both agree with torch on the concatenated tensor at the
+    tolerances of test_conv2d_cat_multi_source.  (The conv bias in front of a GroupNorm has a mathematically zero gradient: against
+    torch it is measured on the scale of the weight gradient.)"""
+    from packnet_sfm.hip import _seq, ops
+    assert ops.conv2d_cat_wgrad_supported([32, 16], 32, 6, 8, 3, B=1) and ops.conv2d_cat_wgrad_supported([32, 32, 16], 32, 6, 8, 3, B=1)
+    assert not ops.conv2d_cat_wgrad_supported([16, 16], 32, 6, 8, 3, B=1)
+    data = _conv_node_data(Cs, 100 + 7 * sum(Cs) + Cs[0])
+    ref = _conv_node_reference(data, tap, gn)
+    assert _seq.get() is not None
+    res = {}
+    try:
+        for on in (False, True):
+            _seq.set_enabled(on)
+            res[on] = _conv_node_run('cpu', data, tap, gn)
+    finally:
+        _seq.set_enabled(True)
+    names = ['out'] + ['d input %d' % i for i in range(len(Cs))] + ['dw', 'db', 'dgamma', 'dbeta'][:len(ref) - 1 - len(Cs)]
+    assert len(res[False]) == len(res[True]) == len(ref)
+    dw_max = float(ref[1 + len(Cs)].abs().max())
+    for n, u, v, r in zip(names, res[False], res[True], ref):
+        assert torch.equal(u, v), '%s differs between the Python bodies and the sequencer (max |d| %.3e)' % (n, float((u - v).abs().max()))
+        tol = 1e-5 if n == 'out' or n.startswith('d input') else 2e-5
+        e = P.err(v, r, floor=dw_max if (gn and n == 'db') else 0.0)
+        print('%s %s tap=%s gn=%s: %.3e' % (n, Cs, tap, gn, e))
+        assert e <= tol, '%s vs torch: relative error %.3e > %.1e' % (n, e, tol)
