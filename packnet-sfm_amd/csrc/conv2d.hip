@@ -1119,15 +1119,6 @@ static inline int with_pp_taps(int G, F&& f) {
   return f(std::integral_constant<int, 1>{});
 }
 
-// more than 64 KB of dynamic LDS needs an explicit opt-in per kernel and device, once (ensure_lds_limit, api.hip: nothing to do on
-// the emulator); 0 on success
-template <void (*Kernel)(ConvArgs)>
-static inline int allow_wide_lds(size_t smem_bytes, const char* what) {
-  static unsigned long long done = 0;     // one bit per device
-  if (smem_bytes <= 64 * 1024) return 0;
-  return ensure_lds_limit(reinterpret_cast<const void*>(Kernel), &done, (int)kMaxSmemPipe, what);
-}
-
 // extras of a launch's epilogue: the addend of ConvArgs (round 5; null: none).  (The GroupNorm statistics that rode along here in round 5
 // -- pnsfm_conv2d_forward_gn -- were measured neutral twice and removed in round 6.)
 struct ConvGnOut {
@@ -1252,6 +1243,23 @@ static float time_on_stream(hipStream_t stream, int reps, F fn) {
     if (total >= 0.4f || done >= 12) break;
   }
   return total / done;
+}
+
+// the pixel splits the tuner tries for a kernel with `tiles` pixel tiles and `base_blocks` workgroups per split: wanted splits 1, 2, 3,
+// 4, then x 1.5, each rounded to whole tiles per split and taken once, from the first that gives the chip `floor_blocks` workgroups (or
+// is the last one) up to `ceil_blocks` (an unsplit launch is always admitted).  fn(split) returns false to end the search.
+template <class F>
+static void for_split_candidates(int tiles, int base_blocks, long floor_blocks, long ceil_blocks, F&& fn) {
+  int prev = -1;
+  for (int want = 1; want <= tiles; want = want < 4 ? want + 1 : (want * 3 + 1) / 2) {
+    const int tps = ceil_div(tiles, want);
+    const int split = ceil_div(tiles, tps);
+    if (split == prev) continue;
+    prev = split;
+    if ((long)base_blocks * split < floor_blocks && split < tiles) continue;      // cannot fill the chip
+    if ((long)base_blocks * split > ceil_blocks && split > 1) break;
+    if (!fn(split)) break;
+  }
 }
 #endif
 
@@ -2240,7 +2248,7 @@ static int wgrad_run(const WgradPlan& p) {
 
 #ifndef PNSFM_EMU
 // (c) the autotuner: times the pixel splits (and tile parameters) of every kernel the shape supports and returns the fastest
-// (g_tune_mu held).  The four searches are deliberately separate: their progressions, dedupe rules and thresholds differ.
+// (g_tune_mu held).  The generic kernel's search has its own progression and dedupe rule; the other three share for_split_candidates.
 static WgradDecision wgrad_tune(const WgradPlan& p, const std::array<int, 7>& key) {
   const int B = p.B, Cin = p.Cin, Cout = p.Cout, ks = p.ks, H0 = p.H0, W0 = p.W0, H3 = p.H3, W3 = p.W3;
   const ConvSrc* ms = p.ms;
@@ -2265,56 +2273,33 @@ static WgradDecision wgrad_tune(const WgradPlan& p, const std::array<int, 7>& ke
     if ((base * split > 40L * 256 || split > p.max_split_f32) && split > 1) break;
     time_candidate({0, split});
   }
-  if (p.v2_ok && !ms) {     // tap-major kernel: pixel splits around one workgroup per CU
-    const int base2 = wgrad2_base_blocks(Cin, Cout, ks), tiles2 = wgrad2_total_tiles(B, H0, W0);
-    int prev = -1;
-    for (int want = 1; want <= tiles2; want = want < 4 ? want + 1 : (want * 3 + 1) / 2) {
-      const int tps = ceil_div(tiles2, want);
-      const int split = ceil_div(tiles2, tps);
-      if (split == prev) continue;
-      prev = split;
-      if ((long)base2 * split < 160 && split < tiles2) continue;      // cannot fill the chip
-      if ((long)base2 * split > 6L * 256 && split > 1) break;
+  if (p.v2_ok && !ms)       // tap-major kernel: pixel splits around one workgroup per CU
+    for_split_candidates(wgrad2_total_tiles(B, H0, W0), wgrad2_base_blocks(Cin, Cout, ks), 160, 6L * 256, [&](int split) {
       time_candidate({1, split});
-    }
-  }
+      return true;
+    });
   if (p.v3_ok) {     // split-bf16 kernel: NT in {1, 2} x co tiles per workgroup x pixel splits around two workgroups per CU
     const int tiles3 = wgrad3_total_tiles(B, H3, W3);
     const int wm_most = wgrad3_WM(Cout, 0);
     for (int NT = 1; NT <= (wgrad3_nt2_ok(Cin, ks) ? 2 : 1); ++NT)
-      for (int WMv = wm_most; WMv >= 1; WMv >>= 1) {
-        const int base3 = wgrad3_base_blocks(Cin, Cout, ks, NT, WMv);
-        int prev = -1;
-        for (int want = 1; want <= tiles3; want = want < 4 ? want + 1 : (want * 3 + 1) / 2) {
-          const int tps = ceil_div(tiles3, want);
-          const int split = ceil_div(tiles3, tps);
-          if (split == prev) continue;
-          prev = split;
-          if ((long)base3 * split < 200 && split < tiles3) continue;      // cannot fill the chip
-          if ((long)base3 * split > 16L * 256 && split > 1) break;
-          if (WMv != wm_most && split > 2) break;     // fewer co tiles per workgroup only pays when it replaces the pixel split
-          if (ms && NT == 2 && !conv_src_aligned(*ms, Cin, 64)) continue;
+      for (int WMv = wm_most; WMv >= 1; WMv >>= 1)
+        for_split_candidates(tiles3, wgrad3_base_blocks(Cin, Cout, ks, NT, WMv), 200, 16L * 256, [&](int split) {
+          if (WMv != wm_most && split > 2) return false;     // fewer co tiles per workgroup only pays when it replaces the pixel split
+          if (ms && NT == 2 && !conv_src_aligned(*ms, Cin, 64)) return true;
           for (int occ = 0; occ < ((ks == 3 && NT == 1 && W3 % 8 == 0) ? 2 : 1); ++occ)    // occ 1: the three-workgroups-per-CU build
             time_candidate({2, split, NT, WMv | (occ ? 8 : 0)});
-        }
-      }
+          return true;
+        });
   }
   if (p.v4_ok) {     // nine-taps kernel: ci tiles per workgroup x tile width x pixel splits around two workgroups per CU
     for (int WCI = 1; WCI <= 2; ++WCI)
       for (int tgi = 0; tgi < (W0 > 24 ? 2 : 1); ++tgi) {
         const int TG = W0 > 24 ? 4 + tgi : 3, TR = TG == 3 ? wgrad4_TR(H0, 0) : 4;
         if (W0 > 24 && round_up(W0, 8 * TG) > round_up(W0, 8 * (9 - TG)) + 8) continue;      // clearly the more wasteful width
-        const int tiles4 = wgrad4_total_tiles(B, H0, W0, TG, TR), base4 = wgrad4_base_blocks(Cin, Cout, WCI);
-        int prev = -1;
-        for (int want = 1; want <= tiles4; want = want < 4 ? want + 1 : (want * 3 + 1) / 2) {
-          const int tps = ceil_div(tiles4, want);
-          const int split = ceil_div(tiles4, tps);
-          if (split == prev) continue;
-          prev = split;
-          if ((long)base4 * split < 200 && split < tiles4) continue;      // cannot fill the chip
-          if ((long)base4 * split > 16L * 256 && split > 1) break;
+        for_split_candidates(wgrad4_total_tiles(B, H0, W0, TG, TR), wgrad4_base_blocks(Cin, Cout, WCI), 200, 16L * 256, [&](int split) {
           time_candidate({3, split, 1, 0, WCI, TG, TR});
-        }
+          return true;
+        });
       }
   }
   return best;

@@ -33,22 +33,7 @@
 #define PNSFM_BX3_SLAB 3072      // bytes per (32-row m-block, 16-channel chunk, tap)
 #define PNSFM_BX3_MAXIT 4        // patch items (pixel, 8-channel half) a thread prefetches in registers (PS <= 512 pixels); larger patches are staged in rounds
 
-// 8 consecutive-k fp32 values -> the three 16-byte operand pieces.  Exact 3-way split with round-to-nearest pieces:
-//   h = bf16(v), m = bf16(v - h), l = v - h - m   (v - h and v - h - m are exact in fp32; l has <= 8 significant bits, so
-//   the last conversion is exact too: v == h + m + l).  |m| <= 2^-9 |v|, |l| <= 2^-18 |v|, signs mixed.
-// 11 VALU instructions per PAIR of values: 3 v_cvt_pk_bf16_f32, 4 unpacks (shift / mask), 4 subtractions.
-__device__ __forceinline__ void bx3_split8(const float (&v)[8], pnsfm_u32x4& H, pnsfm_u32x4& M, pnsfm_u32x4& L) {
-#pragma unroll
-  for (int i = 0; i < 8; i += 2) {
-    const unsigned h = pnsfm_cvt_pk_bf16(v[i], v[i + 1]);
-    const float r0 = v[i] - pnsfm_u2f(h << 16), r1 = v[i + 1] - pnsfm_u2f(h & 0xffff0000u);
-    const unsigned m = pnsfm_cvt_pk_bf16(r0, r1);
-    const float s0 = r0 - pnsfm_u2f(m << 16), s1 = r1 - pnsfm_u2f(m & 0xffff0000u);
-    H[i >> 1] = h;
-    M[i >> 1] = m;
-    L[i >> 1] = pnsfm_cvt_pk_bf16(s0, s1);
-  }
-}
+// (bx3_split8 -- 8 consecutive-k fp32 values -> the three 16-byte operand pieces -- lives in pnsfm_common.h: the weight-gradient files use it too)
 
 // OCC = workgroups the register budget is sized for (__launch_bounds__): 2 (<= 256 VGPRs) or 3 (<= 168: one fragment set instead of
 // the tap-ahead pair, three patch items in flight) -- three waves per SIMD cover each other's staging / DMA-issue / barrier phases

@@ -272,12 +272,7 @@ template <int KS, int FC>
 static int launch_wgrad2(Wgrad2Args a, dim3 grid, hipStream_t s) {
   using Gm = Wgrad2Geom<KS, FC>;
   const size_t smem = 2 * (size_t)Gm::BUF * sizeof(float);
-#ifndef PNSFM_EMU
-  static unsigned long long raised = 0;      // one bit per device
-  if (smem > 64 * 1024 && ensure_lds_limit(reinterpret_cast<const void*>(&conv2d_wgrad2_kernel<KS, FC>), &raised, 160 * 1024,
-                                           "conv2d_backward_weight"))
-    return -1;
-#endif
+  if (allow_wide_lds<&conv2d_wgrad2_kernel<KS, FC>>(smem, "conv2d_backward_weight")) return -1;
   PNSFM_LAUNCH((conv2d_wgrad2_kernel<KS, FC>), grid, dim3(256), smem, s, a);
   return check_launch("conv2d_backward_weight (tap-major)");
 }

@@ -1,9 +1,9 @@
 // conv2d_wgrad3.hip -- weight gradient of a stride-1 KxK convolution on the bf16 matrix pipe (split-bf16 arithmetic).
 //
 // Replaces the autograd weight gradient of nn.Conv2d in the reference's Conv2D / ResidualConv / Pack / Unpack blocks
-//   (/root/reference/packnet_sfm/networks/layers/packnet/layers01.py:28-36, 57-60, 235-246, 274-281):
+//   (packnet_sfm/networks/layers/packnet/layers01.py:28-36, 57-60, 235-246, 274-281):
 //   dW[co][ci][ky][kx] = sum_{b, y, x} dY[b][co][y][x] * X[b][ci][y + ky - P][x + kx - P]
-// with the arithmetic of conv2d_bx3.h: every fp32 operand is split EXACTLY into three bf16 pieces (h, m, l) and the product
+// with the arithmetic of conv2d_bx3.h (bx3_split8, pnsfm_common.h): every fp32 operand is split EXACTLY into three bf16 pieces (h, m, l) and the product
 // is rebuilt from the 6 piece products hh, hm, mh, hl, lh, mm with fp32 accumulation (v_mfma_f32_32x32x16_bf16): fp32-class
 // error at 16/6 the MAC rate of v_mfma_f32_32x32x2_f32.
 //
@@ -25,52 +25,15 @@
 // Widths that are a multiple of 4 but not of 8 (20, 4: the upper half of an 8-pixel group may lie past the row end) run a
 // variant that range-checks the two halves separately; tiles are 4 rows x 32 columns, or 4 x 16 where that wastes fewer columns (W = 40, 80, 20).  k = 3, 5, 7.
 // Roofline: MFMA-bound: 2*Cout*Cin*K*K*B*H*W algorithmic flop against 2500/6 TFLOP/s (bf16 dense peak / 6 products).
-#include "pnsfm_common.h"
+// The argument block and the host side of a launch (checks, split clamp, scratch, reduction) are shared with conv2d_wgrad4.hip:
+// conv2d_wgrad_bx3.h.
+#include "conv2d_wgrad_bx3.h"
 #include "../../include/pnsfm.h"
 
 namespace pnsfm {
 
-struct Wgrad3Args {
-  const float* x1;   // multi-source input (ConvSrc, pnsfm_common.h): channels [C0, C01) live in x1, [C01, Cin) in x2
-  const float* x2;
-  int C0, C01;       // C0 = C01 = Cin for a single source
-  const float* x;    // [B][Cin][H][W]  (multi-source: [B][C0][H][W])
-  const float* dy;   // [B][Cout][H][W]
-  float* dw;         // [Cout][Cin][KS][KS]   written directly when the launch has ONE pixel split ...
-  float* dbias;      // [Cout] or null
-  float* ws;         // ... else partial sums [split][KS(ky)][COP][KS(kx)][CIP] (+ [split][COP] bias partials at ws_bias),
-  float* ws_bias;    //     reduced by wgrad3_reduce_kernel: no atomics, a fixed summation order
-  int COP, CIP;      // padded channel extents of the workspace (whole workgroup tiles)
-  int B, Cin, Cout, H, W;
-  int tiles_x, tiles_per_img, total_tiles, tiles_per_split;
-  int ci_tiles;      // logical grid x = ci_tiles * KS
-  int gx, gy, bmap;  // 1-D launch: ci tiles * KS, co groups, block order (pnsfm_common.h: block_map_mode)
-};
-#ifdef PNSFM_WG_ABLATE          // compile-time what-if mask (see conv2d_wgrad4.hip)
-#define PNSFM_WG_ABL(a) (PNSFM_WG_ABLATE)
-#else
-#define PNSFM_WG_ABL(a) 0
-#endif
-
-#ifdef PNSFM_EMU
-static inline unsigned w3_alignbit16(unsigned hi, unsigned lo) { return (lo >> 16) | (hi << 16); }
-#else
-__device__ __forceinline__ unsigned w3_alignbit16(unsigned hi, unsigned lo) { return __builtin_amdgcn_alignbit(hi, lo, 16); }
-#endif
-
-// 8 consecutive fp32 values -> three 16-byte bf16 pieces (see conv2d_bx3.h: exact, round-to-nearest pieces)
-__device__ __forceinline__ void w3_split8(const float (&v)[8], pnsfm_u32x4& H, pnsfm_u32x4& M, pnsfm_u32x4& L) {
-#pragma unroll
-  for (int i = 0; i < 8; i += 2) {
-    const unsigned h = pnsfm_cvt_pk_bf16(v[i], v[i + 1]);
-    const float r0 = v[i] - pnsfm_u2f(h << 16), r1 = v[i + 1] - pnsfm_u2f(h & 0xffff0000u);
-    const unsigned m = pnsfm_cvt_pk_bf16(r0, r1);
-    const float s0 = r0 - pnsfm_u2f(m << 16), s1 = r1 - pnsfm_u2f(m & 0xffff0000u);
-    H[i >> 1] = h;
-    M[i >> 1] = m;
-    L[i >> 1] = pnsfm_cvt_pk_bf16(s0, s1);
-  }
-}
+struct Wgrad3Launch { int ci_tiles, gx, gy, bmap; };      // logical grid x = gx = ci_tiles * KS: (ci tile, kernel row)
+struct Wgrad3Args : WgradBx3Args<Wgrad3Launch> {};      // (a type of its own: the kernels' symbols keep their names)
 
 // OCC = 3 (3x3, one ci tile per wave only): register budget of three workgroups per CU (<= 168 VGPRs: shorter dY ring, one patch tile in
 // flight) -- the third wave per SIMD covers the staging / barrier phases the other two leave the matrix pipe idle in.
@@ -113,8 +76,8 @@ __global__ void __launch_bounds__(256, OCC) conv2d_wgrad3_kernel(Wgrad3Args a) {
   const int H = a.H, W = a.W, HW = H * W;
   // logical block ((ci tile, kernel row), co group, pixel split): first index fastest -- the workgroups of one pixel split read the
   // same dY and X -- and a contiguous range of that order per XCD (pnsfm_common.h)
-  const unsigned Lb = a.bmap == 2 ? pnsfm_xcd_logical_block(blockIdx.x, gridDim.x) : blockIdx.x;
-  const int bx = (int)(Lb % (unsigned)a.gx), by = (int)((Lb / (unsigned)a.gx) % (unsigned)a.gy), bz = (int)(Lb / (unsigned)(a.gx * a.gy));
+  const unsigned Lb = a.g.bmap == 2 ? pnsfm_xcd_logical_block(blockIdx.x, gridDim.x) : blockIdx.x;
+  const int bx = (int)(Lb % (unsigned)a.g.gx), by = (int)((Lb / (unsigned)a.g.gx) % (unsigned)a.g.gy), bz = (int)(Lb / (unsigned)(a.g.gx * a.g.gy));
   const int cit = bx / KS, ky = bx - cit * KS;
   const int ci0 = cit * NCI;
   const int co0 = (by * WM + wm) * 32;
@@ -194,7 +157,7 @@ __global__ void __launch_bounds__(256, OCC) conv2d_wgrad3_kernel(Wgrad3Args a) {
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
       pnsfm_u32x4 Hh, Mm, Ll;
-      w3_split8(rw[it], Hh, Mm, Ll);
+      bx3_split8(rw[it], Hh, Mm, Ll);
       unsigned char* d = smem + it_lds[it];
       *reinterpret_cast<pnsfm_u32x4*>(d) = Hh;
       *reinterpret_cast<pnsfm_u32x4*>(d + PIECE * 2) = Mm;
@@ -255,7 +218,7 @@ __global__ void __launch_bounds__(256, OCC) conv2d_wgrad3_kernel(Wgrad3Args a) {
               if ((sh & 1) == 0) Bv[d] = Wd[4 + d + sh / 2];
               else {
                 const int lo = 4 + d + (sh - 1) / 2;     // (sh - 1) is even: exact division also for negative shifts
-                Bv[d] = (abl & 4) ? (Wd[lo + 1] ^ Wd[lo]) : w3_alignbit16(Wd[lo + 1], Wd[lo]);
+                Bv[d] = (abl & 4) ? (Wd[lo + 1] ^ Wd[lo]) : pnsfm_alignbit16(Wd[lo + 1], Wd[lo]);
               }
             }
             if (abl & 16) { acc[nt][kx][0] += __builtin_bit_cast(float, Bv[0] ^ Bv[1] ^ Bv[2] ^ Bv[3] ^ A[0][0] ^ A[1][1] ^ A[2][2]); continue; }
@@ -295,7 +258,7 @@ __global__ void __launch_bounds__(256, OCC) conv2d_wgrad3_kernel(Wgrad3Args a) {
               if ((sh & 1) == 0) Bv[s][d] = Wd[s][4 + d + sh / 2];
               else {
                 const int lo = 4 + d + (sh - 1) / 2;     // (sh - 1) is even: exact division also for negative shifts
-                Bv[s][d] = (abl & 4) ? (Wd[s][lo + 1] ^ Wd[s][lo]) : w3_alignbit16(Wd[s][lo + 1], Wd[s][lo]);
+                Bv[s][d] = (abl & 4) ? (Wd[s][lo + 1] ^ Wd[s][lo]) : pnsfm_alignbit16(Wd[s][lo + 1], Wd[s][lo]);
               }
             }
           if (abl & 16) { acc[nt][kx][0] += __builtin_bit_cast(float, Bv[0][0] ^ Bv[1][1] ^ Bv[2][2] ^ Bv[0][3] ^ Bv[1][2] ^ Bv[2][0] ^ A[0][0] ^ A[1][1] ^ A[2][2]); continue; }
@@ -344,7 +307,7 @@ __global__ void __launch_bounds__(256, OCC) conv2d_wgrad3_kernel(Wgrad3Args a) {
               A[2][d] = __builtin_bit_cast(unsigned, araw[slot][(d + 2) & 7]);
             }
           } else
-          w3_split8(araw[slot], A[0], A[1], A[2]);
+          bx3_split8(araw[slot], A[0], A[1], A[2]);
           if (do_bias) {
 #pragma unroll
             for (int u = 0; u < 8; ++u) bsum += araw[slot][u];
@@ -531,13 +494,7 @@ bool wgrad3_nt2_ok(int Cin, int ks) { return ks <= 3 && Cin > 32; }
 template <int KS, int NT, int WM, int TC, bool MASKED, int OCC = 2>
 static int launch_wgrad3(const Wgrad3Args& a, dim3 grid, hipStream_t s) {
   using Gm = Wgrad3Geom<KS, NT, WM, TC, OCC>;
-#ifndef PNSFM_EMU
-  static unsigned long long raised = 0;      // one bit per device
-  if (Gm::SMEM > 64 * 1024 &&
-      ensure_lds_limit(reinterpret_cast<const void*>(&conv2d_wgrad3_kernel<KS, NT, WM, TC, MASKED, OCC>), &raised, 160 * 1024,
-                       "conv2d_backward_weight"))
-    return -1;
-#endif
+  if (allow_wide_lds<&conv2d_wgrad3_kernel<KS, NT, WM, TC, MASKED, OCC>>(Gm::SMEM, "conv2d_backward_weight")) return -1;
   PNSFM_LAUNCH((conv2d_wgrad3_kernel<KS, NT, WM, TC, MASKED, OCC>), grid, dim3(256), (size_t)Gm::SMEM, s, a);
   return check_launch("conv2d_backward_weight (split-bf16)");
 }
@@ -545,52 +502,25 @@ static int launch_wgrad3(const Wgrad3Args& a, dim3 grid, hipStream_t s) {
 int enqueue_wgrad3(const float* x, const float* dy, float* dw, float* dbias, int B, int Cin, int Cout, int H, int W, int ks,
                    int split, int NT, int WMwant, hipStream_t s, const ConvSrc* ms) {
   if (!wgrad3_supported(Cin, Cout, H, W, ks)) { set_error("conv2d_backward_weight (split-bf16): unsupported shape"); return -1; }
-  if ((size_t)B * Cin * H * W * 4 >= (1ull << 31) || (size_t)B * Cout * H * W * 4 >= (1ull << 31)) {
-    set_error("conv2d_backward_weight (split-bf16): tensor too large for 32-bit buffer offsets");
-    return -1;
-  }
   if (NT != 2 || !wgrad3_nt2_ok(Cin, ks)) NT = 1;
   if (ms && NT == 2 && !conv_src_aligned(*ms, Cin, 64)) NT = 1;     // a 64-channel tile would straddle two tensors
   // two instantiations do not fit their register budget without spilling (3x3, four co tiles per workgroup, 32-column tiles: two
   // ci tiles per wave, and the three-workgroups-per-CU build): those requests run the one-ci-tile / two-workgroup build instead
   const bool tight = ks == 3 && wgrad3_WM(Cout, WMwant & 7) == 4 && wgrad3_tc(W) == 32 && W % 8 == 0;
   if (tight) { NT = 1; WMwant &= 7; }
-  if (ms && !conv_src_aligned(*ms, Cin, 32)) {
-    set_error("conv2d_backward_weight (split-bf16): the input tensors must end on 32-channel boundaries");
-    return -1;
-  }
-  Wgrad3Args a;
-  a.x = x; a.dy = dy; a.dw = dw; a.dbias = dbias;
-  a.x1 = ms ? ms->x1 : nullptr; a.x2 = ms ? ms->x2 : nullptr;
-  a.C0 = ms ? ms->C0 : Cin; a.C01 = ms ? ms->C0 + ms->C1 : Cin;
-  a.B = B; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W;
   const int tc = wgrad3_tc(W);
   const bool masked = W % 8 != 0;
-  a.tiles_x = ceil_div(W, tc);
-  a.tiles_per_img = a.tiles_x * ceil_div(H, 4);
-  a.total_tiles = B * a.tiles_per_img;
-  if (split < 1) split = 1;
-  if (split > a.total_tiles) split = a.total_tiles;
-  a.tiles_per_split = ceil_div(a.total_tiles, split);
-  const int splitP = ceil_div(a.total_tiles, a.tiles_per_split);
-  a.ci_tiles = ceil_div(Cin, 32 * NT);
+  const int ci_tiles = ceil_div(Cin, 32 * NT);
   const bool occ3 = (WMwant & 8) != 0 && ks == 3 && NT == 1 && !masked;      // WM | 8: the three-workgroups-per-CU build
   WMwant &= 7;
   const int WM = wgrad3_WM(Cout, WMwant);
   const int co_groups = ceil_div(ceil_div(Cout, 32), WM);
-  a.COP = co_groups * WM * 32;
-  a.CIP = a.ci_tiles * 32 * NT;
-  a.ws = nullptr; a.ws_bias = nullptr;
-  // pixel-split launch: partial tensors in the stream's scratch buffer (api.hip), summed by wgrad3_reduce_kernel
-  const size_t part = (size_t)ks * a.COP * ks * a.CIP;
-  ScratchLease lease(s, splitP > 1 ? ((size_t)splitP * (part + a.COP)) * sizeof(float) : 0);
-  if (splitP > 1) {
-    if (!lease.p) return -1;
-    a.ws = lease.as<float>();
-    a.ws_bias = a.ws + (size_t)splitP * part;
-  }
-  a.gx = a.ci_tiles * ks; a.gy = co_groups; a.bmap = block_map_mode();
-  dim3 grid(a.ci_tiles * ks * co_groups * splitP);
+  Wgrad3Args a;
+  const int splitP = wgrad_bx3_begin(a, "split-bf16", x, dy, dw, dbias, B, Cin, Cout, H, W, ks, 4, tc, co_groups * WM * 32,
+                                     ci_tiles * 32 * NT, split, s, ms);
+  if (splitP < 0) return -1;
+  a.g = {ci_tiles, ci_tiles * ks, co_groups, block_map_mode()};
+  dim3 grid(ci_tiles * ks * co_groups * splitP);
   int rc = 0;
 #define PNSFM_W3T(KSv, NTv, WMv)                                                    \
   do {                                                                              \
@@ -619,10 +549,7 @@ int enqueue_wgrad3(const float* x, const float* dy, float* dw, float* dbias, int
   else PNSFM_W3(7, 1);
 #undef PNSFM_W3T
 #undef PNSFM_W3
-  if (a.ws) {
-    if (!rc) rc = launch_wgrad3_reduce(a.ws, a.ws_bias, dw, dbias, splitP, ks, a.COP, a.CIP, Cin, Cout, s);
-  }
-  return rc;
+  return wgrad_bx3_finish(a, splitP, rc, ks, s);
 }
 
 }  // namespace pnsfm

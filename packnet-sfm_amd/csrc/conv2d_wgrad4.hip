@@ -1,8 +1,8 @@
 // conv2d_wgrad4.hip -- weight gradient of a stride-1 3x3 convolution, ALL NINE TAPS per workgroup (split-bf16 arithmetic).
 //
 // Same contract and arithmetic as conv2d_wgrad3.hip (the autograd weight gradient of nn.Conv2d in the reference's Conv2D /
-// ResidualConv / Pack / Unpack blocks, /root/reference/packnet_sfm/networks/layers/packnet/layers01.py:28-36, 57-60, 235-246,
-// 274-281):   dW[co][ci][ky][kx] = sum_{b, y, x} dY[b][co][y][x] * X[b][ci][y + ky - 1][x + kx - 1]
+// ResidualConv / Pack / Unpack blocks, packnet_sfm/networks/layers/packnet/layers01.py:28-36, 57-60, 235-246, 274-281):
+//   dW[co][ci][ky][kx] = sum_{b, y, x} dY[b][co][y][x] * X[b][ci][y + ky - 1][x + kx - 1]
 // every fp32 operand split EXACTLY into three bf16 pieces, the product rebuilt from the 6 piece products with fp32 accumulation.
 //
 // Why a second kernel.  wgrad3 gives a workgroup ONE kernel row: a 3x3 layer re-reads and re-splits every dY fragment three
@@ -15,7 +15,7 @@
 //     tiles 3 or 5 groups wide (W = 20, 40, 80, ...) waste nothing but the masked half group of W % 8 == 4;
 //   * A operand (dY): lane (co = l&15 [+16], group = l>>4) reads 32 contiguous bytes of the NCHW tensor straight from global
 //     memory, one or two k-steps ahead; the bias gradient is the running sum of the same registers;
-//   * B operand (X): the patch (TR + 2 rows, 8 columns of halo either side) is staged like wgrad3's: fp32 rows -> registers
+//   * B operand (X): the patch (TR + 2 rows, 8 columns of halo either side) is staged as in conv2d_wgrad3.hip: fp32 rows -> registers
 //     (issued before the previous tile's MFMAs) -> 3 bf16 pieces -> LDS [piece][ci][row][col], channel stride 8 * odd.  A lane
 //     reads its aligned 8-pixel block once per (kernel row, piece) plus the two neighbouring dwords and builds the three
 //     shifted operands with one v_alignbit_b32 per dword;
@@ -23,54 +23,15 @@
 //     pixel tiles are split over the launch's third logical dimension and the partial tensors of a split launch go to the stream's scratch buffer in
 //     wgrad3's layout ([split][ky][co][kx][ci]) for wgrad3_reduce_kernel: no atomics, bit-reproducible.
 // Roofline: MFMA-bound: 2*Cout*Cin*9*B*H*W algorithmic flop against 2500/6 TFLOP/s (bf16 dense peak / 6 products).
-#include "pnsfm_common.h"
+// The argument block and the host side of a launch (checks, split clamp, scratch, reduction) are shared with conv2d_wgrad3.hip:
+// conv2d_wgrad_bx3.h.
+#include "conv2d_wgrad_bx3.h"
 #include "../../include/pnsfm.h"
 
 namespace pnsfm {
 
-struct Wgrad4Args {
-  const float* x1;   // multi-source input (ConvSrc, pnsfm_common.h): channels [C0, C01) live in x1, [C01, Cin) in x2
-  const float* x2;
-  int C0, C01;       // C0 = C01 = Cin for a single source
-  const float* x;    // [B][Cin][H][W]  (multi-source: [B][C0][H][W])
-  const float* dy;   // [B][Cout][H][W]
-  float* dw;         // [Cout][Cin][3][3]   written directly when the launch has ONE pixel split ...
-  float* dbias;      // [Cout] or null
-  float* ws;         // ... else partial sums [split][ky][COP][kx][CIP] (+ [split][COP] bias partials at ws_bias)
-  float* ws_bias;
-  int COP, CIP;      // padded channel extents of the workspace (whole workgroup tiles)
-  int B, Cin, Cout, H, W;
-  int tiles_x, tiles_per_img, total_tiles, tiles_per_split;
-  int gx, gy, bmap;  // 1-D launch: ci tiles, co groups, block order (pnsfm_common.h: block_map_mode)
-};
-// what-if builds (tools/r6/wgrad_ablate.py; results wrong by construction): -DPNSFM_WG_ABLATE=<mask>, a COMPILE-TIME constant (a run-time
-// switch changed hipcc's register allocation: the 7x7 build ran 2x slower with every switch off) -- 1 no dY split, 2 no neighbour LDS
-// reads, 4 no shifted operands, 8 patch staged for the first tile only, 16 no MFMAs, 32 dY loaded once
-#ifdef PNSFM_WG_ABLATE
-#define PNSFM_WG_ABL(a) (PNSFM_WG_ABLATE)
-#else
-#define PNSFM_WG_ABL(a) 0
-#endif
-
-#ifdef PNSFM_EMU
-static inline unsigned w4_alignbit16(unsigned hi, unsigned lo) { return (lo >> 16) | (hi << 16); }
-#else
-__device__ __forceinline__ unsigned w4_alignbit16(unsigned hi, unsigned lo) { return __builtin_amdgcn_alignbit(hi, lo, 16); }
-#endif
-
-// 8 consecutive fp32 values -> three 16-byte bf16 pieces (conv2d_bx3.h: exact, round-to-nearest pieces)
-__device__ __forceinline__ void w4_split8(const float (&v)[8], pnsfm_u32x4& H, pnsfm_u32x4& M, pnsfm_u32x4& L) {
-#pragma unroll
-  for (int i = 0; i < 8; i += 2) {
-    const unsigned h = pnsfm_cvt_pk_bf16(v[i], v[i + 1]);
-    const float r0 = v[i] - pnsfm_u2f(h << 16), r1 = v[i + 1] - pnsfm_u2f(h & 0xffff0000u);
-    const unsigned m = pnsfm_cvt_pk_bf16(r0, r1);
-    const float s0 = r0 - pnsfm_u2f(m << 16), s1 = r1 - pnsfm_u2f(m & 0xffff0000u);
-    H[i >> 1] = h;
-    M[i >> 1] = m;
-    L[i >> 1] = pnsfm_cvt_pk_bf16(s0, s1);
-  }
-}
+struct Wgrad4Launch { int gx, gy, bmap; };      // logical grid x = gx = ci tiles
+struct Wgrad4Args : WgradBx3Args<Wgrad4Launch> {};      // (a type of its own: the kernels' symbols keep their names)
 
 template <int WCI, int TG, int TR>
 struct Wgrad4Geom {
@@ -109,8 +70,8 @@ __global__ void __launch_bounds__(256, 2) conv2d_wgrad4_kernel(Wgrad4Args a) {
   const int H = a.H, W = a.W, HW = H * W;
   // logical block (ci tile, co group, pixel split): ci tile fastest -- the workgroups of one pixel split read the same dY and X
   // -- and a contiguous range of that order per XCD (pnsfm_common.h)
-  const unsigned Lb = a.bmap == 2 ? pnsfm_xcd_logical_block(blockIdx.x, gridDim.x) : blockIdx.x;
-  const int bx = (int)(Lb % (unsigned)a.gx), by = (int)((Lb / (unsigned)a.gx) % (unsigned)a.gy), bz = (int)(Lb / (unsigned)(a.gx * a.gy));
+  const unsigned Lb = a.g.bmap == 2 ? pnsfm_xcd_logical_block(blockIdx.x, gridDim.x) : blockIdx.x;
+  const int bx = (int)(Lb % (unsigned)a.g.gx), by = (int)((Lb / (unsigned)a.g.gx) % (unsigned)a.g.gy), bz = (int)(Lb / (unsigned)(a.g.gx * a.g.gy));
   const int ci0 = bx * NCI;
   const int co0 = (by * WCO + wco) * 32;
   const int t_begin = bz * a.tiles_per_split;
@@ -190,7 +151,7 @@ __global__ void __launch_bounds__(256, 2) conv2d_wgrad4_kernel(Wgrad4Args a) {
     for (int it = 0; it < NIT; ++it) {
       if (ITEMS % 256 != 0 && it == NIT - 1 && it_lds[it] < 0) continue;
       pnsfm_u32x4 Hh, Mm, Ll;
-      w4_split8(raw[it], Hh, Mm, Ll);
+      bx3_split8(raw[it], Hh, Mm, Ll);
       unsigned char* d = smem + it_lds[it];
       *reinterpret_cast<pnsfm_u32x4*>(d) = Hh;
       *reinterpret_cast<pnsfm_u32x4*>(d + PIECE * 2) = Mm;
@@ -241,10 +202,10 @@ __global__ void __launch_bounds__(256, 2) conv2d_wgrad4_kernel(Wgrad4Args a) {
         pnsfm_u32x4 Bt[3];
         if (abl & 4) { Bt[0] = c; Bt[2] = c; Bt[0][0] ^= pv; Bt[2][3] ^= nx; }
         else {
-        Bt[0][0] = w4_alignbit16(c[0], pv);   Bt[0][1] = w4_alignbit16(c[1], c[0]);
-        Bt[0][2] = w4_alignbit16(c[2], c[1]); Bt[0][3] = w4_alignbit16(c[3], c[2]);
-        Bt[2][0] = w4_alignbit16(c[1], c[0]); Bt[2][1] = w4_alignbit16(c[2], c[1]);
-        Bt[2][2] = w4_alignbit16(c[3], c[2]); Bt[2][3] = w4_alignbit16(nx, c[3]);
+        Bt[0][0] = pnsfm_alignbit16(c[0], pv);   Bt[0][1] = pnsfm_alignbit16(c[1], c[0]);
+        Bt[0][2] = pnsfm_alignbit16(c[2], c[1]); Bt[0][3] = pnsfm_alignbit16(c[3], c[2]);
+        Bt[2][0] = pnsfm_alignbit16(c[1], c[0]); Bt[2][1] = pnsfm_alignbit16(c[2], c[1]);
+        Bt[2][2] = pnsfm_alignbit16(c[3], c[2]); Bt[2][3] = pnsfm_alignbit16(nx, c[3]);
         }
         Bt[1] = c;
         if (abl & 16) { acc[0][ky][0][0] += __builtin_bit_cast(float, Bt[0][0] ^ Bt[2][3] ^ A[0][0][0] ^ A[1][2][3] ^ A[0][1][1] ^ A[1][1][2] ^ A[1][0][0] ^ A[0][2][3]); continue; }
@@ -285,8 +246,8 @@ __global__ void __launch_bounds__(256, 2) conv2d_wgrad4_kernel(Wgrad4Args a) {
             A[s2][2][d] = __builtin_bit_cast(unsigned, araw[slot][s2][(d + 2) & 7]);
           }
       } else {
-      w4_split8(araw[slot][0], A[0][0], A[0][1], A[0][2]);
-      w4_split8(araw[slot][1], A[1][0], A[1][1], A[1][2]);
+      bx3_split8(araw[slot][0], A[0][0], A[0][1], A[0][2]);
+      bx3_split8(araw[slot][1], A[1][0], A[1][1], A[1][2]);
       }
       if (do_bias) {
 #pragma unroll
@@ -344,10 +305,6 @@ __global__ void __launch_bounds__(256, 2) conv2d_wgrad4_kernel(Wgrad4Args a) {
   }
 }
 
-// conv2d_wgrad3.hip: sums the partial tensors of a pixel-split launch in a fixed order
-int launch_wgrad3_reduce(const float* ws, const float* ws_bias, float* dw, float* dbias, int Z, int KS, int COP, int CIP, int Cin,
-                         int Cout, hipStream_t s);
-
 bool wgrad4_supported(int Cin, int Cout, int H, int W, int ks) {
   return ks == 3 && W % 4 == 0 && Cin >= 16 && Cout >= 16 && H >= 1;      // rows of 4-pixel groups (16-byte aligned)
 }
@@ -364,13 +321,7 @@ int wgrad4_base_blocks(int Cin, int Cout, int WCI) { return ceil_div(Cin, 16 * W
 template <int WCI, int TG, int TR, bool MASKED>
 static int launch_wgrad4(const Wgrad4Args& a, dim3 grid, hipStream_t s) {
   using Gm = Wgrad4Geom<WCI, TG, TR>;
-#ifndef PNSFM_EMU
-  static unsigned long long raised = 0;      // one bit per device
-  if (Gm::SMEM > 64 * 1024 &&
-      ensure_lds_limit(reinterpret_cast<const void*>(&conv2d_wgrad4_kernel<WCI, TG, TR, MASKED>), &raised, 160 * 1024,
-                       "conv2d_backward_weight"))
-    return -1;
-#endif
+  if (allow_wide_lds<&conv2d_wgrad4_kernel<WCI, TG, TR, MASKED>>(Gm::SMEM, "conv2d_backward_weight")) return -1;
   PNSFM_LAUNCH((conv2d_wgrad4_kernel<WCI, TG, TR, MASKED>), grid, dim3(256), (size_t)Gm::SMEM, s, a);
   return check_launch("conv2d_backward_weight (split-bf16, nine taps)");
 }
@@ -379,42 +330,16 @@ static int launch_wgrad4(const Wgrad4Args& a, dim3 grid, hipStream_t s) {
 int enqueue_wgrad4(const float* x, const float* dy, float* dw, float* dbias, int B, int Cin, int Cout, int H, int W, int split,
                    int cfg, hipStream_t s, const ConvSrc* ms) {
   if (!wgrad4_supported(Cin, Cout, H, W, 3)) { set_error("conv2d_backward_weight (nine taps): unsupported shape"); return -1; }
-  if ((size_t)B * Cin * H * W * 4 >= (1ull << 31) || (size_t)B * Cout * H * W * 4 >= (1ull << 31)) {
-    set_error("conv2d_backward_weight (nine taps): tensor too large for 32-bit buffer offsets");
-    return -1;
-  }
-  if (ms && !conv_src_aligned(*ms, Cin, 32)) {
-    set_error("conv2d_backward_weight (nine taps): the input tensors must end on 32-channel boundaries");
-    return -1;
-  }
   const int WCI = (cfg & 15) == 1 ? 1 : 2;
   const int TG = wgrad4_TG(W, (cfg >> 4) & 15);
   const int TR = TG == 3 ? wgrad4_TR(H, (cfg >> 8) & 15) : 4;      // 6-row tiles exist for the 3-group (W <= 24) tiles only
   const bool masked = W % 8 != 0;
-  Wgrad4Args a;
-  a.x = x; a.dy = dy; a.dw = dw; a.dbias = dbias;
-  a.x1 = ms ? ms->x1 : nullptr; a.x2 = ms ? ms->x2 : nullptr;
-  a.C0 = ms ? ms->C0 : Cin; a.C01 = ms ? ms->C0 + ms->C1 : Cin;
-  a.B = B; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W;
-  a.tiles_x = ceil_div(W, 8 * TG);
-  a.tiles_per_img = a.tiles_x * ceil_div(H, TR);
-  a.total_tiles = B * a.tiles_per_img;
-  if (split < 1) split = 1;
-  if (split > a.total_tiles) split = a.total_tiles;
-  a.tiles_per_split = ceil_div(a.total_tiles, split);
-  const int splitP = ceil_div(a.total_tiles, a.tiles_per_split);
   const int ci_tiles = ceil_div(Cin, 16 * WCI), co_groups = ceil_div(Cout, 32 * (4 / WCI));
-  a.COP = co_groups * 32 * (4 / WCI);
-  a.CIP = ci_tiles * 16 * WCI;
-  a.ws = nullptr; a.ws_bias = nullptr;
-  const size_t part = (size_t)9 * a.COP * a.CIP;
-  ScratchLease lease(s, splitP > 1 ? ((size_t)splitP * (part + a.COP)) * sizeof(float) : 0);
-  if (splitP > 1) {
-    if (!lease.p) return -1;
-    a.ws = lease.as<float>();
-    a.ws_bias = a.ws + (size_t)splitP * part;
-  }
-  a.gx = ci_tiles; a.gy = co_groups; a.bmap = block_map_mode();
+  Wgrad4Args a;
+  const int splitP = wgrad_bx3_begin(a, "nine taps", x, dy, dw, dbias, B, Cin, Cout, H, W, 3, TR, 8 * TG, co_groups * 32 * (4 / WCI),
+                                     ci_tiles * 16 * WCI, split, s, ms);
+  if (splitP < 0) return -1;
+  a.g = {ci_tiles, co_groups, block_map_mode()};
   dim3 grid(ci_tiles * co_groups * splitP);
   int rc = 0;
 #define PNSFM_W4(WCIv, TGv, TRv)                                                  \
@@ -432,8 +357,7 @@ int enqueue_wgrad4(const float* x, const float* dy, float* dw, float* dbias, int
   if (WCI == 1) PNSFM_W4G(1); else PNSFM_W4G(2);
 #undef PNSFM_W4G
 #undef PNSFM_W4
-  if (a.ws && !rc) rc = launch_wgrad3_reduce(a.ws, a.ws_bias, dw, dbias, splitP, 3, a.COP, a.CIP, Cin, Cout, s);
-  return rc;
+  return wgrad_bx3_finish(a, splitP, rc, 3, s);
 }
 
 }  // namespace pnsfm

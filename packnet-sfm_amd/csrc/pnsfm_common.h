@@ -189,6 +189,31 @@ __device__ __forceinline__ float pnsfm_buf_load(const pnsfm_buf& b, unsigned vof
 #include <cstddef>
 #include <cstdint>
 
+// ---- split-bf16 arithmetic (conv2d_bx3.h has the derivation): the ONE definition every kernel family uses -- forward, backward-data,
+// ping-pong, 1x1, the stem and the split-bf16 weight gradients.  The `*_error_vs_fp64` tests rest on these being one function.
+// 8 consecutive-k fp32 values -> the three 16-byte operand pieces.  Exact 3-way split with round-to-nearest pieces:
+//   h = bf16(v), m = bf16(v - h), l = v - h - m   (v - h and v - h - m are exact in fp32; l has <= 8 significant bits, so
+//   the last conversion is exact too: v == h + m + l).  |m| <= 2^-9 |v|, |l| <= 2^-18 |v|, signs mixed.
+// 11 VALU instructions per PAIR of values: 3 v_cvt_pk_bf16_f32, 4 unpacks (shift / mask), 4 subtractions.
+__device__ __forceinline__ void bx3_split8(const float (&v)[8], pnsfm_u32x4& H, pnsfm_u32x4& M, pnsfm_u32x4& L) {
+#pragma unroll
+  for (int i = 0; i < 8; i += 2) {
+    const unsigned h = pnsfm_cvt_pk_bf16(v[i], v[i + 1]);
+    const float r0 = v[i] - pnsfm_u2f(h << 16), r1 = v[i + 1] - pnsfm_u2f(h & 0xffff0000u);
+    const unsigned m = pnsfm_cvt_pk_bf16(r0, r1);
+    const float s0 = r0 - pnsfm_u2f(m << 16), s1 = r1 - pnsfm_u2f(m & 0xffff0000u);
+    H[i >> 1] = h;
+    M[i >> 1] = m;
+    L[i >> 1] = pnsfm_cvt_pk_bf16(s0, s1);
+  }
+}
+// v_alignbit_b32 by 16: the dword of two bf16 elements that starts one element into `lo` (a one-element shift of a packed operand)
+#ifdef PNSFM_EMU
+static inline unsigned pnsfm_alignbit16(unsigned hi, unsigned lo) { return (lo >> 16) | (hi << 16); }
+#else
+__device__ __forceinline__ unsigned pnsfm_alignbit16(unsigned hi, unsigned lo) { return __builtin_amdgcn_alignbit(hi, lo, 16); }
+#endif
+
 // ---- fp16 storage (evaluation / inference forward, include/pnsfm.h "fp16 forward").  Activations and parameters are stored as IEEE
 // half; every kernel computes in fp32 and rounds its output ONCE to nearest-even ((_Float16)v is v_cvt_f16_f32 in the default
 // round-to-nearest mode, never the round-toward-zero v_cvt_pkrtz form).  The storage-templated kernels load / store through these
@@ -319,6 +344,16 @@ int enqueue_wgrad4(const float* x, const float* dy, float* dw, float* dbias, int
 // more than 64 KB of dynamic LDS needs hipFuncSetAttribute once per kernel AND device: `mask` (one static per kernel
 // instantiation) remembers the devices already done (api.hip).  0 on success.
 int ensure_lds_limit(const void* kernel, unsigned long long* mask, int bytes, const char* what);
+// ... which is what every launcher of such a kernel calls: raises the limit to all 160 KB of a CDNA4 CU's LDS, once per kernel
+// instantiation and device (nothing to do on the emulator); 0 on success
+template <auto Kernel>
+static inline int allow_wide_lds(size_t smem_bytes, const char* what) {
+#ifndef PNSFM_EMU
+  static unsigned long long done = 0;     // one bit per device
+  if (smem_bytes > 64 * 1024) return ensure_lds_limit(reinterpret_cast<const void*>(Kernel), &done, 160 * 1024, what);
+#endif
+  return 0;
+}
 
 // profiling of the dominant kernels with events on the launch stream (see api.hip)
 void prof_begin(int kind, double flops, hipStream_t stream, const int* meta = nullptr);

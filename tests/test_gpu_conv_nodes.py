@@ -5,7 +5,7 @@ import pytest
 import torch
 
 import parity_cases as P
-from test_kernels_emulated import CONV_NODE_SOURCES, _conv_node_data, _conv_node_run
+from test_kernels_emulated import CONV_NODE_SOURCES, WGRAD_CAT_PINNED, _check_wgrad_cat_pinned, _conv_node_data, _conv_node_run
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
@@ -60,3 +60,12 @@ def test_conv_nodes_side_stream_fork_and_sequencer(Cs, tap, gn, twice):
         HF._FAST_FORK = was_fork
         HF.set_wgrad_stream(was_side)
         _seq.set_enabled(True)
+
+
+@pytest.mark.parametrize('kernel', [3, 2])
+@pytest.mark.parametrize('case', WGRAD_CAT_PINNED)
+def test_conv2d_wgrad_cat_pinned_kernel_gpu(case, kernel):
+    """The multi-source (cat) weight gradient pinned to the nine-taps kernel and to wgrad3 (test_kernels_emulated's cases) on the
+    device, vs F.conv2d's autograd on the concatenated tensor."""
+    assert torch.cuda.is_available(), 'these tests need an MI355X'
+    _check_wgrad_cat_pinned(DEV, case, kernel, 5e-5)

@@ -1152,6 +1152,54 @@ def test_conv2d_cat_multi_source(emulated_kernels, case):
         assert ops.conv2d_cat_wgrad_supported(list(case[1]), case[2], case[3], case[4], case[5], B=case[0])
 
 
+# (sources, Cout, B, H, W, pixel split, nine-taps tile rows): the second tensor, a masked half group (W % 8 == 4) and the two-stage
+# reduction -- 4-row tiles pinned: the library's 6-row tile would make the 6 x 20 image ONE tile and clamp the split to 1 -- ; the third
+# tensor, a 5-group tile, direct stores and ragged rows
+WGRAD_CAT_PINNED = [((32, 16), 32, 1, 6, 20, 2, 4), ((32, 32, 16), 48, 2, 5, 40, 1, 0)]
+
+
+def _check_wgrad_cat_pinned(device, case, kernel, tol):
+    """ops.conv2d_backward_weight_cat with the decision pinned through pnsfm_tune_set (multi-source key: kind 2 + 10 + 100 + 1000) to
+    kernel 3 (nine taps, two ci tiles per workgroup, library tile width) or 2 (wgrad3, one ci tile per wave), vs F.conv2d's autograd on
+    the concatenated tensor.  No entry point reports the split that ran: the tile counts are worked out here so that the pinned split
+    is one the kernels keep (conv2d_wgrad_bx3.h clamps it to the tile count)."""
+    import ctypes
+    import torch.nn.functional as F
+    from packnet_sfm.hip import _lib, ops
+    lib = _lib.get()
+    lib.pnsfm_set_conv_math(1)
+    Cs, Cout, B, H, W, split, TR = case
+    Cin = sum(Cs)
+    TG = 3 if W <= 24 else (5 if -(-W // 40) * 40 < -(-W // 32) * 32 else 4)              # wgrad4_TG: tile width in 8-pixel groups
+    tiles4 = B * -(-W // (8 * TG)) * -(-H // (TR or 4))                                    # nine taps: TR x 8 TG pixel tiles
+    tiles3 = B * -(-W // 16) * -(-H // 4)                                                  # wgrad3: 4 x 16 (both widths: 16 wastes fewer columns / W % 8 == 4)
+    assert split <= (tiles4 if kernel == 3 else tiles3), 'the pinned pixel split would be clamped'
+    key = (ctypes.c_int * 7)(2 + 10 + 100 + 1000, B, Cin, Cout, H * W, W, 3)
+    assert lib.pnsfm_tune_set(key, split, (3 | ((2 | (TR << 8)) << 4)) if kernel == 3 else (2 | (1 << 4))) == 0
+    g = torch.Generator().manual_seed(Cin + Cout + H + W)
+    xs = [torch.randn(B, c, H, W, generator=g) for c in Cs]
+    w = torch.randn(Cout, Cin, 3, 3, generator=g) * 0.1
+    b = torch.randn(Cout, generator=g)
+    wr, br = w.clone().requires_grad_(True), b.clone().requires_grad_(True)
+    yr = F.conv2d(torch.cat(xs, 1), wr, br, padding=1)
+    dy = torch.randn(yr.shape, generator=g)
+    yr.backward(dy)
+    try:
+        dw, db = ops.conv2d_backward_weight_cat([t.to(device) for t in xs], dy.to(device), 3)
+        P.check(dw, wr.grad, tol, 'wgrad (cat, kernel %d)' % kernel)
+        P.check(db, br.grad, tol, 'dbias (cat, kernel %d)' % kernel)
+    finally:
+        lib.pnsfm_set_wgrad_variant(-1)      # clears the pinned entry
+
+
+@pytest.mark.parametrize('kernel', [3, 2])
+@pytest.mark.parametrize('case', WGRAD_CAT_PINNED)
+def test_conv2d_wgrad_cat_pinned_kernel(emulated_kernels, case, kernel):
+    """The multi-source (cat) weight gradient on the nine-taps kernel and on wgrad3: both kernels pick the source tensor of a ci tile
+    the same way and must read the same channels."""
+    _check_wgrad_cat_pinned('cpu', case, kernel, 1e-5)
+
+
 @pytest.mark.parametrize('shape,cfg', [((2, 48, 64, 9, 32, 3), c) for c in [(2, 3, 0, 1), (1, 4, 1, 3), (2, 7, 0, 1), (1, 7, 1, 2), (2, 6, 0, 1)]] +
                          [((2, 40, 33, 5, 24, 1), (2, 7, 0, 1)), ((2, 40, 33, 5, 24, 1), (1, 4, 1, 3)),
                           ((1, 32, 40, 8, 32, 7), (1, 7, 1, 2)), ((1, 32, 40, 8, 32, 7), (2, 3, 0, 1))])
