@@ -146,7 +146,17 @@ int pnsfm_tune_set(const int* key7, int v0, int v1);
  * split-bf16 LDS plans, 7 ping-pong workgroup, 8 the 1x1 kernel without LDS), pixel tiles per wave NT, M tiles per wave MT, taps per weight stage G, K-split,
  * tile mode (0 classic, 1 16-wide rectangles, 2 row bands), workgroups, LDS bytes}.  A pinned configuration that does not fit
  * a shape silently falls back to the heuristic one; tests that pin a variant assert on this.  A backward-weight call that ran the
- * stem's kernel (3 input channels, 5x5) leaves {105, 0, MT, 0, pixel splits, 0, workgroups, 0}.  Returns 1 when no launch happened yet. */
+ * stem's kernel (3 input channels, 5x5) leaves {105, 0, MT, 0, pixel splits, 0, workgroups, 0}.
+ * Every backward-weight call leaves the kernel build it LAUNCHED (written where the template instantiation is chosen: a decision the
+ * library re-routes or drops shows here), code = 100 + the profiling tools' `kernel` column, [4] = pixel splits launched, [6] =
+ * workgroups, [7] = dynamic LDS bytes:
+ *   {100, stride, MT, pixels per tile PT, splits, tile mode, workgroups, LDS}                    generic f32 kernel
+ *   {102, 0, 0, 0, splits, 0, workgroups, 0}                                                     tap-major kernel
+ *   {103, NT, WM, TC, splits, OCC | masked << 4 | KS << 8, workgroups, LDS}                      split-bf16, one kernel row per workgroup
+ *        (conv2d_wgrad3_kernel<KS, NT, WM, TC, MASKED, OCC>: ci tiles per wave, co tiles per workgroup, tile columns, workgroups per CU)
+ *   {104, WCI, TG, TR, splits, masked << 4, workgroups, LDS}                                     split-bf16, nine taps per workgroup
+ *        (conv2d_wgrad4_kernel<WCI, TG, TR, MASKED>: ci tiles per workgroup, tile width in 8-pixel groups, tile rows)
+ * Returns 1 when no launch happened yet. */
 int pnsfm_conv2d_last_config(int* out8);
 /* Tuning database: environment PNSFM_TUNE_DB=<file> loads earlier autotune decisions when the library first tunes and
  * appends new ones (text, one line per layer shape) -- what MIOpen's user find-db does for the reference's cuDNN/MIOpen

@@ -1309,6 +1309,11 @@ static ConvDecision conv_tune(const ConvGeom& g, const std::array<int, 7>& key, 
 
 // configuration of the calling thread's most recent forward / backward-data launch (pnsfm_conv2d_last_config)
 static thread_local std::array<int, 8> g_last_conv = {-1, 0, 0, 0, 0, 0, 0, 0};
+// ... and of its most recent weight-gradient launch: written where the template instantiation is chosen (here and in
+// conv2d_wgrad{2,3,4}.hip), so it says what was launched, not what was asked for.  Layouts: include/pnsfm.h
+void conv_last_config_set(int code, int p1, int p2, int p3, int splits, int p5, int blocks, int smem) {
+  g_last_conv = {code, p1, p2, p3, splits, p5, blocks, smem};
+}
 
 static int launch_conv(const float* x, const float* wp, const float* bias, float* y, int B, int Cin, int Cout,
                        int H, int W, int ks, hipStream_t stream, const char* what, int kind_tag, int S = 1, int Hi = 0,
@@ -2215,6 +2220,7 @@ static int enqueue_wgrad_generic(const WgradPlan& p, int split) {
     c.zstride = slab;
   }
   dim3 grid(p.n_tiles, p.m_tiles, c.splitP);
+  conv_last_config_set(100, p.S, p.MT, c.PT, c.splitP, c.mode, (int)(grid.x * grid.y * grid.z), (int)p.smem);
   if (p.MT == 2) PNSFM_LAUNCH((conv2d_wgrad_kernel<2>), grid, dim3(256), p.smem, p.s, c);
   else PNSFM_LAUNCH((conv2d_wgrad_kernel<1>), grid, dim3(256), p.smem, p.s, c);
   int rc = check_launch("conv2d_backward_weight");

@@ -309,6 +309,7 @@ int enqueue_wgrad2(const float* x, const float* dy, float* dw, float* dbias, int
     a.zstride = slab;
   }
   dim3 grid(a.ci_tiles * (ks == 5 ? 5 : 1), ceil_div(Cout, 64), a.splitP);
+  conv_last_config_set(102, 0, 0, 0, a.splitP, 0, (int)(grid.x * grid.y * grid.z), 0);
   int rc = 0;
 #define PNSFM_W2(KSv)                                                     \
   do {                                                                    \

@@ -495,6 +495,7 @@ template <int KS, int NT, int WM, int TC, bool MASKED, int OCC = 2>
 static int launch_wgrad3(const Wgrad3Args& a, dim3 grid, hipStream_t s) {
   using Gm = Wgrad3Geom<KS, NT, WM, TC, OCC>;
   if (allow_wide_lds<&conv2d_wgrad3_kernel<KS, NT, WM, TC, MASKED, OCC>>(Gm::SMEM, "conv2d_backward_weight")) return -1;
+  conv_last_config_set(103, NT, WM, TC, (int)grid.x / (a.g.gx * a.g.gy), OCC | (MASKED ? 16 : 0) | (KS << 8), (int)grid.x, Gm::SMEM);
   PNSFM_LAUNCH((conv2d_wgrad3_kernel<KS, NT, WM, TC, MASKED, OCC>), grid, dim3(256), (size_t)Gm::SMEM, s, a);
   return check_launch("conv2d_backward_weight (split-bf16)");
 }

@@ -322,6 +322,7 @@ template <int WCI, int TG, int TR, bool MASKED>
 static int launch_wgrad4(const Wgrad4Args& a, dim3 grid, hipStream_t s) {
   using Gm = Wgrad4Geom<WCI, TG, TR>;
   if (allow_wide_lds<&conv2d_wgrad4_kernel<WCI, TG, TR, MASKED>>(Gm::SMEM, "conv2d_backward_weight")) return -1;
+  conv_last_config_set(104, WCI, TG, TR, (int)grid.x / (a.g.gx * a.g.gy), MASKED ? 16 : 0, (int)grid.x, Gm::SMEM);
   PNSFM_LAUNCH((conv2d_wgrad4_kernel<WCI, TG, TR, MASKED>), grid, dim3(256), (size_t)Gm::SMEM, s, a);
   return check_launch("conv2d_backward_weight (split-bf16, nine taps)");
 }

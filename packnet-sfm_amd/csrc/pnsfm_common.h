@@ -311,6 +311,11 @@ int conv_pack_MP(int Mc);
 int conv_pick_MT(int Mc);
 bool conv_bx3_supported(int Kc, int ks);   // shapes the split-bf16 forward / backward-data kernels take
 
+// pnsfm_conv2d_last_config of a weight-gradient launch (conv2d.hip keeps the record): called by whoever picks the kernel build, with
+// what it launched -- {code = 100 + the profiling `kernel` column, three build parameters, pixel splits launched, a fifth parameter,
+// workgroups, LDS bytes} (include/pnsfm.h)
+void conv_last_config_set(int code, int p1, int p2, int p3, int splits, int p5, int blocks, int smem);
+
 // tap-major weight-gradient kernel (conv2d_wgrad2.hip); the generic one lives in conv2d.hip and the autotuner picks
 bool wgrad2_supported(int Cin, int Cout, int H, int W, int ks);
 int wgrad2_total_tiles(int B, int H, int W);

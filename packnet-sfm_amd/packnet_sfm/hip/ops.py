@@ -268,11 +268,17 @@ def conv2d_forward_strided(x, wp_fwd, bias, Cout, ks, stride):
     return y
 
 
-def conv2d_backward_weight_strided(x, dy, ks, stride, want_bias=True):
+def conv2d_backward_weight_strided(x, dy, ks, stride, want_bias=True, dw_out=None, db_out=None):
     _chk(x, dy); _f32(x, dy)
     B, Cin, H, W = x.shape
     Cout = dy.shape[1]
-    dw, db = _alloc_dw_db(Cout, Cin, ks, want_bias, x.device)
+    if dw_out is not None:      # gradient slots, as conv2d_backward_weight
+        _chk(dw_out, db_out); _f32(dw_out, db_out)
+        if tuple(dw_out.shape) != (Cout, Cin, ks, ks) or (want_bias and (db_out is None or db_out.numel() != Cout)):
+            raise RuntimeError("conv2d_backward_weight_strided: gradient slot has the wrong shape")
+        dw, db = dw_out.view(dw_out.shape), (db_out.view(db_out.shape) if want_bias else None)
+    else:
+        dw, db = _alloc_dw_db(Cout, Cin, ks, want_bias, x.device)
     rc = _lib.get().pnsfm_conv2d_backward_weight_strided(_ptr(x), _ptr(dy), _ptr(dw), _ptr(db), B, Cin, Cout, H, W, ks, stride,
                                                          _stream(x))
     _lib.check(rc, "conv2d_backward_weight_strided")

@@ -29,23 +29,7 @@ def _need_gpu():
 
 
 # ------------------------------------------------------------------------------------------------ (a) wgrad3 vs fp64
-def _wgrad_fp64(x, dy, ks):
-    """dW[co][ci][ky][kx] = sum_{b,y,x} dY * X(shifted) in float64, and the same sum over |dY| |X| (the quantity rounding errors
-    scale with), by unfold + matmul per image (rocBLAS dgemm: an implementation that shares nothing with the kernels under test)."""
-    B, Cin, H, W = x.shape
-    Cout = dy.shape[1]
-    dw = torch.zeros(Cout, Cin * ks * ks, dtype=torch.float64, device=x.device)
-    mag = torch.zeros_like(dw)
-    cstep = max(1, (1 << 28) // (H * W * ks * ks))              # <= 2 GiB of unfolded fp64 columns at a time
-    for b in range(B):
-        dyb = dy[b].double().reshape(Cout, H * W)
-        for c0 in range(0, Cin, cstep):
-            c1 = min(Cin, c0 + cstep)
-            cols = F.unfold(x[b:b + 1, c0:c1].double(), ks, padding=ks // 2)[0]        # [(c1-c0)*k*k, H*W]
-            dw[:, c0 * ks * ks:c1 * ks * ks] += dyb @ cols.t()
-            mag[:, c0 * ks * ks:c1 * ks * ks] += dyb.abs() @ cols.abs().t()
-            del cols
-    return dw.view(Cout, Cin, ks, ks), mag.view(Cout, Cin, ks, ks)
+from wgrad_cases import wgrad_fp64 as _wgrad_fp64      # float64 unfold + matmul, shared with tests/test_gpu_wgrad_ladder.py
 
 
 WGRAD_REAL_SHAPES = [  # (B, Cin, Cout, H, W, k): weight gradients of the 192x640 batch-4 step at their real reduction length

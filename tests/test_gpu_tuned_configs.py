@@ -5,7 +5,7 @@ shape alone) with autotuning on and the shipped database loaded, then the eight 
 (variant, NT, MT, taps per stage, K-split, tile mode, blocks, LDS bytes) are compared with tests/golden/tuned_configs.json.  The
 fixture was recorded by replay_database() below on the build of the commit BEFORE the launch policy of conv2d.hip was reorganised
 (decision codec, one dispatch, WgradPlan), so a line that decodes, falls back or tiles differently afterwards fails here.
-Weight-gradient lines (kinds x2) have no configuration read-back and are not part of this test."""
+Weight-gradient lines (kinds x2) are not part of this test: tests/test_gpu_wgrad_ladder.py replays them against what each line names."""
 import ctypes
 import json
 import os

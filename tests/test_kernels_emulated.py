@@ -5,6 +5,7 @@ import pytest
 import torch
 
 import parity_cases as P
+import wgrad_cases as WC
 
 
 @pytest.mark.parametrize('name', ['conv2d_k3', 'conv2d_k5', 'conv2d_k7'])
@@ -424,7 +425,10 @@ def test_conv2d_wgrad_split_bf16(emulated_kernels, shape):
 def test_conv2d_wgrad_split_bf16_pinned(emulated_kernels, shape, cfg):
     """wgrad3 configurations the autotuner explores on the GPU, pinned through pnsfm_tune_set: cfg = (pixel split, ci tiles per
     wave NT, co tiles per workgroup WM; WM | 8 = the build whose register budget lets three workgroups share a CU) -- WM below the
-    layer's maximum turns waves into extra pixel shares (LDS reduction)."""
+    layer's maximum turns waves into extra pixel shares (LDS reduction).  The build that ran is read back (wgrad_cases.launched_build):
+    NT = 2 runs as NT = 1 on the 5x5 shape (two ci tiles per wave exist for 1x1 and 3x3 only) and on the Cout = 128, W = 32 shape
+    when all four co tiles are asked for (the "tight" re-route of enqueue_wgrad3, which also drops | 8: cfg (2, 1, 12) runs
+    <3, 1, 4, 32, OCC 2> there); elsewhere WM | 8 is the OCC = 3 build on the 3x3 shapes with NT = 1, and plain OCC = 2 on the 5x5 one."""
     import ctypes
     import torch.nn.functional as F
     from packnet_sfm.hip import _lib, ops
@@ -443,6 +447,14 @@ def test_conv2d_wgrad_split_bf16_pinned(emulated_kernels, shape, cfg):
     dy = torch.randn(yr.shape, generator=g)
     yr.backward(dy)
     dw, db = ops.conv2d_backward_weight(x, dy, ks)
+    most = 4 if Cout > 96 else (2 if Cout > 32 else 1)
+    WMr = (WM & 7) if (WM & 7) < most else most
+    tight = ks == 3 and WMr == 4 and W == 32
+    NTr = NT if (ks <= 3 and Cin > 32 and not tight) else 1
+    TC = 16 if W == 40 else 32                          # W = 40: three 16-column tiles waste fewer columns than two 32-column ones
+    cfg_ran = ops.conv2d_last_config()
+    assert WC.launched_build(cfg_ran) == (103, ks, NTr, WMr, TC, 0, 3 if (WM & 8 and ks == 3 and NTr == 1 and not tight) else 2), cfg_ran
+    assert cfg_ran[4] == WC.clamped_split(WC.launched_tiles(cfg_ran, B, H, W, ks), split), cfg_ran
     P.check(dw, wr.grad, 1e-5, 'wgrad (split-bf16, pinned)')
     P.check(db, br.grad, 1e-5, 'dbias (split-bf16, pinned)')
     lib.pnsfm_set_wgrad_variant(-1)      # clears the pinned entry
@@ -481,9 +493,29 @@ def test_conv2d_wgrad_nine_taps(emulated_kernels, shape, cfg):
     dy = torch.randn(yr.shape, generator=g)
     yr.backward(dy)
     dw, db = ops.conv2d_backward_weight(x, dy, ks)
+    cfg_ran = ops.conv2d_last_config()
+    build = WC.launched_build(cfg_ran)
+    assert build[0] == 104 and build[1] == WCI and build[4] == (1 if W % 8 else 0), cfg_ran
+    assert build[2] == (3 if W <= 24 else (TG or build[2])) and build[3] == (TR or build[3]) and build[2:4] in ((3, 4), (3, 6), (4, 4), (5, 4)), cfg_ran
+    assert cfg_ran[4] == WC.clamped_split(WC.launched_tiles(cfg_ran, B, H, W, ks), split), cfg_ran
     P.check(dw, wr.grad, 1e-5, 'wgrad (nine taps)')
     P.check(db, br.grad, 1e-5, 'dbias (nine taps)')
     lib.pnsfm_set_wgrad_variant(-1)      # clears the pinned entry
+
+
+def test_wgrad_ladder_table_is_sound():
+    """tests/wgrad_cases.py names exactly the 58 + 16 builds the two split-bf16 dispatch ladders can launch."""
+    WC.check_table()
+
+
+@pytest.mark.parametrize('case', WC.CASES, ids=WC.CASE_IDS)
+def test_wgrad_ladder_case_emulated(emulated_kernels, case):
+    """Every weight-gradient build (tests/wgrad_cases.py: the table tests/test_gpu_wgrad_ladder.py runs on the device) on the emulator:
+    the build and the pixel splits read back, NaN guards around the gradient slots, every element written, and float64 error within
+    16 * 2^-24 of sum |dY||X| -- far inside this file's usual 1e-5 of the maximum, and tight enough to see one of the six piece
+    products missing.  One launch per case, at the case's pixel split (short last share, two-stage reduction); the un-split launch
+    and the repeated launch of each case run on the device only."""
+    WC.run_case('cpu', case, with_single_split=False, repeat=False)
 
 
 @pytest.mark.parametrize('nf', [8, 4])
@@ -1161,8 +1193,8 @@ WGRAD_CAT_PINNED = [((32, 16), 32, 1, 6, 20, 2, 4), ((32, 32, 16), 48, 2, 5, 40,
 def _check_wgrad_cat_pinned(device, case, kernel, tol):
     """ops.conv2d_backward_weight_cat with the decision pinned through pnsfm_tune_set (multi-source key: kind 2 + 10 + 100 + 1000) to
     kernel 3 (nine taps, two ci tiles per workgroup, library tile width) or 2 (wgrad3, one ci tile per wave), vs F.conv2d's autograd on
-    the concatenated tensor.  No entry point reports the split that ran: the tile counts are worked out here so that the pinned split
-    is one the kernels keep (conv2d_wgrad_bx3.h clamps it to the tile count)."""
+    the concatenated tensor.  The tile counts are worked out here so that the pinned split is one the kernels keep
+    (conv2d_wgrad_bx3.h clamps it to the tile count); the build and the split that ran are read back (pnsfm_conv2d_last_config)."""
     import ctypes
     import torch.nn.functional as F
     from packnet_sfm.hip import _lib, ops
@@ -1186,6 +1218,13 @@ def _check_wgrad_cat_pinned(device, case, kernel, tol):
     yr.backward(dy)
     try:
         dw, db = ops.conv2d_backward_weight_cat([t.to(device) for t in xs], dy.to(device), 3)
+        cfg_ran = ops.conv2d_last_config()
+        build = WC.launched_build(cfg_ran)
+        if kernel == 3:
+            assert build == (104, 2, TG, TR or build[3], 1 if W % 8 else 0) and build[3] in (4, 6), cfg_ran
+        else:
+            assert build == (103, 3, 1, 2 if Cout > 32 else 1, 16, 1 if W % 8 else 0, 2), cfg_ran
+        assert cfg_ran[4] == split, cfg_ran
         P.check(dw, wr.grad, tol, 'wgrad (cat, kernel %d)' % kernel)
         P.check(db, br.grad, tol, 'dbias (cat, kernel %d)' % kernel)
     finally:
