@@ -217,26 +217,17 @@ int pnsfm_set_gn_fused(int on);
  *   y[b][4c+2i+j][h][w] = x[b][c][2h+i][2w+j];  x:[B,C,H,W] -> y:[B,4C,H/2,W/2]
  * depth_to_space == nn.PixelShuffle(2) layers01.py:275,285:  x:[B,4C,H,W] -> y:[B,C,2H,2W]
  * Each is the other's backward. */
-int pnsfm_space_to_depth(const float* x, float* y, int B, int C, int H, int W, void* stream);
-/* same, for an x that is a channel slice of a wider tensor (image b starts at x + b*x_batch_stride floats): the
- * gradient that reaches PixelShuffle's backward through torch.cat((unpack, skip), 1) (PackNet01.py:140-172) */
-int pnsfm_space_to_depth_strided(const float* x, float* y, int B, int C, int H, int W, size_t x_batch_stride, void* stream);
+/* x may be a channel slice of a wider tensor: image b starts at x + b*x_batch_stride floats (C*H*W for a contiguous x).  That is the
+ * gradient that reaches PixelShuffle's backward through torch.cat((unpack, skip), 1) (PackNet01.py:140-172). */
+int pnsfm_space_to_depth(const float* x, float* y, int B, int C, int H, int W, size_t x_batch_stride, void* stream);
 int pnsfm_depth_to_space(const float* x, float* y, int B, int C, int H, int W, void* stream);
 
-/* ---- Conv3d(1 -> 8, 3x3x3, padding 1) over the (channel, y, x) volume ----------------------
+/* ---- Conv3d(1 -> NF, 3x3x3, padding 1) over the (channel, y, x) volume, NF = 4 or 8 ---------
  * replaces self.conv3d in PackLayerConv3d / UnpackLayerConv3d: layers01.py:236-237,241-245,
- * :276-277,280-284.  p:[B,D,H,W] (the unsqueezed single 3-D feature), out:[B,8*D,H,W] with
- * channel f*D+d (the `.view(b, c*d, h, w)` at :244-245).  w3:[8][27] (= [8,1,3,3,3]), b3:[8]. */
-int pnsfm_conv3d_1to8_forward(const float* p, const float* w3, const float* b3, float* out,
-                              int B, int D, int H, int W, void* stream);
-int pnsfm_conv3d_1to8_backward_data(const float* dout, const float* w3, float* dp,
-                                    int B, int D, int H, int W, void* stream);
-/* dw3:[8*27], db3:[8]; overwritten. ws: double[8*28] scratch. */
-int pnsfm_conv3d_1to8_backward_weight(const float* p, const float* dout, float* dw3, float* db3, double* ws,
-                                      int B, int D, int H, int W, void* stream);
-/* The same three with NF = 4 or 8 feature maps (`d=num_3d_feat` of PackLayerConv3d / UnpackLayerConv3d,
- * layers01.py:213-232,250-268: 8 in PackNet01, 4 in PackNetSlim01.py:39 and PackNetSAN01.py).  out / dout:[B,NF*D,H,W],
- * w3:[NF][27], b3:[NF] (forward: NULL = no bias); ws stays double[8*28]. */
+ * :276-277,280-284 (`d=num_3d_feat`, :213-232,250-268: 8 in PackNet01, 4 in PackNetSlim01.py:39 and PackNetSAN01.py).
+ * p:[B,D,H,W] (the unsqueezed single 3-D feature), out / dout:[B,NF*D,H,W] with channel f*D+d (the `.view(b, c*d, h, w)`
+ * at :244-245).  w3:[NF][27] (= [NF,1,3,3,3]), b3:[NF] (forward: NULL = no bias).
+ * backward_weight: dw3:[NF*27], db3:[NF]; overwritten.  ws: double[8*28] scratch. */
 int pnsfm_conv3d_forward(const float* p, const float* w3, const float* b3, float* out,
                          int B, int D, int H, int W, int NF, void* stream);
 int pnsfm_conv3d_backward_data(const float* dout, const float* w3, float* dp,
@@ -280,59 +271,42 @@ int pnsfm_supervised_loss_backward(const float* pred, const float* gt, const dou
  * replaces MultiViewPhotometricLoss.warp_ref_image for ONE scale and J context images:
  *   losses/multiview_photometric_loss.py:127-165, utils/depth.py:103-120 (inv2depth),
  *   geometry/camera.py:112-148 (reconstruct), :150-191 (project),
- *   geometry/camera_utils.py:27-59 (view_synthesis: bilinear, zeros, align_corners=True).
+ *   geometry/camera_utils.py:27-59 (view_synthesis: bilinear, align_corners=True).
  * inv_depth:[B,1,H,W]; ref:[J,B,3,H,W]; K, refK:[B,3,3] already scaled to this resolution;
- * T:[J,B,4,4] target->context rigid transforms (Pose.mat); warped:[J,B,3,H,W]. */
+ * T:[J,B,4,4] target->context rigid transforms (Pose.mat); warped:[J,B,3,H,W].
+ * padding_mode: grid_sample's (camera_utils.py:58-59, `padding_mode` of the loss config): 0 = 'zeros', 1 = 'border', 2 = 'reflection'.
+ * backward: d_inv_depth:[B,1,H,W] (sum over J, overwritten); dT:[J,B,4,4] (rows 0..2 filled, row 3 zero; the pose gradient is
+ * accumulated in fp64 in the stream's scratch buffer). */
 int pnsfm_view_synthesis_forward(const float* inv_depth, const float* ref, const float* K, const float* refK,
-                                 const float* T, float* warped, int J, int B, int H, int W, void* stream);
-/* d_inv_depth:[B,1,H,W] (sum over J, overwritten); dT:[J,B,4,4] (rows 0..2 filled, row 3 zero).
- * ws: double[J*B*12] scratch (fp64 accumulation of the pose gradient). */
+                                 const float* T, float* warped, int J, int B, int H, int W, int padding_mode, void* stream);
 int pnsfm_view_synthesis_backward(const float* d_warped, const float* inv_depth, const float* ref,
-                                  const float* K, const float* refK, const float* T,
-                                  float* d_inv_depth, float* dT, double* ws, int J, int B, int H, int W, void* stream);
-/* The same with grid_sample's other padding modes (camera_utils.py:58-59, `padding_mode` of the loss config):
- * padding_mode 0 = 'zeros' (the two entry points above), 1 = 'border', 2 = 'reflection' (align_corners=True). */
-int pnsfm_view_synthesis_forward_pad(const float* inv_depth, const float* ref, const float* K, const float* refK,
-                                     const float* T, float* warped, int J, int B, int H, int W, int padding_mode,
-                                     void* stream);
-int pnsfm_view_synthesis_backward_pad(const float* d_warped, const float* inv_depth, const float* ref,
-                                      const float* K, const float* refK, const float* T, float* d_inv_depth, float* dT,
-                                      double* ws, int J, int B, int H, int W, int padding_mode, void* stream);
+                                  const float* K, const float* refK, const float* T, float* d_inv_depth, float* dT,
+                                  int J, int B, int H, int W, int padding_mode, void* stream);
 
-/* ---- photometric loss of one scale: SSIM + L1, automask, min/mean reduce -------------------
+/* ---- photometric loss of one scale: SSIM + L1, automask, min/mean reduce, optional clipping ----
  * replaces SSIM() :14-53, MultiViewPhotometricLoss.SSIM :169-186, calc_photometric_loss :188-223
- * and the per-scale body of reduce_photometric_loss :225-253 (clip_loss > 0: the _clip variants below).
+ * and the per-scale body of reduce_photometric_loss :225-253.
  * Candidates per pixel, in the reference's order (:321-334): warped[0], ref[0], warped[1], ref[1], ...
- * (ref[j] entries only when automask != 0).  reduce_op: 0 = 'min', 1 = 'mean'.
- * loss_sum: double[1], receives sum over pixels of the reduced per-pixel loss (caller divides by B*H*W);
- * argmin: uint8[B*H*W] (candidate index chosen per pixel; written for reduce_op==0). */
-int pnsfm_photometric_forward(const float* warped, const float* ref, const float* target,
-                              double* loss_sum, uint8_t* argmin, int J, int B, int H, int W,
-                              float ssim_weight, float C1, float C2, int automask, int reduce_op, void* stream);
-/* d_warped:[J,B,3,H,W] = grad_scale * d(loss_sum)/d(warped), overwritten. */
-/* Variants that keep scalars on the device (round 4: no ATen launch between these kernels and autograd): forward_mean writes
- * loss_mean float[1] = loss_sum / (B*H*W); backward_dev multiplies grad_scale by upstream[0] (device scalar, nullable) and takes
- * clip = 0 | 1 (the byte layout of pnsfm_photometric_forward / _forward_clip). */
-int pnsfm_photometric_forward_mean(const float* warped, const float* ref, const float* target, float* loss_mean, uint8_t* argmin,
-                                   int J, int B, int H, int W, float ssim_weight, float C1, float C2, int automask, int reduce_op,
-                                   void* stream);
-int pnsfm_photometric_backward_dev(const float* warped, const float* target, const uint8_t* argmin, float* d_warped,
-                                   float grad_scale, const float* upstream /*nullable*/, int J, int B, int H, int W,
-                                   float ssim_weight, float C1, float C2, int automask, int reduce_op, int clip, void* stream);
-int pnsfm_photometric_backward(const float* warped, const float* target, const uint8_t* argmin,
-                               float* d_warped, float grad_scale, int J, int B, int H, int W,
-                               float ssim_weight, float C1, float C2, int automask, int reduce_op, void* stream);
-/* clip_loss > 0 (:214-219): every candidate map is clamped at mean + clip_loss * std of itself (torch.std: unbiased; the
- * threshold is a float in the reference, so no gradient flows through it).  Three launches: statistics pass, threshold
- * kernel, clamped pass.  stats_ws: double[12], thr_ws: float[6] scratch.  The per-pixel byte then also records clamping
- * (min: argmin | clamped << 7; mean: bit mask of clamped candidates) and MUST go to pnsfm_photometric_backward_clip. */
-int pnsfm_photometric_forward_clip(const float* warped, const float* ref, const float* target,
-                                   double* loss_sum, uint8_t* argmin, int J, int B, int H, int W,
-                                   float ssim_weight, float C1, float C2, int automask, int reduce_op,
-                                   float clip_loss, double* stats_ws, float* thr_ws, void* stream);
-int pnsfm_photometric_backward_clip(const float* warped, const float* target, const uint8_t* argmin,
-                                    float* d_warped, float grad_scale, int J, int B, int H, int W,
-                                    float ssim_weight, float C1, float C2, int automask, int reduce_op, void* stream);
+ * (ref[j] entries only when automask != 0; automask needs reduce_op 0).  reduce_op: 0 = 'min', 1 = 'mean'.  J <= 3; H, W >= 3.
+ * The scalar, either or both (not both null), with no ATen launch between these kernels and autograd:
+ *   loss_sum: double[1] = sum over pixels of the reduced per-pixel loss (the caller divides by B*H*W);
+ *   loss_mean: float[1] = that sum times 1 / (B*H*W).
+ * clip_loss > 0 (:214-219; <= 0: off): every candidate map is clamped at mean + clip_loss * std of itself (torch.std: unbiased;
+ * the threshold is a float in the reference, so no gradient flows through it): a statistics pass and a threshold kernel run in
+ * front of the clamped pass, their sums and thresholds in the stream's scratch buffer.
+ * ssim_weight > 0; ssim_weight == 0 (the reference's L1-only loss) only with reduce_op 1 and no clipping, where its per-channel
+ * maps coincide with this kernel's channel mean (otherwise: pnsfm_photometric_l1_forward).
+ * argmin: uint8[B*H*W], one byte per pixel for backward:
+ *   without clipping: the candidate index chosen (written for reduce_op 0 only);
+ *   with clipping:    reduce_op 0: candidate index | clamped << 7;  reduce_op 1: bit mask of the clamped candidates. */
+int pnsfm_photometric_forward(const float* warped, const float* ref, const float* target, double* loss_sum /*nullable*/,
+                              float* loss_mean /*nullable*/, uint8_t* argmin, int J, int B, int H, int W, float ssim_weight,
+                              float C1, float C2, int automask, int reduce_op, float clip_loss, void* stream);
+/* d_warped:[J,B,3,H,W] = grad_scale * upstream[0] * d(loss_sum)/d(warped), overwritten.  upstream: device scalar, null = 1.
+ * clip = 0 | 1 names the layout of the argmin bytes above: 1 when the forward call ran with clip_loss > 0. */
+int pnsfm_photometric_backward(const float* warped, const float* target, const uint8_t* argmin, float* d_warped,
+                               float grad_scale, const float* upstream /*nullable*/, int J, int B, int H, int W,
+                               float ssim_weight, float C1, float C2, int automask, int reduce_op, int clip, void* stream);
 
 /* ---- edge-aware smoothness of one scale ------------------------------------------------------
  * replaces calc_smoothness utils/depth.py:165-198 (after inv_depths_normalize :146-162) with

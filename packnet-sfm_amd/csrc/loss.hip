@@ -873,9 +873,8 @@ using namespace pnsfm;
 
 extern "C" {
 
-int pnsfm_view_synthesis_forward_pad(const float* inv_depth, const float* ref, const float* K, const float* refK,
-                                     const float* T, float* warped, int J, int B, int H, int W, int padding_mode,
-                                     void* stream) {
+int pnsfm_view_synthesis_forward(const float* inv_depth, const float* ref, const float* K, const float* refK, const float* T,
+                                 float* warped, int J, int B, int H, int W, int padding_mode, void* stream) {
   if (J < 1 || B < 1 || H < 2 || W < 2) { set_error("view_synthesis_forward: bad shape"); return -1; }
   if (padding_mode < 0 || padding_mode > 2) { set_error("view_synthesis_forward: padding_mode must be 0 (zeros), 1 (border) or 2 (reflection)"); return -1; }
   dim3 grid(ceil_div(H * W, 256), B, J);
@@ -884,26 +883,14 @@ int pnsfm_view_synthesis_forward_pad(const float* inv_depth, const float* ref, c
   return check_launch("view_synthesis_forward");
 }
 
-int pnsfm_view_synthesis_forward(const float* inv_depth, const float* ref, const float* K, const float* refK, const float* T,
-                                 float* warped, int J, int B, int H, int W, void* stream) {
-  return pnsfm_view_synthesis_forward_pad(inv_depth, ref, K, refK, T, warped, J, B, H, W, 0, stream);
-}
-
 int pnsfm_view_synthesis_backward(const float* d_warped, const float* inv_depth, const float* ref, const float* K,
-                                  const float* refK, const float* T, float* d_inv_depth, float* dT, double* ws, int J, int B,
-                                  int H, int W, void* stream) {
-  return pnsfm_view_synthesis_backward_pad(d_warped, inv_depth, ref, K, refK, T, d_inv_depth, dT, ws, J, B, H, W, 0, stream);
-}
-
-int pnsfm_view_synthesis_backward_pad(const float* d_warped, const float* inv_depth, const float* ref, const float* K,
-                                      const float* refK, const float* T, float* d_inv_depth, float* dT, double* ws, int J,
-                                      int B, int H, int W, int padding_mode, void* stream) {
+                                  const float* refK, const float* T, float* d_inv_depth, float* dT, int J, int B, int H, int W,
+                                  int padding_mode, void* stream) {
   if (J < 1 || B < 1 || H < 2 || W < 2) { set_error("view_synthesis_backward: bad shape"); return -1; }
   if (padding_mode < 0 || padding_mode > 2) { set_error("view_synthesis_backward: bad padding_mode"); return -1; }
   hipStream_t s = (hipStream_t)stream;
-  (void)ws;     // (round 3's zero-filled atomics target; the per-block partials now live in the stream's scratch buffer)
   dim3 grid(ceil_div(H * W, 256), B);
-  ScratchLease lease(s, (size_t)J * B * grid.x * 12 * sizeof(double));
+  ScratchLease lease(s, (size_t)J * B * grid.x * 12 * sizeof(double));      // per-block partials of the pose gradient
   double* const part = lease.as<double>();
   if (!part) return -1;
   PNSFM_LAUNCH(view_synthesis_bwd_kernel, grid, dim3(256), 0, s, d_warped, inv_depth, ref, K, refK, T, d_inv_depth, part, J, B,
@@ -927,80 +914,58 @@ __global__ void photometric_clip_finish_kernel(const double* __restrict__ stats,
 
 // per-workgroup partial sums of a two-stage reduction live in the stream's scratch buffer (api.hip: ScratchLease)
 
-int pnsfm_photometric_forward_clip(const float* warped, const float* ref, const float* target, double* loss_sum,
-                                   uint8_t* argmin, int J, int B, int H, int W, float ssim_weight, float C1, float C2,
-                                   int automask, int reduce_op, float clip_loss, double* stats_ws, float* thr_ws, void* stream) {
+int pnsfm_photometric_forward(const float* warped, const float* ref, const float* target, double* loss_sum, float* loss_mean,
+                              uint8_t* argmin, int J, int B, int H, int W, float ssim_weight, float C1, float C2, int automask,
+                              int reduce_op, float clip_loss, void* stream) {
+  if (!loss_sum && !loss_mean) { set_error("photometric_forward: loss_sum and loss_mean are both null"); return -1; }
   if (J < 1 || J > 3 || H < 3 || W < 3) { set_error("photometric_forward: bad shape (J=%d H=%d W=%d; J<=3)", J, H, W); return -1; }
-  if (!(ssim_weight > 0.f)) { set_error("photometric_forward: ssim_weight must be > 0"); return -1; }
-  if (automask && reduce_op != 0) { set_error("photometric_forward: automask requires the 'min' reduce op"); return -1; }
-  if (!(clip_loss > 0.f) || !stats_ws || !thr_ws) { set_error("photometric_forward_clip: clip_loss must be > 0 with scratch buffers"); return -1; }
-  hipStream_t s = (hipStream_t)stream;
-  const int ncand = J * (automask ? 2 : 1);
-  int e = (int)hipMemsetAsync(stats_ws, 0, 12 * sizeof(double), s);
-  if (e) { set_error("photometric_forward: memset failed"); return e; }
-  dim3 grid(ceil_div(W, PH_T), ceil_div(H, PH_T), B);
-  const int nblk = (int)(grid.x * grid.y * grid.z);
-  ScratchLease lease(s, (size_t)nblk * sizeof(double));
-  double* part = lease.as<double>();
-  if (!part) return -1;
-  const size_t smem = (size_t)(1 + 2 * J) * 3 * PH_S1 * PH_S1 * sizeof(float);
-  PNSFM_LAUNCH(photometric_fwd_kernel, grid, dim3(256), smem, s, warped, ref, target, part, argmin, J, B, H, W, ssim_weight,
-               C1, C2, automask, reduce_op, (const float*)nullptr, stats_ws);
-  PNSFM_LAUNCH(photometric_clip_finish_kernel, dim3(1), dim3(64), 0, s, (const double*)stats_ws, thr_ws, ncand,
-               (double)B * H * W, clip_loss);
-  PNSFM_LAUNCH(photometric_fwd_kernel, grid, dim3(256), smem, s, warped, ref, target, part, argmin, J, B, H, W, ssim_weight,
-               C1, C2, automask, reduce_op, (const float*)thr_ws, (double*)nullptr);
-  PNSFM_LAUNCH(sum_partials_kernel, dim3(1), dim3(256), 0, s, (const double*)part, nblk, 1, loss_sum);
-  return check_launch("photometric_forward_clip");
-}
-
-int pnsfm_photometric_forward(const float* warped, const float* ref, const float* target, double* loss_sum, uint8_t* argmin,
-                              int J, int B, int H, int W, float ssim_weight, float C1, float C2, int automask, int reduce_op,
-                              void* stream) {
-  if (J < 1 || J > 3 || H < 3 || W < 3) { set_error("photometric_forward: bad shape (J=%d H=%d W=%d; J<=3)", J, H, W); return -1; }
+  const bool clip = clip_loss > 0.f;
   // ssim_weight == 0 is the reference's L1-only loss, whose per-CHANNEL maps only coincide with this kernel's channel
   // mean under the 'mean' reduce without clipping (multiview_photometric_loss.py:205-219, 238-246)
-  if (!(ssim_weight >= 0.f) || (ssim_weight == 0.f && reduce_op == 0)) {
-    set_error("photometric_forward: ssim_weight must be > 0 (or == 0 with the 'mean' reduce op)");
+  if (clip ? !(ssim_weight > 0.f) : (!(ssim_weight >= 0.f) || (ssim_weight == 0.f && reduce_op == 0))) {
+    set_error("photometric_forward: ssim_weight must be > 0 (or == 0 with the 'mean' reduce op and no clipping)");
     return -1;
   }
   if (automask && reduce_op != 0) { set_error("photometric_forward: automask requires the 'min' reduce op"); return -1; }
   hipStream_t s = (hipStream_t)stream;
   dim3 grid(ceil_div(W, PH_T), ceil_div(H, PH_T), B);
   const int nblk = (int)(grid.x * grid.y * grid.z);
-  ScratchLease lease(s, (size_t)nblk * sizeof(double));
+  // scratch: [nblk] loss partials | clipping: [6][2] candidate statistics | [6] thresholds
+  ScratchLease lease(s, ((size_t)nblk + (clip ? 12 + 3 : 0)) * sizeof(double));
   double* part = lease.as<double>();
   if (!part) return -1;
   const size_t smem = (size_t)(1 + 2 * J) * 3 * PH_S1 * PH_S1 * sizeof(float);
+  const float* thr = nullptr;
+  if (clip) {      // statistics pass (fp64 atomics into zeroed sums), thresholds; the main pass below then clamps
+    double* const stats = part + nblk;
+    float* const thr_w = reinterpret_cast<float*>(stats + 12);
+    int e = (int)hipMemsetAsync(stats, 0, 12 * sizeof(double), s);
+    if (e) { set_error("photometric_forward: memset failed"); return e; }
+    PNSFM_LAUNCH(photometric_fwd_kernel, grid, dim3(256), smem, s, warped, ref, target, part, argmin, J, B, H, W, ssim_weight,
+                 C1, C2, automask, reduce_op, (const float*)nullptr, stats);
+    PNSFM_LAUNCH(photometric_clip_finish_kernel, dim3(1), dim3(64), 0, s, (const double*)stats, thr_w, J * (automask ? 2 : 1),
+                 (double)B * H * W, clip_loss);
+    thr = thr_w;
+  }
   PNSFM_LAUNCH(photometric_fwd_kernel, grid, dim3(256), smem, s, warped, ref, target, part, argmin, J, B, H, W, ssim_weight,
-               C1, C2, automask, reduce_op, (const float*)nullptr, (double*)nullptr);
-  PNSFM_LAUNCH(sum_partials_kernel, dim3(1), dim3(256), 0, s, (const double*)part, nblk, 1, loss_sum);
+               C1, C2, automask, reduce_op, thr, (double*)nullptr);
+  if (loss_mean)
+    PNSFM_LAUNCH(sum_partials_scaled_kernel, dim3(1), dim3(256), 0, s, (const double*)part, nblk, 1, 1.0 / ((double)B * H * W), 0.0,
+                 loss_sum, loss_mean);
+  else
+    PNSFM_LAUNCH(sum_partials_kernel, dim3(1), dim3(256), 0, s, (const double*)part, nblk, 1, loss_sum);
   return check_launch("photometric_forward");
 }
 
-static int photometric_backward_impl(const float* warped, const float* target, const uint8_t* argmin, float* d_warped,
-                                     float grad_scale, int J, int B, int H, int W, float ssim_weight, float C1, float C2,
-                                     int automask, int reduce_op, int clip, void* stream, const float* gdev = nullptr) {
+int pnsfm_photometric_backward(const float* warped, const float* target, const uint8_t* argmin, float* d_warped,
+                               float grad_scale, const float* upstream, int J, int B, int H, int W, float ssim_weight, float C1,
+                               float C2, int automask, int reduce_op, int clip, void* stream) {
   if (J < 1 || J > 3 || H < 3 || W < 3) { set_error("photometric_backward: bad shape (J<=3)"); return -1; }
   dim3 grid(ceil_div(W, PH_T), ceil_div(H, PH_T), B);
   const size_t smem = ((size_t)(1 + J) * 3 * PH_S2 * PH_S2 + (size_t)J * 9 * PH_S1 * PH_S1) * sizeof(float);
   PNSFM_LAUNCH(photometric_bwd_kernel, grid, dim3(256), smem, (hipStream_t)stream, warped, target, argmin, d_warped,
-               grad_scale, J, B, H, W, ssim_weight, C1, C2, automask, reduce_op, clip, gdev);
+               grad_scale, J, B, H, W, ssim_weight, C1, C2, automask, reduce_op, clip ? 1 : 0, upstream);
   return check_launch("photometric_backward");
-}
-
-int pnsfm_photometric_backward(const float* warped, const float* target, const uint8_t* argmin, float* d_warped,
-                               float grad_scale, int J, int B, int H, int W, float ssim_weight, float C1, float C2,
-                               int automask, int reduce_op, void* stream) {
-  return photometric_backward_impl(warped, target, argmin, d_warped, grad_scale, J, B, H, W, ssim_weight, C1, C2, automask,
-                                   reduce_op, 0, stream);
-}
-
-int pnsfm_photometric_backward_clip(const float* warped, const float* target, const uint8_t* argmin, float* d_warped,
-                                    float grad_scale, int J, int B, int H, int W, float ssim_weight, float C1, float C2,
-                                    int automask, int reduce_op, void* stream) {
-  return photometric_backward_impl(warped, target, argmin, d_warped, grad_scale, J, B, H, W, ssim_weight, C1, C2, automask,
-                                   reduce_op, 1, stream);
 }
 
 int pnsfm_smoothness_forward(const float* inv_norm, const float* image, double* sums, int B, int H, int W, void* stream) {
@@ -1013,36 +978,6 @@ int pnsfm_smoothness_forward(const float* inv_norm, const float* image, double* 
   PNSFM_LAUNCH(smoothness_fwd_kernel, grid, dim3(256), 0, s, inv_norm, image, part, H, W);
   PNSFM_LAUNCH(sum_partials_kernel, dim3(1), dim3(256), 0, s, (const double*)part, nblk, 2, sums);
   return check_launch("smoothness_forward");
-}
-
-int pnsfm_photometric_forward_mean(const float* warped, const float* ref, const float* target, float* loss_mean, uint8_t* argmin,
-                                   int J, int B, int H, int W, float ssim_weight, float C1, float C2, int automask, int reduce_op,
-                                   void* stream) {
-  if (J < 1 || J > 3 || H < 3 || W < 3) { set_error("photometric_forward: bad shape (J=%d H=%d W=%d; J<=3)", J, H, W); return -1; }
-  if (!(ssim_weight >= 0.f) || (ssim_weight == 0.f && reduce_op == 0)) {
-    set_error("photometric_forward: ssim_weight must be > 0 (or == 0 with the 'mean' reduce op)");
-    return -1;
-  }
-  if (automask && reduce_op != 0) { set_error("photometric_forward: automask requires the 'min' reduce op"); return -1; }
-  hipStream_t s = (hipStream_t)stream;
-  dim3 grid(ceil_div(W, PH_T), ceil_div(H, PH_T), B);
-  const int nblk = (int)(grid.x * grid.y * grid.z);
-  ScratchLease lease(s, (size_t)nblk * sizeof(double));
-  double* part = lease.as<double>();
-  if (!part) return -1;
-  const size_t smem = (size_t)(1 + 2 * J) * 3 * PH_S1 * PH_S1 * sizeof(float);
-  PNSFM_LAUNCH(photometric_fwd_kernel, grid, dim3(256), smem, s, warped, ref, target, part, argmin, J, B, H, W, ssim_weight,
-               C1, C2, automask, reduce_op, (const float*)nullptr, (double*)nullptr);
-  PNSFM_LAUNCH(sum_partials_scaled_kernel, dim3(1), dim3(256), 0, s, (const double*)part, nblk, 1, 1.0 / ((double)B * H * W), 0.0,
-               (double*)nullptr, loss_mean);
-  return check_launch("photometric_forward_mean");
-}
-
-int pnsfm_photometric_backward_dev(const float* warped, const float* target, const uint8_t* argmin, float* d_warped,
-                                   float grad_scale, const float* upstream, int J, int B, int H, int W, float ssim_weight, float C1,
-                                   float C2, int automask, int reduce_op, int clip, void* stream) {
-  return photometric_backward_impl(warped, target, argmin, d_warped, grad_scale, J, B, H, W, ssim_weight, C1, C2, automask,
-                                   reduce_op, clip ? 1 : 0, stream, upstream);
 }
 
 int pnsfm_photometric_l1_forward(const float* warped, const float* ref, const float* target, float* loss_mean, int* rec, int J, int B,

@@ -635,7 +635,7 @@ using namespace pnsfm;
 
 extern "C" {
 
-int pnsfm_space_to_depth_strided(const float* x, float* y, int B, int C, int H, int W, size_t x_batch_stride, void* stream) {
+int pnsfm_space_to_depth(const float* x, float* y, int B, int C, int H, int W, size_t x_batch_stride, void* stream) {
   if ((H & 1) || (W & 1)) { set_error("space_to_depth: H, W must be even (got %d x %d)", H, W); return -1; }
   if (x_batch_stride < (size_t)C * H * W) { set_error("space_to_depth: batch stride smaller than one image"); return -1; }
   const size_t total = (size_t)B * C * H * W;
@@ -647,10 +647,6 @@ int pnsfm_space_to_depth_strided(const float* x, float* y, int B, int C, int H, 
     PNSFM_LAUNCH(s2d_kernel<float>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, x, y, C, H, W, total, x_batch_stride);
   }
   return check_launch("space_to_depth");
-}
-
-int pnsfm_space_to_depth(const float* x, float* y, int B, int C, int H, int W, void* stream) {
-  return pnsfm_space_to_depth_strided(x, y, B, C, H, W, (size_t)C * H * W, stream);
 }
 
 int pnsfm_depth_to_space(const float* x, float* y, int B, int C, int H, int W, void* stream) {
@@ -767,19 +763,6 @@ int pnsfm_conv3d_backward_weight(const float* p, const float* dout, float* dw3, 
   PNSFM_LAUNCH(conv3d_wgrad_finish_kernel, dim3(NF * 28), dim3(64), 0, s, (const float*)part, dw3, db3, (int)(grid.x * grid.z),
                (int)grid.y, fpb);
   return check_launch("conv3d_backward_weight_finish");
-}
-
-// PackNet01's fixed d = 8 (the original entry points)
-int pnsfm_conv3d_1to8_forward(const float* p, const float* w3, const float* b3, float* out, int B, int D, int H, int W,
-                              void* stream) {
-  return pnsfm_conv3d_forward(p, w3, b3, out, B, D, H, W, 8, stream);
-}
-int pnsfm_conv3d_1to8_backward_data(const float* dout, const float* w3, float* dp, int B, int D, int H, int W, void* stream) {
-  return pnsfm_conv3d_backward_data(dout, w3, dp, B, D, H, W, 8, stream);
-}
-int pnsfm_conv3d_1to8_backward_weight(const float* p, const float* dout, float* dw3, float* db3, double* ws, int B, int D,
-                                      int H, int W, void* stream) {
-  return pnsfm_conv3d_backward_weight(p, dout, dw3, db3, ws, B, D, H, W, 8, stream);
 }
 
 }  // extern "C"

@@ -42,12 +42,8 @@ SIGNATURES = {
     "pnsfm_groupnorm_act_forward": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _i, _p]),
     "pnsfm_groupnorm_act_backward": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "pnsfm_set_gn_fused": (_i, [_i]),
-    "pnsfm_space_to_depth": (_i, [_p, _p, _i, _i, _i, _i, _p]),
-    "pnsfm_space_to_depth_strided": (_i, [_p, _p, _i, _i, _i, _i, _sz, _p]),
+    "pnsfm_space_to_depth": (_i, [_p, _p, _i, _i, _i, _i, _sz, _p]),
     "pnsfm_depth_to_space": (_i, [_p, _p, _i, _i, _i, _i, _p]),
-    "pnsfm_conv3d_1to8_forward": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
-    "pnsfm_conv3d_1to8_backward_data": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
-    "pnsfm_conv3d_1to8_backward_weight": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "pnsfm_conv3d_forward": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "pnsfm_conv3d_backward_data": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "pnsfm_conv3d_backward_weight": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
@@ -65,16 +61,10 @@ SIGNATURES = {
     "pnsfm_supervised_loss_backward": (_i, [_p, _p, _p, _p, _p, _sz, _i, _i, _p]),
     "pnsfm_invdepth_conv_forward": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _f, _p]),
     "pnsfm_invdepth_conv_backward": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
-    "pnsfm_view_synthesis_forward": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
-    "pnsfm_view_synthesis_backward": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
-    "pnsfm_view_synthesis_forward_pad": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
-    "pnsfm_view_synthesis_backward_pad": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
-    "pnsfm_photometric_forward": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _f, _i, _i, _p]),
-    "pnsfm_photometric_backward": (_i, [_p, _p, _p, _p, _f, _i, _i, _i, _i, _f, _f, _f, _i, _i, _p]),
-    "pnsfm_photometric_forward_clip": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _f, _i, _i, _f, _p, _p, _p]),
-    "pnsfm_photometric_backward_clip": (_i, [_p, _p, _p, _p, _f, _i, _i, _i, _i, _f, _f, _f, _i, _i, _p]),
-    "pnsfm_photometric_forward_mean": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _f, _i, _i, _p]),
-    "pnsfm_photometric_backward_dev": (_i, [_p, _p, _p, _p, _f, _p, _i, _i, _i, _i, _f, _f, _f, _i, _i, _i, _p]),
+    "pnsfm_view_synthesis_forward": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "pnsfm_view_synthesis_backward": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "pnsfm_photometric_forward": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _f, _i, _i, _f, _p]),
+    "pnsfm_photometric_backward": (_i, [_p, _p, _p, _p, _f, _p, _i, _i, _i, _i, _f, _f, _f, _i, _i, _i, _p]),
     "pnsfm_smoothness_norm_forward": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
     "pnsfm_smoothness_norm_backward": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "pnsfm_region_ops": (_i, [_p, _i, _p]),

@@ -1551,7 +1551,7 @@ class PhotometricFn(Function):
             loss_sum, argmin = ops.photometric_forward(warped, ref, target, ssim_w, C1, C2, automask, reduce_op, clip_loss)
             ctx.save_for_backward(warped, target, argmin)
             return (loss_sum / float(B * H * W)).to(torch.float32).reshape(())
-        loss, argmin = ops.photometric_forward_mean(warped, ref, target, ssim_w, C1, C2, automask, reduce_op)
+        loss, argmin = ops.photometric_forward(warped, ref, target, ssim_w, C1, C2, automask, reduce_op)
         ctx.save_for_backward(warped, target, argmin)
         return loss.reshape(())
 
@@ -1561,7 +1561,7 @@ class PhotometricFn(Function):
         warped, target, argmin = ctx.saved_tensors
         ssim_w, C1, C2, automask, reduce_op, n, clip = ctx.meta
         up = g.reshape(1).to(torch.float32).contiguous()
-        d = ops.photometric_backward_dev(warped, target, argmin, 1.0 / n, up, ssim_w, C1, C2, automask, reduce_op, clip)
+        d = ops.photometric_backward(warped, target, argmin, 1.0 / n, up, ssim_w, C1, C2, automask, reduce_op, clip)
         return d, None, None, None, None, None, None, None, None
 
 

@@ -344,8 +344,8 @@ def space_to_depth(x):
     _chk(y := torch.empty((B, 4 * C, H // 2, W // 2), dtype=torch.float32, device=x.device)); _f32(x)
     if _lib.REQUIRE_CUDA and not x.is_cuda:
         raise RuntimeError("packnet_sfm HIP op got a %s tensor: the HIP kernels run on MI355X only" % x.device)
-    _lib.check(_lib.get().pnsfm_space_to_depth_strided(_ptr(x), _ptr(y), B, C, H, W, x.stride(0) if B > 1 else C * H * W,
-                                                       _stream(x)), "space_to_depth")
+    _lib.check(_lib.get().pnsfm_space_to_depth(_ptr(x), _ptr(y), B, C, H, W, x.stride(0) if B > 1 else C * H * W, _stream(x)),
+               "space_to_depth")
     return y
 
 
@@ -538,8 +538,8 @@ def view_synthesis_forward(inv_depth, ref, K, refK, T, padding_mode=0):
     _chk(inv_depth, ref, K, refK, T); _f32(inv_depth, ref, K, refK, T)
     J, B, _, H, W = ref.shape
     warped = torch.empty_like(ref)
-    _lib.check(_lib.get().pnsfm_view_synthesis_forward_pad(_ptr(inv_depth), _ptr(ref), _ptr(K), _ptr(refK), _ptr(T), _ptr(warped),
-                                                           J, B, H, W, int(padding_mode), _stream(ref)), "view_synthesis_forward")
+    _lib.check(_lib.get().pnsfm_view_synthesis_forward(_ptr(inv_depth), _ptr(ref), _ptr(K), _ptr(refK), _ptr(T), _ptr(warped),
+                                                       J, B, H, W, int(padding_mode), _stream(ref)), "view_synthesis_forward")
     return warped
 
 
@@ -548,67 +548,42 @@ def view_synthesis_backward(d_warped, inv_depth, ref, K, refK, T, padding_mode=0
     J, B, _, H, W = ref.shape
     d_inv = torch.empty_like(inv_depth)
     dT = torch.empty_like(T)
-    ws = torch.empty((J * B * 12,), dtype=torch.float64, device=ref.device)
-    _lib.check(_lib.get().pnsfm_view_synthesis_backward_pad(_ptr(d_warped), _ptr(inv_depth), _ptr(ref), _ptr(K), _ptr(refK),
-                                                            _ptr(T), _ptr(d_inv), _ptr(dT), _ptr(ws), J, B, H, W,
-                                                            int(padding_mode), _stream(ref)), "view_synthesis_backward")
+    _lib.check(_lib.get().pnsfm_view_synthesis_backward(_ptr(d_warped), _ptr(inv_depth), _ptr(ref), _ptr(K), _ptr(refK), _ptr(T),
+                                                        _ptr(d_inv), _ptr(dT), J, B, H, W, int(padding_mode), _stream(ref)),
+               "view_synthesis_backward")
     return d_inv, dT
 
 
+def _upstream_ptr(upstream):
+    """the optional float32 device scalar that a backward kernel multiplies its gradient by (None: null pointer = 1)"""
+    _chk(upstream); _f32(upstream)
+    return _ptr(upstream)
+
+
 def photometric_forward(warped, ref, target, ssim_weight, C1, C2, automask, reduce_op, clip_loss=0.0):
-    """-> (loss_sum float64[1], argmin uint8[B,H,W]).  clip_loss > 0: candidates clamped at mean + clip_loss*std."""
+    """-> (loss, argmin uint8[B,H,W]).  loss: float32[1] = pixel mean of the reduced photometric map; with clip_loss > 0 (candidates
+    clamped at mean + clip_loss*std) float64[1] = its pixel SUM, which the caller divides."""
     _chk(warped, ref, target); _f32(warped, ref, target)
     J, B, _, H, W = warped.shape
-    loss_sum = torch.empty((1,), dtype=torch.float64, device=warped.device)
+    clip = clip_loss > 0.0
+    loss = torch.empty((1,), dtype=torch.float64 if clip else torch.float32, device=warped.device)
     argmin = torch.empty((B, H, W), dtype=torch.uint8, device=warped.device)
-    if clip_loss > 0.0:
-        stats = torch.empty((12,), dtype=torch.float64, device=warped.device)
-        thr = torch.empty((6,), dtype=torch.float32, device=warped.device)
-        _lib.check(_lib.get().pnsfm_photometric_forward_clip(
-            _ptr(warped), _ptr(ref), _ptr(target), _ptr(loss_sum), _ptr(argmin), J, B, H, W, float(ssim_weight), float(C1),
-            float(C2), int(automask), int(reduce_op), float(clip_loss), _ptr(stats), _ptr(thr), _stream(warped)),
-            "photometric_forward_clip")
-        return loss_sum, argmin
-    _lib.check(_lib.get().pnsfm_photometric_forward(_ptr(warped), _ptr(ref), _ptr(target), _ptr(loss_sum), _ptr(argmin), J, B, H,
-                                                    W, float(ssim_weight), float(C1), float(C2), int(automask), int(reduce_op),
+    _lib.check(_lib.get().pnsfm_photometric_forward(_ptr(warped), _ptr(ref), _ptr(target), _ptr(loss if clip else None),
+                                                    _ptr(None if clip else loss), _ptr(argmin), J, B, H, W, float(ssim_weight),
+                                                    float(C1), float(C2), int(automask), int(reduce_op), float(clip_loss),
                                                     _stream(warped)), "photometric_forward")
-    return loss_sum, argmin
-
-
-def photometric_backward(warped, target, argmin, grad_scale, ssim_weight, C1, C2, automask, reduce_op, clip=False):
-    _chk(warped, target, argmin); _f32(warped, target)
-    J, B, _, H, W = warped.shape
-    d_warped = torch.empty_like(warped)
-    fn = _lib.get().pnsfm_photometric_backward_clip if clip else _lib.get().pnsfm_photometric_backward
-    _lib.check(fn(_ptr(warped), _ptr(target), _ptr(argmin), _ptr(d_warped), float(grad_scale),
-                                                     J, B, H, W, float(ssim_weight), float(C1), float(C2), int(automask),
-                                                     int(reduce_op), _stream(warped)), "photometric_backward")
-    return d_warped
-
-
-def photometric_forward_mean(warped, ref, target, ssim_weight, C1, C2, automask, reduce_op):
-    """-> (loss float32[1] = pixel mean of the reduced photometric map, argmin uint8[B,H,W]); no clipping."""
-    _chk(warped, ref, target); _f32(warped, ref, target)
-    J, B, _, H, W = warped.shape
-    loss = torch.empty((1,), dtype=torch.float32, device=warped.device)
-    argmin = torch.empty((B, H, W), dtype=torch.uint8, device=warped.device)
-    _lib.check(_lib.get().pnsfm_photometric_forward_mean(_ptr(warped), _ptr(ref), _ptr(target), _ptr(loss), _ptr(argmin), J, B, H, W,
-                                                         float(ssim_weight), float(C1), float(C2), int(automask), int(reduce_op),
-                                                         _stream(warped)), "photometric_forward_mean")
     return loss, argmin
 
 
-def photometric_backward_dev(warped, target, argmin, grad_scale, upstream, ssim_weight, C1, C2, automask, reduce_op, clip=False):
+def photometric_backward(warped, target, argmin, grad_scale, upstream, ssim_weight, C1, C2, automask, reduce_op, clip=False):
     """d_warped = grad_scale * upstream[0] * d(loss_sum)/d(warped); `upstream`: float32 device scalar (or None)."""
     _chk(warped, target, argmin); _f32(warped, target)
-    if upstream is not None:
-        _chk(upstream); _f32(upstream)
     J, B, _, H, W = warped.shape
     d_warped = torch.empty_like(warped)
-    _lib.check(_lib.get().pnsfm_photometric_backward_dev(_ptr(warped), _ptr(target), _ptr(argmin), _ptr(d_warped), float(grad_scale),
-                                                         _ptr(upstream), J, B, H, W, float(ssim_weight), float(C1), float(C2),
-                                                         int(automask), int(reduce_op), int(bool(clip)), _stream(warped)),
-               "photometric_backward_dev")
+    _lib.check(_lib.get().pnsfm_photometric_backward(_ptr(warped), _ptr(target), _ptr(argmin), _ptr(d_warped), float(grad_scale),
+                                                     _upstream_ptr(upstream), J, B, H, W, float(ssim_weight), float(C1), float(C2),
+                                                     int(automask), int(reduce_op), int(bool(clip)), _stream(warped)),
+               "photometric_backward")
     return d_warped
 
 
@@ -626,12 +601,11 @@ def photometric_l1_forward(warped, ref, target, automask, reduce_op, clip_loss):
 
 def photometric_l1_backward(warped, target, rec, grad_scale, upstream, automask, reduce_op):
     _chk(warped, target, rec); _f32(warped, target)
-    if upstream is not None:
-        _chk(upstream); _f32(upstream)
     J, B, _, H, W = warped.shape
     d_warped = torch.empty_like(warped)
     _lib.check(_lib.get().pnsfm_photometric_l1_backward(_ptr(warped), _ptr(target), _ptr(rec), _ptr(d_warped), float(grad_scale),
-                                                        _ptr(upstream), J, B, H, W, int(automask), int(reduce_op), _stream(warped)),
+                                                        _upstream_ptr(upstream), J, B, H, W, int(automask), int(reduce_op),
+                                                        _stream(warped)),
                "photometric_l1_backward")
     return d_warped
 
@@ -649,12 +623,10 @@ def smoothness_norm_forward(inv_depth, image):
 
 def smoothness_norm_backward(inv_depth, image, mean, upstream):
     _chk(inv_depth, image, mean); _f32(inv_depth, image, mean)
-    if upstream is not None:
-        _chk(upstream); _f32(upstream)
     B, _, H, W = image.shape
     d = torch.empty_like(inv_depth)
-    _lib.check(_lib.get().pnsfm_smoothness_norm_backward(_ptr(inv_depth), _ptr(image), _ptr(mean), _ptr(upstream), _ptr(d), B, H, W,
-                                                         _stream(image)), "smoothness_norm_backward")
+    _lib.check(_lib.get().pnsfm_smoothness_norm_backward(_ptr(inv_depth), _ptr(image), _ptr(mean), _upstream_ptr(upstream), _ptr(d),
+                                                         B, H, W, _stream(image)), "smoothness_norm_backward")
     return d
 
 

@@ -100,6 +100,22 @@ def test_loss_golden(name):
     P.case_loss(name, DEV)
 
 
+def test_photometric_backward_null_upstream():
+    P.case_photometric_backward_null_upstream(DEV)
+
+
+def test_photometric_forward_sum_and_mean():
+    P.case_photometric_forward_sum_and_mean(DEV)
+
+
+def test_photometric_forward_null_outputs():
+    P.case_photometric_forward_null_outputs(DEV)
+
+
+def test_photometric_clip_repeatable():
+    P.case_photometric_clip_repeatable(DEV)
+
+
 def test_packnet01_golden():
     P.case_packnet01(DEV)
 

@@ -103,6 +103,22 @@ def test_loss(emulated_kernels, name):
     P.case_loss(name, 'cpu')
 
 
+def test_photometric_backward_null_upstream(emulated_kernels):
+    P.case_photometric_backward_null_upstream('cpu')
+
+
+def test_photometric_forward_sum_and_mean(emulated_kernels):
+    P.case_photometric_forward_sum_and_mean('cpu')
+
+
+def test_photometric_forward_null_outputs(emulated_kernels):
+    P.case_photometric_forward_null_outputs('cpu')
+
+
+def test_photometric_clip_repeatable(emulated_kernels):
+    P.case_photometric_clip_repeatable('cpu')
+
+
 def test_region_ops_batched_windows(emulated_kernels):
     P.case_region_ops('cpu')
 
