@@ -498,6 +498,33 @@ int pnsfm_invdepth_conv_forward_h16(const void* x, const void* w, const void* bi
                                     void* stream);
 int pnsfm_region_ops_h16(const void* ops_host, int n_ops, void* stream);
 
+/* ---- depth evaluation: flip-and-fuse post-processing and the depth metrics (csrc/depth_eval.h), since ABI version 3 ---------------
+ * The tail of the reference's ModelWrapper.evaluate_depth (models/model_wrapper.py:291-317) on the device.  Every tensor is
+ * contiguous [B][1][H][W], fp32 (its `_h16` flag 0) or IEEE fp16 (flag 1); arithmetic is fp32 (block and image sums double), an
+ * fp16 output is rounded once to nearest even.  Forward only.  NaN inputs: unspecified.
+ * pnsfm_post_process_inv_depth (utils/depth.py:201-255): one elementwise launch,
+ *   out(x) = mask(W-1-x) inv(x) + mask(x) f(x) + (1 - mask(x) - mask(W-1-x)) fuse(inv(x), f(x)),  f(x) = flipped(W-1-x),
+ *   mask(x) = 1 - clamp(20 (x / (W-1) - 0.05), 0, 1);  method 0 = mean, 1 = max, 2 = min.
+ * pnsfm_depth_metrics (utils/depth.py:258-324, scale_depth :327-360): metrics[7] = {abs_rel, sqr_rel, rmse, rmse_log, a1, a2, a3}
+ *   summed over the images that have a valid pixel and divided by B; rows[B][8] = the per-image values and the valid-pixel count
+ *   (all zero for an image without one).  A ground-truth pixel is valid when min_depth < gt < max_depth and it lies in rows [y1, y2),
+ *   columns [x1, x2) (the whole image, or the host-computed Garg window).  The prediction at a ground-truth pixel is sampled on the
+ *   fly: scale_output 0 = bilinear, align_corners (a straight load when the sizes agree), 1 = top-center paste (flush with the bottom
+ *   edge, centred horizontally, zero outside; needs Hp <= Hg, Wp <= Wg).  pred_is_inverse != 0: pred holds INVERSE depth and every tap
+ *   is inverted as 1 / max(v, 1e-6) before the taps are interpolated (the reference resizes depth).  use_gt_scale != 0: the
+ *   prediction is multiplied by median(valid gt) / median(valid sampled prediction) -- exact lower medians (torch.median) by a radix
+ *   select with integer histograms -- and then clamped to [min_depth, max_depth].  A fixed number of launches whatever B and the image
+ *   size, no device->host copy, no synchronisation, no float atomics: bit-reproducible.
+ *   ws: pnsfm_depth_metrics_ws_bytes(B) bytes, 8-byte aligned, no initialisation needed; after a use_gt_scale call its first 2 B floats
+ *   are {median gt, median sampled prediction} per image.  sampled (nullable, testing aid): [B][Hg][Wg] floats, receives the sampled
+ *   prediction at every ground-truth pixel. */
+int pnsfm_post_process_inv_depth(const void* inv, int inv_h16, const void* flipped, int flipped_h16, void* out, int out_h16, int B, int H,
+                                 int W, int method, void* stream);
+size_t pnsfm_depth_metrics_ws_bytes(int B);
+int pnsfm_depth_metrics(const void* gt, int gt_h16, const void* pred, int pred_h16, float* metrics, float* rows, void* ws,
+                        float* sampled /*nullable*/, int B, int Hg, int Wg, int Hp, int Wp, float min_depth, float max_depth, int y1,
+                        int y2, int x1, int x2, int scale_output, int use_gt_scale, int pred_is_inverse, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -168,3 +168,5 @@ int pnsfm_supervised_loss_backward(const float* pred, const float* gt, const dou
 }
 
 }  // extern "C"
+
+#include "depth_eval.h"      // depth evaluation: post-processing and metrics (same streaming-reduction family)

@@ -80,6 +80,10 @@ SIGNATURES = {
     "pnsfm_upsample_nearest_forward_h16": (_i, [_p, _p, _i, _i, _i, _i, _p]),
     "pnsfm_invdepth_conv_forward_h16": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _f, _p]),
     "pnsfm_region_ops_h16": (_i, [_p, _i, _p]),
+    # depth evaluation (post-processing and metrics; fp32 or fp16 storage by a flag per tensor)
+    "pnsfm_post_process_inv_depth": (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _p]),
+    "pnsfm_depth_metrics_ws_bytes": (_sz, [_i]),
+    "pnsfm_depth_metrics": (_i, [_p, _i, _p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _i, _i, _i, _i, _i, _i, _i, _p]),
     "pnsfm_photometric_l1_forward": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p]),
     "pnsfm_photometric_l1_backward": (_i, [_p, _p, _p, _p, _f, _p, _i, _i, _i, _i, _i, _i, _p]),
     "pnsfm_smoothness_forward": (_i, [_p, _p, _p, _i, _i, _i, _p]),

@@ -1649,3 +1649,53 @@ class SmoothnessNormFn(Function):
 
 def smoothness_norm(inv_depth, image):
     return SmoothnessNormFn.apply(inv_depth, image)
+
+
+# ---- depth evaluation (include/pnsfm.h "depth evaluation"; csrc/depth_eval.h) ------------------------------------------------------
+# Forward only, like the fp16 forward: evaluation runs under torch.no_grad(); with a gradient-requiring input the result carries a
+# node whose backward raises, for fp32 and fp16 alike.
+_EVAL_ONLY_FWD = "the depth-evaluation kernels are forward only (post-processing and metrics run under torch.no_grad())"
+
+
+class _EvalForwardOnlyFn(Function):
+    @staticmethod
+    def forward(ctx, fn, *args):
+        return fn(*args)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        raise NotImplementedError(_EVAL_ONLY_FWD)
+
+
+def post_process_inv_depth(inv, inv_flipped, method='mean'):
+    """Flip-and-fuse post-processing of an inverse-depth map and the map predicted from the mirrored image (the reference's
+    utils/depth.py:229-255) in ONE launch; [B,1,H,W] fp32 or fp16 -> inv's dtype (fp32 arithmetic, one rounding)."""
+    if method not in ops.PP_METHODS:
+        raise ValueError('Unknown post-process method {}'.format(method))
+    run = lambda a, b: ops.post_process_inv_depth(a.contiguous(), b.contiguous(), ops.PP_METHODS[method])      # noqa: E731
+    if torch.is_grad_enabled() and (inv.requires_grad or inv_flipped.requires_grad):
+        return _EvalForwardOnlyFn.apply(run, inv, inv_flipped)
+    return run(inv, inv_flipped)
+
+
+def depth_metrics(gt, pred, min_depth, max_depth, window=None, scale_output='resize', use_gt_scale=True, pred_is_inverse=False,
+                  details=False):
+    """[abs_rel, sqr_rel, rmse, rmse_log, a1, a2, a3] of packnet_sfm.utils.depth.compute_depth_metrics as a [7] fp32 DEVICE tensor, in a
+    fixed number of launches and without a host sync.  gt [B,1,Hg,Wg], pred [B,1,Hp,Wp], fp32 or fp16 each (arithmetic is fp32: for
+    fp16 storage the result is the Python function's on .float() inputs).  window = (y1, y2, x1, x2): the rows / columns of gt that
+    count (None: all; the Garg crop: utils.depth.crop_window).  pred_is_inverse: pred is INVERSE depth, inverted per tap before the
+    resize (inv2depth without its pass).
+    details=True -> (metrics, rows [B,8] = per-image metrics + valid-pixel count, medians [B,2] = (gt, sampled prediction) of each
+    image or None without use_gt_scale, sampled [B,1,Hg,Wg] = the prediction the kernels saw at every ground-truth pixel)."""
+    if scale_output not in ops.SCALE_OUTPUTS:
+        raise NotImplementedError('Depth scale function {} not implemented.'.format(scale_output))
+    if torch.is_grad_enabled() and (gt.requires_grad or pred.requires_grad):
+        raise NotImplementedError(_EVAL_ONLY_FWD)
+    if window is None:
+        window = (0, gt.shape[2], 0, gt.shape[3])
+    metrics, rows, ws, sampled = ops.depth_metrics(gt.contiguous(), pred.contiguous(), min_depth, max_depth, window,
+                                                   ops.SCALE_OUTPUTS[scale_output], use_gt_scale, pred_is_inverse, dump=details)
+    if not details:
+        return metrics
+    B = gt.shape[0]
+    return metrics, rows, (ws[:2 * B].view(torch.float32).reshape(B, 2) if use_gt_scale else None), sampled

@@ -673,6 +673,56 @@ def supervised_loss_backward(pred, gt, ws, grad_out, method, sparse):
     return dpred
 
 
+# ---------------------------------------------------------------------------------- depth evaluation
+PP_METHODS = {'mean': 0, 'max': 1, 'min': 2}
+SCALE_OUTPUTS = {'resize': 0, 'top-center': 1}
+
+
+def _f32_or_h16(*tensors):
+    for t in tensors:
+        if t.dtype not in (torch.float32, torch.float16):
+            raise RuntimeError("packnet_sfm depth-evaluation op needs float32 or float16 tensors, got %s" % t.dtype)
+
+
+def _b1hw(t, what):
+    if t.dim() != 4 or t.shape[1] != 1:
+        raise RuntimeError("%s must be [B,1,H,W], got %s" % (what, tuple(t.shape)))
+
+
+def post_process_inv_depth(inv, inv_flipped, method):
+    """inv, inv_flipped: [B,1,H,W], fp32 or fp16 -> the flip-and-fuse map in inv's dtype (one launch)."""
+    _chk(inv, inv_flipped); _f32_or_h16(inv, inv_flipped); _b1hw(inv, "post_process_inv_depth: inv_depth")
+    if inv.shape != inv_flipped.shape:
+        raise RuntimeError("post_process_inv_depth: %s and its flipped counterpart %s differ in shape" % (tuple(inv.shape), tuple(inv_flipped.shape)))
+    B, _, H, W = inv.shape
+    out = torch.empty_like(inv)
+    h = [int(t.dtype == torch.float16) for t in (inv, inv_flipped, out)]
+    _lib.check(_lib.get().pnsfm_post_process_inv_depth(_ptr(inv), h[0], _ptr(inv_flipped), h[1], _ptr(out), h[2], B, H, W, int(method),
+                                                       _stream(inv)), "post_process_inv_depth")
+    return out
+
+
+def depth_metrics(gt, pred, min_depth, max_depth, window, scale_output, use_gt_scale, pred_is_inverse, dump=False):
+    """gt [B,1,Hg,Wg], pred [B,1,Hp,Wp] (fp32 or fp16 each); window = (y1, y2, x1, x2) rows / columns of gt that count.
+    -> (metrics [7] fp32, rows [B,8] fp32, ws int32 words (its first 2B words: the fp32 medians), sampled [B,1,Hg,Wg] fp32 | None),
+    all on gt's device; nothing is copied to the host."""
+    _chk(gt, pred); _f32_or_h16(gt, pred); _b1hw(gt, "depth_metrics: gt"); _b1hw(pred, "depth_metrics: pred")
+    if pred.shape[0] != gt.shape[0]:
+        raise RuntimeError("depth_metrics: gt %s and pred %s differ in batch size" % (tuple(gt.shape), tuple(pred.shape)))
+    B, _, Hg, Wg = gt.shape
+    lib = _lib.get()
+    metrics = torch.empty((7,), dtype=torch.float32, device=gt.device)
+    rows = torch.empty((B, 8), dtype=torch.float32, device=gt.device)
+    ws = torch.empty((int(lib.pnsfm_depth_metrics_ws_bytes(B)) // 8,), dtype=torch.float64, device=gt.device).view(torch.int32)
+    sampled = torch.empty((B, 1, Hg, Wg), dtype=torch.float32, device=gt.device) if dump else None
+    y1, y2, x1, x2 = (int(v) for v in window)
+    _lib.check(lib.pnsfm_depth_metrics(_ptr(gt), int(gt.dtype == torch.float16), _ptr(pred), int(pred.dtype == torch.float16),
+                                       _ptr(metrics), _ptr(rows), _ptr(ws), _ptr(sampled), B, Hg, Wg, pred.shape[2], pred.shape[3],
+                                       float(min_depth), float(max_depth), y1, y2, x1, x2, int(scale_output), int(bool(use_gt_scale)),
+                                       int(bool(pred_is_inverse)), _stream(gt)), "depth_metrics")
+    return metrics, rows, ws, sampled
+
+
 # ------------------------------------------------------------------------------------------------ NRS
 def nrs_project_forward(direction, ray, temperature):
     """direction, ray: [3,h,w] -> (coords [h,w,2] = expected (row, col), stat [h,w,2] for backward)."""

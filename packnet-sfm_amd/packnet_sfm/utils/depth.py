@@ -2,6 +2,7 @@
 packnet_sfm/utils/depth.py).  inv2depth on the loss path is fused into the view-synthesis kernel."""
 import torch
 
+from packnet_sfm.utils.image import flip_lr
 from packnet_sfm.utils.types import is_seq
 
 
@@ -77,6 +78,77 @@ def compute_depth_metrics(config, gt, pred, use_gt_scale=True):
         p = p.clamp(config.min_depth, config.max_depth)
         totals += torch.stack([fn(g, p) for _, fn in _DEPTH_METRICS]).double().cpu()
     return (totals / B).type_as(gt)
+
+
+def crop_window(crop, H, W):
+    """(y1, y2, x1, x2): the rows / columns of an H x W ground truth that config.crop keeps ('' | 'garg')."""
+    if crop == 'garg':
+        return (int(_GARG_ROWS[0] * H), int(_GARG_ROWS[1] * H), int(_GARG_COLS[0] * W), int(_GARG_COLS[1] * W))
+    return (0, H, 0, W)
+
+
+def fuse_inv_depth(inv_depth, inv_depth_hat, method='mean'):
+    """Fuse an inverse-depth map and the (already flipped back) map of the mirrored image: 'mean' | 'max' | 'min'."""
+    if method == 'mean':
+        return 0.5 * (inv_depth + inv_depth_hat)
+    if method == 'max':
+        return torch.max(inv_depth, inv_depth_hat)
+    if method == 'min':
+        return torch.min(inv_depth, inv_depth_hat)
+    raise ValueError('Unknown post-process method {}'.format(method))
+
+
+def _on_kernels(*tensors):
+    """Device tensors go to the HIP kernels (so do host tensors while the tests run the kernel sources on the emulator)."""
+    from packnet_sfm.hip import _lib
+    return all(t.is_cuda for t in tensors) or not _lib.REQUIRE_CUDA
+
+
+def post_process_inv_depth(inv_depth, inv_depth_flipped, method='mean'):
+    """Flip-and-fuse post-processing: the left 5 % of the width comes from the flipped prediction, the right 5 % from the plain
+    one, linear ramps over the next 5 % on either side, fuse_inv_depth in between.  Device tensors: one kernel launch
+    (hip.functional.post_process_inv_depth); CPU tensors: the same formula in torch."""
+    if method not in ('mean', 'max', 'min'):
+        raise ValueError('Unknown post-process method {}'.format(method))
+    if _on_kernels(inv_depth, inv_depth_flipped):
+        from packnet_sfm.hip import functional as HF
+        return HF.post_process_inv_depth(inv_depth, inv_depth_flipped, method)
+    W = inv_depth.shape[3]
+    inv_depth_hat = flip_lr(inv_depth_flipped)
+    xs = torch.arange(W, device=inv_depth.device, dtype=inv_depth.dtype) / max(W - 1, 1)
+    mask = 1.0 - torch.clamp(20. * (xs - 0.05), 0., 1.)
+    mask_hat = mask.flip(0)
+    return mask_hat * inv_depth + mask * inv_depth_hat + (1.0 - mask - mask_hat) * fuse_inv_depth(inv_depth, inv_depth_hat, method)
+
+
+def evaluate_depth(config, gt, inv_depth, inv_depth_flipped=None, modes=('', '_pp', '_gt', '_pp_gt'), method='mean'):
+    """The reference's ModelWrapper.evaluate_depth after its two network forwards: inv_depth / inv_depth_flipped [B,1,h,w] are the
+    predictions for the image and for its mirror image, gt [B,1,H,W] the ground truth.  Returns {'metrics': OrderedDict(mode -> [7]
+    tensor like compute_depth_metrics, type_as(gt)), 'inv_depth': the post-processed map (None without inv_depth_flipped)}; a mode
+    containing 'pp' scores the post-processed map, one containing 'gt' uses median scaling.
+    Device tensors: one post-process launch and one hip.functional.depth_metrics call per mode on the INVERSE depth (inverted per
+    tap, resized on the fly): no inv2depth pass, no host sync, the metrics stay on the device.  fp16 maps are scored in fp32
+    arithmetic, i.e. as compute_depth_metrics scores their .float() copies.  CPU tensors: the Python functions of this module."""
+    from collections import OrderedDict
+    if any('pp' in m for m in modes) and inv_depth_flipped is None:
+        raise ValueError('evaluate_depth: the post-processed modes need inv_depth_flipped')
+    inv_depth_pp = None
+    if inv_depth_flipped is not None:
+        inv_depth_pp = post_process_inv_depth(inv_depth, inv_depth_flipped, method=method)
+    metrics = OrderedDict()
+    if _on_kernels(gt, inv_depth):
+        from packnet_sfm.hip import functional as HF
+        window = crop_window(config.crop, gt.shape[2], gt.shape[3])
+        for mode in modes:
+            metrics[mode] = HF.depth_metrics(gt, inv_depth_pp if 'pp' in mode else inv_depth, config.min_depth, config.max_depth,
+                                             window=window, scale_output=getattr(config, 'scale_output', 'resize'),
+                                             use_gt_scale='gt' in mode, pred_is_inverse=True).type_as(gt)
+    else:
+        depth = inv2depth(inv_depth)
+        depth_pp = inv2depth(inv_depth_pp) if inv_depth_pp is not None else None
+        for mode in modes:
+            metrics[mode] = compute_depth_metrics(config, gt, depth_pp if 'pp' in mode else depth, use_gt_scale='gt' in mode)
+    return {'metrics': metrics, 'inv_depth': inv_depth_pp}
 
 
 # names of the reference's module of the same path that the hot path does not re-implement (packnet_sfm/_merge.py)

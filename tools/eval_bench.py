@@ -5,6 +5,9 @@
 
     python tools/eval_bench.py --layers          # the fp16 conv kernel alone, per layer class of PackNet01 at 192x640 batch 4
 
+    python tools/eval_bench.py --metrics         # the tail of an evaluation step (post-process + 4 x depth metrics), KITTI shapes
+    python tools/eval_bench.py --metrics-launches fused --calls 12     # N calls of one tail path, for a kernel trace (launch count)
+
 Prints ONE JSON line: per size and path images/s, ms per forward (device events over windows of >= `window` s), host-issue ms per forward,
 conv GFLOP from shapes (as executed, i.e. with the collapsed packing layers, and reference-algorithmic) and achieved conv TFLOP/s."""
 import argparse
@@ -116,6 +119,103 @@ def time_path(fn, window, ev_only=False):
     return ms_dev / n, 1e3 * t_host / n
 
 
+def _tail_paths(cfg, gt, inv, inv_f):
+    """The two forms of an evaluation step's tail after the two network forwards: (i) the Python composition -- inv2depth x 2, the
+    post-process formula in torch, compute_depth_metrics x 4 (per-image gathers, medians and host syncs) -- and (ii) evaluate_depth
+    (one post-process launch + 4 fused depth_metrics calls, metrics left on the device)."""
+    from packnet_sfm.utils import depth as D
+
+    def torch_post_process(a, f):
+        W = a.shape[3]
+        ah = f.flip(3)
+        xs = torch.linspace(0., 1., W, device=a.device, dtype=a.dtype)
+        mask = 1.0 - torch.clamp(20. * (xs - 0.05), 0., 1.)
+        mask_hat = mask.flip(0)
+        return mask_hat * a + mask * ah + (1.0 - mask - mask_hat) * (0.5 * (a + ah))
+
+    def python_tail():
+        depth, depth_pp = D.inv2depth(inv), D.inv2depth(torch_post_process(inv, inv_f))
+        return [D.compute_depth_metrics(cfg, gt, depth_pp if 'pp' in m else depth, use_gt_scale='gt' in m) for m in ('', '_pp', '_gt', '_pp_gt')]
+
+    def fused_tail():
+        return list(D.evaluate_depth(cfg, gt, inv, inv_f)['metrics'].values())
+    return {'python': python_tail, 'fused': fused_tail}
+
+
+def _tail_inputs(B, dtype, dev):
+    """KITTI-shaped: sparse ground truth 375 x 1242 (about a fifth of the pixels valid), inverse-depth predictions 192 x 640."""
+    import types
+    g = torch.Generator(device=dev).manual_seed(0)
+    gt = 80 * torch.rand((B, 1, 375, 1242), device=dev, generator=g)
+    gt[torch.rand((B, 1, 375, 1242), device=dev, generator=g) > 0.2] = 0
+    inv = 1.0 / (2 + 70 * torch.rand((B, 1, 192, 640), device=dev, generator=g))
+    inv_f = 1.0 / (2 + 70 * torch.rand((B, 1, 192, 640), device=dev, generator=g))
+    cfg = types.SimpleNamespace(crop='garg', min_depth=0.0, max_depth=80.0, scale_output='resize')
+    return cfg, gt.to(dtype), inv.to(dtype), inv_f.to(dtype)
+
+
+def wall_per_call(fn, calls):
+    """ms per call, host clock around the call AND a device synchronise (the Python tail syncs inside; device events alone would
+    flatter it): (median, min) over `calls` calls."""
+    ts = []
+    for _ in range(calls):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        ts.append(1e3 * (time.perf_counter() - t0))
+    ts.sort()
+    return ts[len(ts) // 2], ts[0]
+
+
+def metrics_tail(a):
+    dev = torch.device('cuda:0')
+    result = {'tool': 'eval_bench --metrics', 'device': torch.cuda.get_device_name(0), 'gt': [375, 1242], 'pred': [192, 640],
+              'crop': 'garg', 'modes': 4, 'timing': 'host clock around call + device synchronise, ms per call', 'settings': {}}
+    with torch.no_grad():
+        for B in (1, 4):
+            for name, dtype in (('fp32', torch.float32), ('fp16', torch.float16)):
+                paths = _tail_paths(*_tail_inputs(B, dtype, dev))
+                outs = {k: [t.float().cpu() for t in fn()] for k, fn in paths.items()}
+                for fn in paths.values():
+                    for _ in range(5):
+                        fn()
+                samples = {k: [] for k in paths}
+                for _ in range(a.reps):                      # alternate the two paths
+                    for k, fn in paths.items():
+                        samples[k].append(wall_per_call(fn, a.calls))
+                entry = {k: {'ms_median': round(min(m for m, _ in v), 4), 'ms_min': round(min(lo for _, lo in v), 4),
+                             'ms_median_all_rounds': [round(m, 4) for m, _ in v]} for k, v in samples.items()}
+                entry['python_over_fused'] = round(entry['python']['ms_median'] / entry['fused']['ms_median'], 2)
+                entry['max_abs_metric_difference'] = max(float((x - y).abs().max()) for x, y in zip(outs['python'], outs['fused']))
+                result['settings']['b%d_%s' % (B, name)] = entry
+        if not a.no_forward:                                 # the fp16 network forward in front of the tail, same process
+            from oracle import packnet_oracle as O
+            from packnet_sfm.networks.depth.PackNet01 import PackNet01
+            net = PackNet01(dropout=0.0, version='1A')
+            net.load_state_dict(O.init_params(O.packnet01_param_shapes('1A'), seed=0))
+            net = net.to(dev, dtype=torch.float16).eval()
+            result['hip16_forward_ms'] = {}
+            for B in (1, 4):
+                x = torch.rand((B, 3, 192, 640), device=dev).half()
+                for _ in range(3):
+                    net(rgb=x)
+                result['hip16_forward_ms']['b%d' % B] = round(min(time_path(lambda: net(rgb=x), a.window)[0] for _ in range(a.reps)), 3)
+    print(json.dumps(result))
+
+
+def metrics_launches(a):
+    """`--calls` calls of ONE tail path at batch 4, fp32, for `rocprofv3 --kernel-trace`: launches per call = (kernels traced with
+    --calls n2) - (with --calls n1), over n2 - n1."""
+    dev = torch.device('cuda:0')
+    with torch.no_grad():
+        fn = _tail_paths(*_tail_inputs(4, torch.float32, dev))[a.metrics_launches]
+        for _ in range(a.calls):
+            fn()
+        torch.cuda.synchronize()
+    print(json.dumps({'tool': 'eval_bench --metrics-launches', 'path': a.metrics_launches, 'calls': a.calls}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--sizes', default='192x640x1,192x640x4,384x1280x1')
@@ -124,7 +224,15 @@ def main():
     ap.add_argument('--paths', default='hip32,hip16,eager16')
     ap.add_argument('--layers', action='store_true', help='per-layer-class TFLOP/s of the fp16 conv kernel (192x640, --batch)')
     ap.add_argument('--batch', type=int, default=4)
+    ap.add_argument('--metrics', action='store_true', help='tail of an evaluation step: Python composition vs evaluate_depth')
+    ap.add_argument('--metrics-launches', choices=('python', 'fused'), help='run --calls calls of one tail path (for a kernel trace)')
+    ap.add_argument('--calls', type=int, default=30, help='--metrics: calls per round and path')
+    ap.add_argument('--no-forward', action='store_true', help='--metrics: skip the fp16 network forward')
     a = ap.parse_args()
+    if a.metrics_launches:
+        return metrics_launches(a)
+    if a.metrics:
+        return metrics_tail(a)
     if a.layers:
         with torch.no_grad():
             print(json.dumps({'tool': 'eval_bench --layers', 'device': torch.cuda.get_device_name(0), 'batch': a.batch,
