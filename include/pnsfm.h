@@ -134,14 +134,18 @@ int pnsfm_get_conv_math(void);
  * wide so that W = 20 / 40 / 80 fit; same arithmetic, same two-stage reduction), which is reachable through the tuning database /
  * pnsfm_tune_set only.  For tests. */
 int pnsfm_set_wgrad_variant(int tap_major);
-/* Programmatic entry of the tuning database (what a PNSFM_TUNE_DB line does): key7 = {kind, B, Cin, Cout, H, W, ks} with
- * kind = 0 forward / 1 backward-data / 2 backward-weight, + 10 * stride; for kind 2 the key holds H*W in place of H and the
- * tiling width in place of W (32 for a 1x1 convolution).  forward / backward-data (+ 100 on `kind` for the split-bf16 arithmetic): v0 = NT | variant << 4 | narrow-M << 8,
- * v1 = K-split; backward-weight: v0 = pixel split, v1 = kernel (0 generic, 1 tap-major, 2 | NT << 4 | WM << 6 split-bf16 one
- * kernel row per workgroup, 3 | (WCI | TG << 4 | TR << 8) << 4 split-bf16 nine taps per workgroup).  Forward / backward-data variants:
- * 0..2 f32 stagings, 3..6 split-bf16 LDS plans, 7 ping-pong workgroup, 8 the 1x1 kernel without LDS.  Used by the determinism sweep
- * (tools/conv_config_sweep.py), which checks EVERY configuration the autotuner may pick against the oracle's convolution. */
+/* Programmatic entry of the tuning database (what a PNSFM_TUNE_DB line does): pins the decision {v0, v1} for the launches whose key is
+ * key7 until the next pnsfm_set_conv_variant / pnsfm_set_wgrad_variant.  key7 comes from pnsfm_tune_key; the layout of v0 / v1 is the
+ * decision codec's table in csrc/conv2d.hip (ConvDecision / WgradDecision), mirrored for Python by packnet_sfm/hip/tune.py.  Used by
+ * the tests and by the determinism sweep (tools/conv_config_sweep.py), which checks EVERY configuration the autotuner may pick against
+ * the oracle's convolution. */
 int pnsfm_tune_set(const int* key7, int v0, int v1);
+/* The key under which a launch looks its tuning decision up (first seven columns of a database line), from the functions the
+ * launches themselves call.  kind: 0 forward, 1 backward-data, 2 weight gradient; H, W: the OUTPUT map (y / dY); Cin, Cout: K and M of
+ * the launch as the key holds them (backward-data: K = channels of dY); nsrc: 1..3 input tensors (pnsfm_conv2d_forward_cat /
+ * _backward_weight_cat).  Depends on the arithmetic mode in force (pnsfm_set_conv_math).  Pure host query: no pointers, no launch;
+ * non-zero (message in pnsfm_last_error) for a shape the launch would refuse. */
+int pnsfm_tune_key(int kind, int B, int Cin, int Cout, int H, int W, int ks, int stride, int nsrc, int* key7);
 /* What the calling thread's most recent forward / backward-data launch actually ran: out8 = {variant (0..2 f32 stagings, 3..6
  * split-bf16 LDS plans, 7 ping-pong workgroup, 8 the 1x1 kernel without LDS), pixel tiles per wave NT, M tiles per wave MT, taps per weight stage G, K-split,
  * tile mode (0 classic, 1 16-wide rectangles, 2 row bands), workgroups, LDS bytes}.  A pinned configuration that does not fit

@@ -19,7 +19,7 @@
 //                   7  split-bf16, ping-pong workgroup   conv2d_bx3pp_kernel        (conv2d_bx3pp.h)
 //                   8  split-bf16, 1x1 without LDS       conv1x1_bx3_kernel         (conv2d_bx3_1x1.h)
 //                   9  fp16 forward (inference)          conv2d_h16.h, included at the end
-//   dispatch      enqueue_conv (one launch of a given geometry), launch_conv (decision -> geometry -> launch) and its autotuner
+//   dispatch      enqueue_conv (one launch of a given geometry), launch_conv (conv_tune_key -> decision -> geometry -> launch) and its autotuner
 //   packers       pack_weights_kernel and the batched pack tables
 //   weight grad   sum_slabs_kernel, the stem and the generic f32 kernels; the tap-major, split-bf16 and nine-taps kernels live in
 //                 conv2d_wgrad{2,3,4}.hip.  WgradPlan and the wgrad_* steps choose among them (wgrad_impl)
@@ -324,7 +324,8 @@ static void tune_db_append(const std::array<int, 7>& k, const std::array<int, 2>
 
 // ---- decision codec ---------------------------------------------------------------------------------------------------
 // A tuning decision is two ints {v0, v1}: the value of g_tuned / g_pinned, the last two columns of a database line and the
-// arguments of pnsfm_tune_set.  This is the only place that knows their layout:
+// arguments of pnsfm_tune_set.  This is the only place in C++ that knows their layout (packnet_sfm/hip/tune.py mirrors it field for field
+// for the tests and tools; tests/tune_cases.py holds the two together):
 //
 //   key kind            v0                                                      v1
 //   x0 / x1  forward,   NT | variant << 4 | forceMT << 8 | tm << 9              K-split
@@ -1315,25 +1316,33 @@ void conv_last_config_set(int code, int p1, int p2, int p3, int splits, int p5, 
   g_last_conv = {code, p1, p2, p3, splits, p5, blocks, smem};
 }
 
-static int launch_conv(const float* x, const float* wp, const float* bias, float* y, int B, int Cin, int Cout,
-                       int H, int W, int ks, hipStream_t stream, const char* what, int kind_tag, int S = 1, int Hi = 0,
-                       int Wi = 0, const ConvSrc* ms = nullptr, ConvGnOut* gn = nullptr) {
-  if (S == 1) { Hi = H; Wi = W; }
+// The shape checks of a forward (kind_tag 0) / backward-data (1) launch, the map it tiles, its heuristic geometry and the key of its
+// tuning decision: the one place that forms that key (launch_conv looks it up, pnsfm_tune_key reports it).  H, W: the OUTPUT map, in
+// and out -- a 1x1 stride-1 layer has no halo, any pixel order works, so a map whose width is not a multiple of 32 is tiled as 32-wide
+// rows of the flattened image when that is exact (whole 2-D tiles instead of linear runs whose patches span full-width rows).
+static int conv_tune_key(const char* what, int kind_tag, int B, int Cin, int Cout, int& H, int& W, int ks, int S, ConvGeom& g,
+                         std::array<int, 7>& key) {
   if (B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) { set_error("%s: bad shape", what); return -1; }
   if (ks != 1 && ks != 3 && ks != 5 && ks != 7) { set_error("%s: unsupported kernel size %d", what, ks); return -1; }
   if (S != 1 && S != 2) { set_error("%s: unsupported stride %d", what, S); return -1; }
-  if (ks == 1 && S == 1 && (H * W) % 32 == 0 && W % 32 != 0) {
-    // no halo: any pixel order works, so a map whose width is not a multiple of 32 is tiled as 32-wide rows of the flattened
-    // image (whole 2-D tiles instead of linear runs whose patches span full-width rows)
-    H = (H * W) / 32; W = 32; Hi = H; Wi = W;
-  }
-  ConvGeom g = conv_geom(B, Cin, Cout, H, W, ks, S);
+  if (ks == 1 && S == 1 && (H * W) % 32 == 0 && W % 32 != 0) { H = (H * W) / 32; W = 32; }
+  g = conv_geom(B, Cin, Cout, H, W, ks, S);
   if (g.smem_bytes > (g.DMA >= 2 ? kMaxSmemPipe : kMaxSmem)) { set_error("%s: image too wide for the LDS halo patch (W=%d)", what, W); return -1; }
+  key = {kind_tag + 10 * S + (conv_use_bx3(Cin, ks) ? 100 : 0), B, Cin, Cout, H, W, ks};
+  return 0;
+}
+
+static int launch_conv(const float* x, const float* wp, const float* bias, float* y, int B, int Cin, int Cout,
+                       int H, int W, int ks, hipStream_t stream, const char* what, int kind_tag, int S = 1, int Hi = 0,
+                       int Wi = 0, const ConvSrc* ms = nullptr, ConvGnOut* gn = nullptr) {
+  ConvGeom g;
+  std::array<int, 7> key;
+  if (conv_tune_key(what, kind_tag, B, Cin, Cout, H, W, ks, S, g, key)) return -1;
+  if (S == 1) { Hi = H; Wi = W; }
   {
     // tuned / pinned configuration of this shape: the autotuner's result, a PNSFM_TUNE_DB line or pnsfm_tune_set (tests pin
     // configurations the un-tuned heuristics would not pick; that works in every build, the timing search needs a GPU)
     const bool bx3 = conv_use_bx3(Cin, ks);
-    const std::array<int, 7> key = {kind_tag + 10 * S + (bx3 ? 100 : 0), B, Cin, Cout, H, W, ks};
     const bool tune = autotune_enabled();        // (first call: reads the environment and loads PNSFM_TUNE_DB under the lock)
     std::lock_guard<std::mutex> lk(g_tune_mu);
     const std::array<int, 2>* dec = tune_lookup(key, tune);
@@ -2312,6 +2321,13 @@ static WgradDecision wgrad_tune(const WgradPlan& p, const std::array<int, 7>& ke
 }
 #endif
 
+// The key of a weight-gradient plan's tuning decision (wgrad_impl looks it up, pnsfm_tune_key reports it): + 100 where the split-bf16
+// kernel takes the shape under the arithmetic mode in force, + 1000 for several input tensors; H*W of dY and the width the generic
+// kernel tiles (32 for a stride-1 1x1 layer, wgrad_plan_init) in place of H and W.
+static std::array<int, 7> wgrad_tune_key(const WgradPlan& p) {
+  return {2 + 10 * p.S + (p.v3_ok ? 100 : 0) + (p.ms ? 1000 : 0), p.B, p.Cin, p.Cout, p.a.cstride, p.a.W, p.ks};
+}
+
 static int wgrad_impl(const float* x, const float* dy, float* dw, float* dbias, int B, int Cin, int Cout, int H, int W,
                       int ks, int S, int Hi, int Wi, void* stream, const ConvSrc* ms = nullptr) {
   WgradPlan p;
@@ -2322,7 +2338,7 @@ static int wgrad_impl(const float* x, const float* dy, float* dw, float* dbias, 
   {
     // tuned / pinned decision of this shape (autotuner, PNSFM_TUNE_DB / shipped database, pnsfm_tune_set -- the latter in
     // every build, so tests can pin kernel, split, ci tiles per wave and co tiles per workgroup on the emulator too)
-    const std::array<int, 7> key = {2 + 10 * S + (p.v3_ok ? 100 : 0) + (ms ? 1000 : 0), B, Cin, Cout, p.a.cstride, p.a.W, ks};
+    const std::array<int, 7> key = wgrad_tune_key(p);
     const bool tune = autotune_enabled();
     std::lock_guard<std::mutex> lk(g_tune_mu);
     const std::array<int, 2>* dec = tune_lookup(key, tune);
@@ -2385,6 +2401,28 @@ int pnsfm_tune_set(const int* key7, int v0, int v1) {
   if (!key7) { set_error("tune_set: null key"); return -1; }
   std::lock_guard<std::mutex> lk(g_tune_mu);
   g_pinned[{key7[0], key7[1], key7[2], key7[3], key7[4], key7[5], key7[6]}] = {v0, v1};
+  return 0;
+}
+
+int pnsfm_tune_key(int kind, int B, int Cin, int Cout, int H, int W, int ks, int stride, int nsrc, int* key7) {
+  if (!key7) { set_error("tune_key: null key"); return -1; }
+  if (kind < 0 || kind > 2 || nsrc < 1 || nsrc > 3 || (kind == 1 && nsrc > 1)) { set_error("tune_key: no launch of kind %d reads %d input tensors", kind, nsrc); return -1; }
+  std::array<int, 7> key;
+  if (kind < 2) {
+    if (nsrc > 1 && (stride != 1 || !conv_use_bx3(Cin, ks))) { set_error("tune_key: several input tensors need the split-bf16 arithmetic (>= 16 channels) at stride 1"); return -1; }
+    ConvGeom g;
+    if (conv_tune_key("tune_key", kind, B, Cin, Cout, H, W, ks, stride, g, key)) return -1;
+  } else {
+    if (B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) { set_error("tune_key: bad shape"); return -1; }
+    if (nsrc > 1 && stride != 1) { set_error("tune_key: several input tensors need stride 1"); return -1; }
+    const ConvSrc ms = {nullptr, nullptr, 0, 0};
+    WgradPlan p = {};               // a plan without tensors: wgrad_plan_init is a function of the shape alone
+    p.ms = nsrc > 1 ? &ms : nullptr;
+    p.B = B; p.Cin = Cin; p.Cout = Cout; p.ks = ks; p.S = stride;
+    if (wgrad_plan_init(p, H, W, H * stride, W * stride)) return -1;
+    key = wgrad_tune_key(p);
+  }
+  for (int i = 0; i < 7; ++i) key7[i] = key[i];
   return 0;
 }
 

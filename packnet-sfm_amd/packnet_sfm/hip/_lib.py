@@ -119,6 +119,7 @@ SIGNATURES = {
     "pnsfm_get_conv_math": (_i, []),
     "pnsfm_set_wgrad_variant": (_i, [_i]),
     "pnsfm_tune_set": (_i, [ctypes.POINTER(ctypes.c_int), _i, _i]),
+    "pnsfm_tune_key": (_i, [_i] * 9 + [ctypes.POINTER(ctypes.c_int)]),
     "pnsfm_conv2d_last_config": (_i, [ctypes.POINTER(ctypes.c_int)]),
     "pnsfm_calib_mfma": (_i, [_p, _i, _i, _p]),
     "pnsfm_calib_copy": (_i, [_p, _p, _sz, _p]),

@@ -78,8 +78,7 @@ def test_conv2d_wgrad_nine_taps_error_vs_fp64_real_K(shape, cfg):
     """The nine-taps 3x3 weight gradient (csrc/conv2d_wgrad4.hip, 16x16x32 MFMA) at the training step's reduction lengths: same
     fp64 error bound as the one-row kernel, and the two kernels agree to fp32 round-off.  cfg = (tile width in groups, ci tiles
     per workgroup); the pixel split is the one two workgroups per CU ask for."""
-    import ctypes
-    from packnet_sfm.hip import _lib, ops, functional as HF
+    from packnet_sfm.hip import _lib, ops, tune, functional as HF
     lib = _lib.get()
     B, Cin, Cout, H, W, ks = shape
     TG, WCI = cfg
@@ -94,16 +93,16 @@ def test_conv2d_wgrad_nine_taps_error_vs_fp64_real_K(shape, cfg):
     HF.set_conv_math('bx3')
     base = -(-Cin // (16 * WCI)) * -(-Cout // (32 * (4 // WCI)))
     split = max(1, 512 // base)
-    key = (ctypes.c_int * 7)(2 + 10 + 100, B, Cin, Cout, H * W, W, ks)
     lib.pnsfm_set_autotune(0)
     try:
-        lib.pnsfm_set_wgrad_variant(2)
-        dw3, db3 = ops.conv2d_backward_weight(x, dy, ks)
-        lib.pnsfm_set_wgrad_variant(-1)
-        assert lib.pnsfm_tune_set(key, split, 3 | ((WCI | (TG << 4)) << 4)) == 0
-        dw, db = ops.conv2d_backward_weight(x, dy, ks)
+        try:
+            lib.pnsfm_set_wgrad_variant(2)
+            dw3, db3 = ops.conv2d_backward_weight(x, dy, ks)
+        finally:
+            lib.pnsfm_set_wgrad_variant(-1)
+        with tune.pinned((tune.key(tune.WGRAD, B, Cin, Cout, H, W, ks), tune.WgradDecision(3, split, WCI=WCI, TG=TG))):
+            dw, db = ops.conv2d_backward_weight(x, dy, ks)
     finally:
-        lib.pnsfm_set_wgrad_variant(-1)
         lib.pnsfm_set_autotune(1)
     e9 = float(((dw.double() - dw64).abs() / mag).max())
     e3 = float(((dw3.double() - dw64).abs() / mag).max())

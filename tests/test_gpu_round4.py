@@ -72,11 +72,9 @@ def test_deterministic_step_full_size():
 @pytest.mark.parametrize('split', [2, 5])
 def test_conv2d_split_k_two_stage_vs_fp64(shape, split):
     """K-split forward / backward-data (partial outputs in the stream's scratch buffer, conv_splitk_reduce_kernel adds them in
-    split order, bias included) at a real low-resolution layer shape, pinned through pnsfm_tune_set: error against an fp64
+    split order, bias included) at a real low-resolution layer shape, pinned (tune.pinned): error against an fp64
     convolution in the class of the un-split kernel (1e-6 of sum |x||w|), and bit-identical between two launches."""
-    import ctypes
-    from packnet_sfm.hip import _lib, ops
-    lib = _lib.get()
+    from packnet_sfm.hip import ops, tune
     B, Cin, Cout, H, W, ks = shape
     g = torch.Generator().manual_seed(sum(shape))
     x = torch.randn(B, Cin, H, W, generator=g).to(DEV)
@@ -88,18 +86,14 @@ def test_conv2d_split_k_two_stage_vs_fp64(shape, split):
     dx64 = F.conv_transpose2d(dy.double(), w.double(), padding=ks // 2)
     scale_y = F.conv2d(x.abs().double(), w.abs().double(), padding=ks // 2).max()
     scale_dx = F.conv_transpose2d(dy.abs().double(), w.abs().double(), padding=ks // 2).max()
-    try:
-        for kind, K, M in ((0, Cin, Cout), (1, Cout, Cin)):
-            key = (ctypes.c_int * 7)(kind + 10 + 100, B, K, M, H, W, ks)
-            assert lib.pnsfm_tune_set(key, 2 | (3 << 4), split) == 0
+    dec = tune.ConvDecision(2, 3, split=split)
+    with tune.pinned(*[(tune.key(kind, B, K, M, H, W, ks), dec) for kind, K, M in ((0, Cin, Cout), (1, Cout, Cin))]):
         y = ops.conv2d_forward(x, wf, b, Cout, ks)
         dx = ops.conv2d_backward_data(dy, wb, Cin, ks)
         assert float((y.double() - y64).abs().max() / scale_y) < 1e-6
         assert float((dx.double() - dx64).abs().max() / scale_dx) < 1e-6
         assert torch.equal(y, ops.conv2d_forward(x, wf, b, Cout, ks))
         assert torch.equal(dx, ops.conv2d_backward_data(dy, wb, Cin, ks))
-    finally:
-        lib.pnsfm_set_conv_variant(3)      # clears the pinned entries
 
 
 def test_region_ops_batched_windows_gpu():

@@ -3,11 +3,9 @@
 The ping-pong workgroup (csrc/conv2d_bx3pp.h, tuner variant 7) pinned ON THE DEVICE against the oracle's convolution.  The host
 emulator (tests/test_kernels_emulated.py) runs workgroups serially and cannot see what is new in this kernel: the barrier in front
 of the last tap's MFMAs, the in-place overwrite of a group's single patch buffer, lgkmcnt-only barriers with LDS-DMA in flight,
-zero-filled ragged stages, the idle second group of an odd tile count.  Every case pins the configuration through pnsfm_tune_set and
+zero-filled ragged stages, the idle second group of an odd tile count.  Every case pins the configuration (packnet_sfm.hip.tune) and
 asserts with pnsfm_conv2d_last_config that variant 7 is what ran (a pin that does not fit a shape falls back silently).
 Reference op: nn.Conv2d of packnet_sfm/networks/layers/packnet/layers01.py:28-36 (+ its autograd backward-data)."""
-import ctypes
-
 import pytest
 import torch
 import torch.nn.functional as F
@@ -24,21 +22,6 @@ def _need_gpu():
     from packnet_sfm.hip import _lib
     assert _lib.get().pnsfm_build_target() == b'gfx950'
     assert _lib.REQUIRE_CUDA
-
-
-def _cfg(NT, variant, narrow=0, tm=0):
-    return NT | (variant << 4) | (narrow << 8) | (tm << 9)
-
-
-def _pin(lib, kind, B, K, M, H, W, ks, v0, split):
-    key = (ctypes.c_int * 7)(kind + 10 + 100, B, K, M, H, W, ks)
-    assert lib.pnsfm_tune_set(key, v0, split) == 0
-
-
-def _last(lib):
-    out = (ctypes.c_int * 8)()
-    assert lib.pnsfm_conv2d_last_config(out) == 0
-    return dict(zip(('variant', 'NT', 'MT', 'G', 'split', 'tm', 'blocks', 'lds'), list(out)))
 
 
 def _data(shape, seed_extra=0):
@@ -73,8 +56,7 @@ PP_CASES = [
 def test_pingpong_kernel_vs_cpu_oracle(case):
     """Forward AND backward-data of the ping-pong kernel against the oracle's convolution at 2e-5 (the tolerance of the other
     variants in test_gpu_parity.py::test_conv2d_vs_cpu_oracle), on the configurations the shipped database takes."""
-    from packnet_sfm.hip import _lib, ops
-    lib = _lib.get()
+    from packnet_sfm.hip import ops, tune
     shape, (NT, narrow, tm), split_f, split_b = case
     B, Cin, Cout, H, W, ks = shape
     x, w, b, dy = _data(shape)
@@ -83,27 +65,23 @@ def test_pingpong_kernel_vs_cpu_oracle(case):
     yr.backward(dy)
     xd, wd, bd, dyd = x.to(DEV), w.to(DEV), b.to(DEV), dy.to(DEV)
     wf, wb = ops.conv2d_pack(wd)
-    try:
-        _pin(lib, 0, B, Cin, Cout, H, W, ks, _cfg(NT, 7, narrow, tm), split_f)
-        _pin(lib, 1, B, Cout, Cin, H, W, ks, _cfg(NT, 7, narrow, tm), split_b)
+    with tune.pinned((tune.key(tune.FORWARD, B, Cin, Cout, H, W, ks), tune.ConvDecision(NT, 7, narrow, tm, split_f)),
+                     (tune.key(tune.BACKWARD_DATA, B, Cout, Cin, H, W, ks), tune.ConvDecision(NT, 7, narrow, tm, split_b))):
         y = ops.conv2d_forward(xd, wf, bd, Cout, ks)
-        c = _last(lib)
+        c = tune.last_config()
         assert c['variant'] == 7 and c['NT'] == NT and c['split'] == split_f, c
         dx = ops.conv2d_backward_data(dyd, wb, Cin, ks)
-        c = _last(lib)
+        c = tune.last_config()
         assert c['variant'] == 7 and c['split'] == split_b, c
         P.check(y, yr, 2e-5, 'fwd (ping-pong)')
         P.check(dx, xr.grad, 2e-5, 'dgrad (ping-pong)')
-    finally:
-        lib.pnsfm_set_conv_variant(3)      # clears the pinned entries
 
 
 @pytest.mark.parametrize('channels', [(64, 128, 1), (64, 64, 1), (32, 32, 0)])
 def test_pingpong_kernel_multi_source(channels):
     """The decoder's concatenations folded into the K loop (pnsfm_conv2d_forward_cat: iconv3 = cat(unpack3, skip3, up(disp4)),
     PackNet01.py:150-168) through the ping-pong kernel against conv(cat(...)) on the CPU."""
-    from packnet_sfm.hip import _lib, ops
-    lib = _lib.get()
+    from packnet_sfm.hip import ops, tune
     C = [c for c in channels if c]
     Cin, Cout, B, H, W, ks = sum(C), 128, 2, 48, 160, 3
     g = torch.Generator().manual_seed(Cin)
@@ -112,14 +90,11 @@ def test_pingpong_kernel_multi_source(channels):
     b = torch.randn(Cout, generator=g)
     yr = F.conv2d(torch.cat(xs, 1), w, b, padding=1)
     wf, _ = ops.conv2d_pack(w.to(DEV), want_bwd=False)
-    try:
-        _pin(lib, 0, B, Cin, Cout, H, W, ks, _cfg(2, 7), 2)
+    with tune.pinned((tune.key(tune.FORWARD, B, Cin, Cout, H, W, ks, sources=len(C)), tune.ConvDecision(2, 7, split=2))):
         y = ops.conv2d_forward_cat([t.to(DEV) for t in xs], wf, b.to(DEV), Cout, ks)
-        c = _last(lib)
+        c = tune.last_config()
         assert c['variant'] == 7 and c['split'] == 2, c
         P.check(y, yr, 2e-5, 'fwd cat (ping-pong)')
-    finally:
-        lib.pnsfm_set_conv_variant(3)
 
 
 @pytest.mark.parametrize('shape,pp', [((1, 64, 64, 48, 160, 7), (2, 0, 1, 1)), ((1, 64, 64, 48, 160, 7), (2, 0, 1, 4)),
@@ -130,8 +105,7 @@ def test_pingpong_error_vs_fp64(shape, pp):
     2.1e-7 of sum |x||w| for the f32-MFMA kernel of the 7x7 shape at K split 1 / 2 / 4, 4.9e-7 / 2.4e-7 / 2.0e-7 for every split-bf16
     variant), so a comparison across different splits says nothing about the arithmetic.  At equal split the six-product arithmetic
     must stay within 1.25x of the f32 instruction's error (measured 0.55-0.94x) and below 1e-6 outright; plain bf16 sits at ~4e-4."""
-    from packnet_sfm.hip import _lib, ops, functional as HF
-    lib = _lib.get()
+    from packnet_sfm.hip import ops, tune, functional as HF
     B, Cin, Cout, H, W, ks = shape
     NT, narrow, tm, split = pp
     g = torch.Generator().manual_seed(sum(shape) + 1)
@@ -145,23 +119,19 @@ def test_pingpong_error_vs_fp64(shape, pp):
     err = {}
     try:
         for mode in ('f32', 'pp'):
-            HF.set_conv_math('f32' if mode == 'f32' else 'bx3')
-            for kind, K, M in ((0, Cin, Cout), (1, Cout, Cin)):
-                key = (ctypes.c_int * 7)(kind + 10 + (100 if mode == 'pp' else 0), B, K, M, H, W, ks)
-                v0 = _cfg(NT, 7, narrow, tm) if mode == 'pp' else _cfg(1, 0)
-                assert lib.pnsfm_tune_set(key, v0, split) == 0
-            wf, wb = ops.conv2d_pack(w.to(DEV))
-            y = ops.conv2d_forward(x.to(DEV), wf, None, Cout, ks).cpu().double()
-            c = _last(lib)
-            assert c['variant'] == (7 if mode == 'pp' else 0) and c['split'] == split, c
-            dx = ops.conv2d_backward_data(dy.to(DEV), wb, Cin, ks).cpu().double()
-            c = _last(lib)
-            assert c['variant'] == (7 if mode == 'pp' else 0) and c['split'] == split, c
+            HF.set_conv_math('f32' if mode == 'f32' else 'bx3')           # (the keys below follow the arithmetic in force)
+            dec = tune.ConvDecision(NT, 7, narrow, tm, split) if mode == 'pp' else tune.ConvDecision(1, 0, split=split)
+            with tune.pinned(*[(tune.key(kind, B, K, M, H, W, ks), dec) for kind, K, M in ((0, Cin, Cout), (1, Cout, Cin))]):
+                wf, wb = ops.conv2d_pack(w.to(DEV))
+                y = ops.conv2d_forward(x.to(DEV), wf, None, Cout, ks).cpu().double()
+                c = tune.last_config()
+                assert c['variant'] == (7 if mode == 'pp' else 0) and c['split'] == split, c
+                dx = ops.conv2d_backward_data(dy.to(DEV), wb, Cin, ks).cpu().double()
+                c = tune.last_config()
+                assert c['variant'] == (7 if mode == 'pp' else 0) and c['split'] == split, c
             err[mode] = (float(((y - y64).abs() / ymag).max()), float(((dx - dx64).abs() / dxmag).max()))
     finally:
         HF.set_conv_math('bx3')
-        lib.pnsfm_set_conv_variant(0)
-        lib.pnsfm_set_conv_variant(3)
     print('K split %d: max |err| / sum|a||b|  (fwd, dgrad):  f32 MFMA %.2e %.2e   ping-pong %.2e %.2e   [2^-24 = 5.96e-08]'
           % ((split,) + err['f32'] + err['pp']))
     for i in range(2):
@@ -175,25 +145,21 @@ def test_pingpong_bit_identical_to_single_tile_kernel(shape, NT, tm, split):
     """conv2d_bx3pp.h's header: "bit-identical results for the same chunk order" -- a pixel tile accumulates the same piece products
     in the same order (chunks ascending, taps ascending, l-m-h pieces) as conv2d_bx3_kernel does with the same (NT, tile mode,
     K-split): torch.equal between variant 7 and variant 3 on the device."""
-    from packnet_sfm.hip import _lib, ops
-    lib = _lib.get()
+    from packnet_sfm.hip import ops, tune
     B, Cin, Cout, H, W, ks = shape
     x, w, b, dy = _data(shape, 3)
     xd, bd, dyd = x.to(DEV), b.to(DEV), dy.to(DEV)
     wf, wb = ops.conv2d_pack(w.to(DEV))
     narrow = 1 if NT == 1 else 0
     out = {}
-    try:
-        for variant in (3, 7):
-            _pin(lib, 0, B, Cin, Cout, H, W, ks, _cfg(NT, variant, narrow, tm), split)
-            _pin(lib, 1, B, Cout, Cin, H, W, ks, _cfg(NT, variant, narrow, tm), split)
+    for variant in (3, 7):
+        dec = tune.ConvDecision(NT, variant, narrow, tm, split)
+        with tune.pinned(*[(tune.key(kind, B, K, M, H, W, ks), dec) for kind, K, M in ((0, Cin, Cout), (1, Cout, Cin))]):
             y = ops.conv2d_forward(xd, wf, bd, Cout, ks)
-            assert _last(lib)['variant'] == variant, _last(lib)
+            assert tune.last_config()['variant'] == variant, tune.last_config()
             dx = ops.conv2d_backward_data(dyd, wb, Cin, ks)
-            assert _last(lib)['variant'] == variant, _last(lib)
+            assert tune.last_config()['variant'] == variant, tune.last_config()
             out[variant] = (y, dx)
-    finally:
-        lib.pnsfm_set_conv_variant(3)
     assert torch.equal(out[3][0], out[7][0]), 'forward: max |d| %.3e' % float((out[3][0] - out[7][0]).abs().max())
     assert torch.equal(out[3][1], out[7][1]), 'backward-data: max |d| %.3e' % float((out[3][1] - out[7][1]).abs().max())
 
@@ -203,18 +169,16 @@ def test_pingpong_bit_identical_to_single_tile_kernel(shape, NT, tm, split):
 def test_pingpong_repeated_launches_are_bit_identical(shape, NT, tm, split):
     """Races are intermittent: 50 launches of one shape (other kernels of the library in between, so that the workgroups meet
     different neighbours and LDS contents) must all return the bits of the first."""
-    from packnet_sfm.hip import _lib, ops
-    lib = _lib.get()
+    from packnet_sfm.hip import ops, tune
     B, Cin, Cout, H, W, ks = shape
     x, w, b, dy = _data(shape, 5)
     xd, bd = x.to(DEV), b.to(DEV)
     wf, _ = ops.conv2d_pack(w.to(DEV), want_bwd=False)
     noise = torch.randn(2, 64, 48, 160, device=DEV)
     nwf, _ = ops.conv2d_pack(torch.randn(64, 64, 3, 3, device=DEV), want_bwd=False)
-    try:
-        _pin(lib, 0, B, Cin, Cout, H, W, ks, _cfg(NT, 7, 0, tm), split)
+    with tune.pinned((tune.key(tune.FORWARD, B, Cin, Cout, H, W, ks), tune.ConvDecision(NT, 7, 0, tm, split))):
         y0 = ops.conv2d_forward(xd, wf, bd, Cout, ks)
-        assert _last(lib)['variant'] == 7
+        assert tune.last_config()['variant'] == 7
         bad = 0
         for it in range(50):
             if it % 3 == 0:
@@ -222,8 +186,6 @@ def test_pingpong_repeated_launches_are_bit_identical(shape, NT, tm, split):
             y = ops.conv2d_forward(xd, wf, bd, Cout, ks)
             bad += int(not torch.equal(y, y0))
         assert bad == 0, '%d of 50 launches differ from the first' % bad
-    finally:
-        lib.pnsfm_set_conv_variant(3)
     # and the first launch is right
     P.check(y0, F.conv2d(x, w, b, padding=ks // 2), 2e-5, 'fwd')
 
@@ -336,37 +298,31 @@ def test_stem_kernel_vs_cpu_oracle_and_generic_kernel(shape, NT):
     """The depth networks' first layer (PackNet01.py:42 `Conv2D(3, 64, 5, 1)`) on its own kernel: against the oracle's convolution at
     2e-5 (full size, PackNetSlim01's 32 channels, 40 channels = a padded 32-row M tile with 45 rows = ragged tile rows, a map of a single
     tile row) and BIT-identical to the generic f32 kernel (variant 1), whose non-zero terms it adds in the same order."""
-    from packnet_sfm.hip import _lib, ops, functional as HF
+    from packnet_sfm.hip import _lib, ops, tune
     lib = _lib.get()
     B, Cin, Cout, H, W, ks = shape
     x, w, b, _ = _data(shape, 3)
     yr = F.conv2d(x, w, b, padding=ks // 2)
     xd, wd, bd = x.to(DEV), w.to(DEV), b.to(DEV)
-    key = (ctypes.c_int * 7)(10, B, Cin, Cout, H, W, ks)
+    key = tune.key(tune.FORWARD, B, Cin, Cout, H, W, ks)
     lib.pnsfm_set_autotune(0)
     try:
         wf, _wb = ops.conv2d_pack(wd)
-        assert lib.pnsfm_tune_set(key, _cfg(NT, 0), 1) == 0
-        y0 = ops.conv2d_forward(xd, wf, bd, Cout, ks)
-        c = _last(lib)
-        MT = 2 if Cout > 32 else 1
-        assert c['variant'] == 0 and c['NT'] == NT and c['lds'] == 4 * (76 * 32 * MT + 3 * (4 * NT + 4) * 36), c      # the stem kernel's LDS image
-        assert lib.pnsfm_tune_set(key, _cfg(NT, 1), 1) == 0
-        y1 = ops.conv2d_forward(xd, wf, bd, Cout, ks)
-        assert _last(lib)['variant'] == 1
+        with tune.pinned((key, tune.ConvDecision(NT, 0))):
+            y0 = ops.conv2d_forward(xd, wf, bd, Cout, ks)
+            c = tune.last_config()
+            MT = 2 if Cout > 32 else 1
+            assert c['variant'] == 0 and c['NT'] == NT and c['lds'] == 4 * (76 * 32 * MT + 3 * (4 * NT + 4) * 36), c      # the stem kernel's LDS image
+        with tune.pinned((key, tune.ConvDecision(NT, 1))):
+            y1 = ops.conv2d_forward(xd, wf, bd, Cout, ks)
+            assert tune.last_config()['variant'] == 1
     finally:
-        lib.pnsfm_set_conv_variant(0)
-        lib.pnsfm_set_conv_variant(3)
         lib.pnsfm_set_autotune(1)
     P.check(y0, yr, 2e-5, 'stem fwd')
     assert torch.equal(y0, y1)
 
 
 # ---- the LDS-free 1x1 kernel (csrc/conv2d_bx3_1x1.h, tuner variant 8): the shortcuts of the residual blocks (layers01.py:57-60)
-def _flat32(H, W):
-    return ((H * W) // 32, 32) if (H * W) % 32 == 0 and W % 32 != 0 else (H, W)       # launch_conv's 32-wide rows of a 1x1 layer
-
-
 # (shape, (NT, narrow M), K split): the shipped database's decisions at BASELINE.json configs[1] / [2], then ragged pixel tiles and
 # K chunks, padded M tiles, K splits (with fewer chunks per split than the prefetch depth)
 C1_CASES = [
@@ -382,11 +338,10 @@ def test_conv1x1_kernel_vs_cpu_oracle_and_lds_kernel(case):
     """Forward and backward-data (the latter also with an addend in the epilogue: the gradient taps of the residual blocks) of the
     LDS-free 1x1 kernel against the oracle's convolution at 2e-5, BIT-identical to conv2d_bx3_kernel (variant 3) at the same K split
     -- same six piece products per chunk in the same order -- and bit-identical over 20 repeated launches."""
-    from packnet_sfm.hip import _lib, ops, functional as HF
+    from packnet_sfm.hip import _lib, ops, tune, functional as HF
     lib = _lib.get()
     shape, (NT, narrow), split = case
     B, Cin, Cout, H, W, ks = shape
-    Hk, Wk = _flat32(H, W)
     x, w, b, dy = _data(shape, 8)
     xr = x.clone().requires_grad_(True)
     yr = F.conv2d(xr, w, b)
@@ -400,20 +355,19 @@ def test_conv1x1_kernel_vs_cpu_oracle_and_lds_kernel(case):
     try:
         wf, wb = ops.conv2d_pack(wd)
         for variant in (8, 3):
-            _pin(lib, 0, B, Cin, Cout, Hk, Wk, ks, NT | (variant << 4) | (narrow << 8), split)
-            _pin(lib, 1, B, Cout, Cin, Hk, Wk, ks, NT | (variant << 4) | (narrow << 8), split)
-            y = ops.conv2d_forward(xd, wf, bd, Cout, ks)
-            c = _last(lib)
-            assert c['variant'] == variant and c['NT'] == NT, c
-            dx = ops.conv2d_backward_data(dyd, wb, Cin, ks)
-            assert _last(lib)['variant'] == variant
-            dxa = ops.conv2d_backward_data(dyd, wb, Cin, ks, addend=addd)
-            out[variant] = (y, dx, dxa)
-            if variant == 8:
-                for _ in range(20):
-                    assert torch.equal(ops.conv2d_forward(xd, wf, bd, Cout, ks), y)
+            dec = tune.ConvDecision(NT, variant, narrow, split=split)
+            with tune.pinned(*[(tune.key(kind, B, K, M, H, W, ks), dec) for kind, K, M in ((0, Cin, Cout), (1, Cout, Cin))]):
+                y = ops.conv2d_forward(xd, wf, bd, Cout, ks)
+                c = tune.last_config()
+                assert c['variant'] == variant and c['NT'] == NT, c
+                dx = ops.conv2d_backward_data(dyd, wb, Cin, ks)
+                assert tune.last_config()['variant'] == variant
+                dxa = ops.conv2d_backward_data(dyd, wb, Cin, ks, addend=addd)
+                out[variant] = (y, dx, dxa)
+                if variant == 8:
+                    for _ in range(20):
+                        assert torch.equal(ops.conv2d_forward(xd, wf, bd, Cout, ks), y)
     finally:
-        lib.pnsfm_set_conv_variant(3)
         lib.pnsfm_set_autotune(1)
     y, dx, dxa = out[8]
     P.check(y, yr, 2e-5, '1x1 fwd')
@@ -428,7 +382,7 @@ def test_stem_weight_gradient_kernel_gpu(shape, split):
     """The stem's weight gradient on conv2d_wgrad_stem5_kernel (split-bf16 arithmetic, 16 pixels per k-step): against the oracle at 5e-5,
     against fp64 with the error bound of the other split-bf16 weight gradients (<= 16 * 2^-24 of sum |dy||x|), the same bits from
     repeated launches; pnsfm_conv2d_last_config proves the kernel ran.  Reference: the autograd weight gradient of PackNet01.py:42."""
-    from packnet_sfm.hip import _lib, ops, functional as HF
+    from packnet_sfm.hip import _lib, ops, tune, functional as HF
     lib = _lib.get()
     B, Cin, Cout, H, W, ks = shape
     x, w, b, dy = _data(shape, 4)
@@ -440,15 +394,13 @@ def test_stem_weight_gradient_kernel_gpu(shape, split):
     HF.set_conv_math('bx3')
     lib.pnsfm_set_autotune(0)
     try:
-        key = (ctypes.c_int * 7)(12, B, Cin, Cout, H * W, W, ks)
-        assert lib.pnsfm_tune_set(key, split, 0) == 0
-        dw, db = ops.conv2d_backward_weight(xd, dyd, ks)
-        assert _last(lib)['variant'] == 105
-        for _ in range(10):
-            dw2, db2 = ops.conv2d_backward_weight(xd, dyd, ks)
-            assert torch.equal(dw, dw2) and torch.equal(db, db2)
+        with tune.pinned((tune.key(tune.WGRAD, B, Cin, Cout, H, W, ks), tune.WgradDecision(0, split))):
+            dw, db = ops.conv2d_backward_weight(xd, dyd, ks)
+            assert tune.last_config()['variant'] == 105
+            for _ in range(10):
+                dw2, db2 = ops.conv2d_backward_weight(xd, dyd, ks)
+                assert torch.equal(dw, dw2) and torch.equal(db, db2)
     finally:
-        lib.pnsfm_set_wgrad_variant(-1)
         lib.pnsfm_set_autotune(1)
     P.check(dw, wr.grad, 5e-5, 'stem wgrad')
     P.check(db, br.grad, 5e-5, 'stem dbias')

@@ -16,43 +16,27 @@ import torch
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
-DB = os.path.join(ROOT, 'packnet-sfm_amd', 'csrc', 'tuned_gfx950.db')
 GOLDEN = os.path.join(ROOT, 'tests', 'golden', 'tuned_configs.json')
-# kind = 0 forward | 1 backward-data, + 10 * stride, + 100 for the split-bf16 arithmetic
-FWD_KINDS, BWD_KINDS, STRIDED_KINDS = (10, 110), (11, 111), (20, 120)
-
-
-def database_lines():
-    """[(line text, [kind, B, K, M, H, W, ks, cfg, split])] of every data line of the shipped database, in file order."""
-    out = []
-    with open(DB) as f:
-        for raw in f:
-            text = ' '.join(raw.split())
-            if not text or text.startswith('#'):
-                continue
-            vals = [int(t) for t in text.split()]
-            assert len(vals) == 9, 'malformed database line: %r' % raw
-            out.append((text, vals))
-    return out
 
 
 def replay_database(ops, lib):
     """Launch every forward / backward-data line once; {line text: the eight ints of pnsfm_conv2d_last_config}."""
-    lines = database_lines()
-    lib.pnsfm_set_wgrad_variant(-1)         # the library default; drops the pins earlier tests of this process may have left
+    from packnet_sfm.hip import tune
+    lines = tune.database_lines()
+    tune.unpin()                            # the library defaults; drops the pins earlier tests of this process may have left
     # (in this order: the first query of a process reads the environment and loads the database)
     assert ops.tune_shipped_entries() == len(lines), 'the shipped database is not what this process tunes from'
     lib.pnsfm_set_autotune(1)
     got = {}
     for text, (kind, B, K, M, H, W, ks, _cfg, _split) in lines:
-        if kind % 10 == 2:
-            continue                        # weight gradient
-        assert kind in FWD_KINDS + BWD_KINDS + STRIDED_KINDS, 'cannot replay kind %d: %s' % (kind, text)
+        direction, S, _bx3, several = tune.kind_fields(kind)
+        if direction == tune.WGRAD:
+            continue
+        assert (direction, S) in ((0, 1), (1, 1), (0, 2)) and not several and kind < 200, 'cannot replay kind %d: %s' % (kind, text)
         # the launch forms the line's key only under the arithmetic the line was tuned for (split-bf16 from 16 K-channels on)
         assert (kind >= 100) == (K >= 16 and lib.pnsfm_get_conv_math() == 1), 'cannot replay under this arithmetic: %s' % text
-        S = 2 if kind in STRIDED_KINDS else 1
         x = torch.zeros(B, K, H * S, W * S, device=DEV)
-        if kind in BWD_KINDS:               # K = channels of dy, M = channels of dx
+        if direction == tune.BACKWARD_DATA:         # K = channels of dy, M = channels of dx
             wp = torch.zeros(ops.conv2d_packed_sizes(M, K, ks)[1], device=DEV)
             y = ops.conv2d_backward_data(x, wp, M, ks)
         else:
@@ -70,13 +54,13 @@ def replay_database(ops, lib):
 
 def test_shipped_decisions_keep_their_launch_configuration():
     assert torch.cuda.is_available(), 'this test needs an MI355X'
-    from packnet_sfm.hip import _lib, ops
+    from packnet_sfm.hip import _lib, ops, tune
     lib = _lib.get()
     assert lib.pnsfm_build_target() == b'gfx950' and _lib.REQUIRE_CUDA
     with open(GOLDEN) as f:
         want = json.load(f)
     got = replay_database(ops, lib)
-    expected_lines = [text for text, vals in database_lines() if vals[0] % 10 != 2]
+    expected_lines = [text for text, vals in tune.database_lines() if vals[0] % 10 != 2]
     assert expected_lines and sorted(got) == sorted(expected_lines)         # every forward / backward-data line was replayed
     assert sorted(want) == sorted(expected_lines), 'tests/golden/tuned_configs.json does not list the database\'s lines'
     wrong = {text: (got[text], want[text]) for text in expected_lines if got[text] != want[text]}

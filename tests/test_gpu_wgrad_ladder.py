@@ -1,7 +1,7 @@
 """GPU (MI355X): every weight-gradient kernel build a tuning decision can launch, at kernel level.
 
   (a) the cases of tests/wgrad_cases.py -- one or more per instantiation of conv2d_wgrad3_kernel (58 reachable) and
-      conv2d_wgrad4_kernel (16), multi-source launches and the generic f32 kernel at stride 2 -- pinned through pnsfm_tune_set,
+      conv2d_wgrad4_kernel (16), multi-source launches and the generic f32 kernel at stride 2 -- pinned (packnet_sfm.hip.tune),
       against float64 at the project's bound (16 * 2^-24 of sum |dY||X|), with the build that ran read back through
       pnsfm_conv2d_last_config, NaN guards around the gradient slots, a bit-identical second launch and the un-split launch next to
       the split one.  The host emulator runs the same table (tests/test_kernels_emulated.py), one fiber at a time: a missing barrier
@@ -13,7 +13,6 @@ import pytest
 import torch
 
 import wgrad_cases as WC
-from test_gpu_tuned_configs import database_lines
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
@@ -38,16 +37,6 @@ def test_wgrad_ladder_case(case):
     WC.run_case(DEV, case)
 
 
-def _decode(v1):
-    """WgradDecision::decode (csrc/conv2d.hip) of the second int of a weight-gradient line."""
-    d = {'kernel': v1 & 15}
-    if d['kernel'] == 2:
-        d.update(NT=2 if ((v1 >> 4) & 3) == 2 else 1, wm=(v1 >> 6) & 15)
-    if d['kernel'] == 3:
-        d.update(WCI=(v1 >> 4) & 15, TG=(v1 >> 8) & 15, TR=(v1 >> 12) & 15)
-    return d
-
-
 def _wgrad3_WM(Cout, want):
     most = 4 if Cout > 96 else (2 if Cout > 32 else 1)
     return want if want in (1, 2, 4) and want < most else most
@@ -57,10 +46,10 @@ def test_shipped_wgrad_decisions_launch_as_written():
     """Replay of the database's weight-gradient lines (zero tensors of the line's shape, autotuner on, shipped database loaded): the
     kernel family, NT / WM / OCC (wgrad3) or WCI / TG / TR (nine taps) and the pixel splits of the launch are the line's, and every
     build reached has a case in tests/wgrad_cases.py."""
-    from packnet_sfm.hip import _lib, ops
+    from packnet_sfm.hip import _lib, ops, tune
     lib = _lib.get()
-    lines = database_lines()
-    lib.pnsfm_set_wgrad_variant(-1)         # the library default; drops the pins earlier tests of this process may have left
+    lines = tune.database_lines()
+    tune.unpin()                            # the library defaults; drops the pins earlier tests of this process may have left
     assert ops.tune_shipped_entries() == len(lines), 'the shipped database is not what this process tunes from'
     assert lib.pnsfm_get_conv_math() == 1
     lib.pnsfm_set_autotune(1)
@@ -89,9 +78,9 @@ def test_shipped_wgrad_decisions_launch_as_written():
         else:
             xs = [torch.zeros(B, Cin, H, Wd, device=DEV)]
             dw, db = ops.conv2d_backward_weight(xs[0], dy, ks)
-        cfg = ops.conv2d_last_config()
-        build = WC.launched_build(cfg)
-        d = _decode(v1)
+        last = tune.last_config()
+        cfg, build = last.raw, last.build
+        d = tune.WgradDecision.decode(split, v1)._asdict()
         if d['kernel'] == 2:
             ok = build[0] == 103 and build[1] == ks and (build[2], build[3], build[6]) == (d['NT'], _wgrad3_WM(Cout, d['wm'] & 7), 3 if d['wm'] & 8 else 2)
         elif d['kernel'] == 3:

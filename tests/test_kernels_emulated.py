@@ -5,6 +5,7 @@ import pytest
 import torch
 
 import parity_cases as P
+import tune_cases as TC
 import wgrad_cases as WC
 
 
@@ -206,18 +207,14 @@ _PIN_CFGS = [(2, 3, 0, 1), (2, 3, 0, 2), (2, 4, 0, 2), (2, 5, 1, 1), (1, 4, 1, 3
                                        for j, c in enumerate(_PIN_CFGS) if i == 0 or c[1] == 7 or (i + j) % 2 == 0])
 def test_conv2d_pinned_tilings(emulated_kernels, shape, cfg):
     """Configurations the un-tuned heuristics never pick for small test shapes (two pixel tiles per wave, narrow M tiles,
-    K splits) pinned through pnsfm_tune_set -- what the autotuner does on the GPU: cfg = (NT, variant, narrow-M, K-split)."""
-    import ctypes
+    K splits) pinned (tune.pinned) -- what the autotuner does on the GPU: cfg = (NT, variant, narrow-M, K-split)."""
     import torch.nn.functional as F
-    from packnet_sfm.hip import _lib, ops
+    from packnet_sfm.hip import _lib, ops, tune
     lib = _lib.get()
     NT, variant, narrow, split = cfg
     bx3 = variant >= 3
     lib.pnsfm_set_conv_math(1 if bx3 else 0)
     B, Cin, Cout, H, W, ks = shape
-    for kind, K, M in ((0, Cin, Cout), (1, Cout, Cin)):
-        key = (ctypes.c_int * 7)(kind + 10 + (100 if bx3 else 0), B, K, M, H, W, ks)
-        assert lib.pnsfm_tune_set(key, NT | (variant << 4) | (narrow << 8), split) == 0
     g = torch.Generator().manual_seed(sum(shape))
     x = torch.randn(B, Cin, H, W, generator=g)
     w = torch.randn(Cout, Cin, ks, ks, generator=g) * 0.1
@@ -227,9 +224,10 @@ def test_conv2d_pinned_tilings(emulated_kernels, shape, cfg):
     yr = F.conv2d(xr, wr, br, padding=ks // 2)
     dy = torch.randn(yr.shape, generator=g)
     yr.backward(dy)
-    P.check(ops.conv2d_forward(x, wf, b, Cout, ks), yr, 1e-5, 'fwd')
-    P.check(ops.conv2d_backward_data(dy, wb, Cin, ks), xr.grad, 1e-5, 'dgrad')
-    lib.pnsfm_set_conv_variant(0)      # clears the pinned entries
+    dec = tune.ConvDecision(NT, variant, narrow, split=split)
+    with tune.pinned(*[(tune.key(kind, B, K, M, H, W, ks), dec) for kind, K, M in ((0, Cin, Cout), (1, Cout, Cin))]):
+        P.check(ops.conv2d_forward(x, wf, b, Cout, ks), yr, 1e-5, 'fwd')
+        P.check(ops.conv2d_backward_data(dy, wb, Cin, ks), xr.grad, 1e-5, 'dgrad')
 
 
 _RB_CFGS = [(1, 3, 0, 1, 1), (2, 3, 0, 1, 1), (2, 4, 1, 2, 1), (1, 3, 0, 1, 2), (2, 5, 0, 1, 2), (2, 3, 1, 2, 2),
@@ -246,18 +244,14 @@ def test_conv2d_rect_and_band_tiles(emulated_kernels, shape, cfg):
     like the autotuner does: cfg = (NT, variant, narrow-M, K-split, tile mode) with tile mode 1 = 16-wide rectangles (16 x 8*NT),
     2 = bands of whole rows (W x floor(128*NT / W)); ragged last tiles in both directions, heights below the tile height.  The last
     two shapes are 32-multiple widths, where the 16-wide rectangles are offered to 5x5 / 7x7 layers only (a pinned band falls back)."""
-    import ctypes
     import torch.nn.functional as F
-    from packnet_sfm.hip import _lib, ops
+    from packnet_sfm.hip import _lib, ops, tune
     lib = _lib.get()
     NT, variant, narrow, split, tm = cfg
     lib.pnsfm_set_conv_math(1)
     B, Cin, Cout, H, W, ks = shape
     if tm == 2 and W > 128 * NT:
         pytest.skip('a row does not fit the tile')
-    for kind, K, M in ((0, Cin, Cout), (1, Cout, Cin)):
-        key = (ctypes.c_int * 7)(kind + 10 + 100, B, K, M, H, W, ks)
-        assert lib.pnsfm_tune_set(key, NT | (variant << 4) | (narrow << 8) | (tm << 9), split) == 0
     g = torch.Generator().manual_seed(sum(shape) + tm)
     x = torch.randn(B, Cin, H, W, generator=g)
     w = torch.randn(Cout, Cin, ks, ks, generator=g) * 0.1
@@ -267,26 +261,25 @@ def test_conv2d_rect_and_band_tiles(emulated_kernels, shape, cfg):
     yr = F.conv2d(xr, wr, br, padding=ks // 2)
     dy = torch.randn(yr.shape, generator=g)
     yr.backward(dy)
-    P.check(ops.conv2d_forward(x, wf, b, Cout, ks), yr, 1e-5, 'fwd')
-    P.check(ops.conv2d_backward_data(dy, wb, Cin, ks), xr.grad, 1e-5, 'dgrad')
-    lib.pnsfm_set_conv_variant(0)      # clears the pinned entries
+    dec = tune.ConvDecision(NT, variant, narrow, tm, split)
+    with tune.pinned(*[(tune.key(kind, B, K, M, H, W, ks), dec) for kind, K, M in ((0, Cin, Cout), (1, Cout, Cin))]):
+        P.check(ops.conv2d_forward(x, wf, b, Cout, ks), yr, 1e-5, 'fwd')
+        P.check(ops.conv2d_backward_data(dy, wb, Cin, ks), xr.grad, 1e-5, 'dgrad')
 
 
 @pytest.mark.parametrize('shape,split', [((1, 3, 64, 8, 64, 5), 1), ((2, 3, 64, 6, 40, 5), 3), ((1, 3, 40, 9, 136, 5), 4), ((3, 3, 24, 4, 8, 5), 2),
                                          ((2, 3, 32, 12, 64, 5), 100), ((1, 3, 70, 5, 72, 5), 2)])
 def test_conv2d_wgrad_stem_kernel(emulated_kernels, shape, split):
     """The stem's weight gradient on its own split-bf16 kernel (conv2d.hip: conv2d_wgrad_stem5_kernel -- 3 input channels, 5x5) vs torch,
-    the pixel split pinned through pnsfm_tune_set: direct stores (one split) and slabs, ragged tiles in both directions (6 / 9 / 5 rows
+    the pixel split pinned (tune.pinned): direct stores (one split) and slabs, ragged tiles in both directions (6 / 9 / 5 rows
     of 4-row tiles, 40 / 136 / 8 / 72 columns of 64-column tiles), both wave layouts (<= 32 channels: four pixel parts; more: two co
     tiles x two parts), padded co tiles (40, 24, 70 channels), more splits than tiles, several images."""
     import ctypes
     import torch.nn.functional as F
-    from packnet_sfm.hip import _lib, ops
+    from packnet_sfm.hip import _lib, ops, tune
     lib = _lib.get()
     lib.pnsfm_set_conv_math(1)
     B, Cin, Cout, H, W, ks = shape
-    key = (ctypes.c_int * 7)(2 + 10, B, Cin, Cout, H * W, W, ks)
-    assert lib.pnsfm_tune_set(key, split, 0) == 0
     g = torch.Generator().manual_seed(sum(shape) + split)
     x = torch.randn(B, Cin, H, W, generator=g)
     w = torch.randn(Cout, Cin, ks, ks, generator=g) * 0.1
@@ -295,22 +288,17 @@ def test_conv2d_wgrad_stem_kernel(emulated_kernels, shape, split):
     yr = F.conv2d(x, wr, br, padding=ks // 2)
     dy = torch.randn(yr.shape, generator=g)
     yr.backward(dy)
-    dw, db = ops.conv2d_backward_weight(x, dy, ks)
-    out = (ctypes.c_int * 8)()
-    tiles = B * -(-H // 4) * -(-W // 64)
-    assert lib.pnsfm_conv2d_last_config(out) == 0 and out[0] == 105 and out[4] == -(-tiles // -(-tiles // min(split, tiles))), list(out)
-    P.check(dw, wr.grad, 1e-5, 'wgrad (stem)')
-    P.check(db, br.grad, 1e-5, 'dbias (stem)')
-    lib.pnsfm_set_conv_math(0)           # the generic f32 kernel on the same data: the two agree to fp32 round-off
-    dw0, db0 = ops.conv2d_backward_weight(x, dy, ks)
-    lib.pnsfm_set_conv_math(1)
-    P.check(dw, dw0, 1e-5, 'wgrad (stem) vs generic')
-    lib.pnsfm_set_wgrad_variant(-1)      # clears the pinned entry
-
-
-def _flat32(H, W):
-    """launch_conv tiles a 1x1 layer whose H*W is a multiple of 32 (and W is not) as 32-wide rows: the tuning key carries those."""
-    return ((H * W) // 32, 32) if (H * W) % 32 == 0 and W % 32 != 0 else (H, W)
+    with tune.pinned((tune.key(tune.WGRAD, B, Cin, Cout, H, W, ks), tune.WgradDecision(0, split))):
+        dw, db = ops.conv2d_backward_weight(x, dy, ks)
+        out = (ctypes.c_int * 8)()
+        tiles = B * -(-H // 4) * -(-W // 64)
+        assert lib.pnsfm_conv2d_last_config(out) == 0 and out[0] == 105 and out[4] == -(-tiles // -(-tiles // min(split, tiles))), list(out)
+        P.check(dw, wr.grad, 1e-5, 'wgrad (stem)')
+        P.check(db, br.grad, 1e-5, 'dbias (stem)')
+        lib.pnsfm_set_conv_math(0)           # the generic f32 kernel on the same data: the two agree to fp32 round-off
+        dw0, db0 = ops.conv2d_backward_weight(x, dy, ks)
+        lib.pnsfm_set_conv_math(1)
+        P.check(dw, dw0, 1e-5, 'wgrad (stem) vs generic')
 
 
 @pytest.mark.parametrize('shape,cfg', [((2, 32, 64, 4, 40, 1), (1, 0, 1)), ((2, 32, 64, 4, 40, 1), (2, 0, 1)), ((1, 48, 33, 12, 40, 1), (1, 0, 1)),
@@ -324,15 +312,11 @@ def test_conv1x1_lds_free_kernel(emulated_kernels, shape, cfg):
     K splits with fewer chunks than the prefetch depth, several images."""
     import ctypes
     import torch.nn.functional as F
-    from packnet_sfm.hip import _lib, ops
+    from packnet_sfm.hip import _lib, ops, tune
     lib = _lib.get()
     NT, narrow, split = cfg
     lib.pnsfm_set_conv_math(1)
     B, Cin, Cout, H, W, ks = shape
-    Hk, Wk = _flat32(H, W)
-    for kind, K, M in ((0, Cin, Cout), (1, Cout, Cin)):
-        key = (ctypes.c_int * 7)(kind + 10 + 100, B, K, M, Hk, Wk, ks)
-        assert lib.pnsfm_tune_set(key, NT | (8 << 4) | (narrow << 8), split) == 0
     g = torch.Generator().manual_seed(sum(shape) + NT)
     x = torch.randn(B, Cin, H, W, generator=g)
     w = torch.randn(Cout, Cin, ks, ks, generator=g) * 0.1
@@ -343,11 +327,12 @@ def test_conv1x1_lds_free_kernel(emulated_kernels, shape, cfg):
     dy = torch.randn(yr.shape, generator=g)
     yr.backward(dy)
     out = (ctypes.c_int * 8)()
-    P.check(ops.conv2d_forward(x, wf, b, Cout, ks), yr, 1e-5, 'fwd (1x1, no LDS)')
-    assert lib.pnsfm_conv2d_last_config(out) == 0 and out[0] == 8 and out[1] == NT, list(out)
-    P.check(ops.conv2d_backward_data(dy, wb, Cin, ks), xr.grad, 1e-5, 'dgrad (1x1, no LDS)')
-    assert lib.pnsfm_conv2d_last_config(out) == 0 and out[0] == 8, list(out)
-    lib.pnsfm_set_conv_variant(0)      # clears the pinned entries
+    dec = tune.ConvDecision(NT, 8, narrow, split=split)
+    with tune.pinned(*[(tune.key(kind, B, K, M, H, W, ks), dec) for kind, K, M in ((0, Cin, Cout), (1, Cout, Cin))]):
+        P.check(ops.conv2d_forward(x, wf, b, Cout, ks), yr, 1e-5, 'fwd (1x1, no LDS)')
+        assert lib.pnsfm_conv2d_last_config(out) == 0 and out[0] == 8 and out[1] == NT, list(out)
+        P.check(ops.conv2d_backward_data(dy, wb, Cin, ks), xr.grad, 1e-5, 'dgrad (1x1, no LDS)')
+        assert lib.pnsfm_conv2d_last_config(out) == 0 and out[0] == 8, list(out)
 
 
 def test_conv1x1_lds_free_pin_falls_back_for_several_sources(emulated_kernels):
@@ -357,14 +342,13 @@ def test_conv1x1_lds_free_pin_falls_back_for_several_sources(emulated_kernels):
     had this check the cat call raised HipError ('the LDS-free 1x1 kernel reads one input tensor')."""
     import ctypes
     import torch.nn.functional as F
-    from packnet_sfm.hip import _lib, ops
+    from packnet_sfm.hip import _lib, ops, tune
     lib = _lib.get()
     lib.pnsfm_set_conv_math(1)
     B, C0, C1, Cout, H, W, ks = 1, 16, 16, 32, 4, 32, 1
-    assert _flat32(H, W) == (H, W)           # 32-wide already: launch_conv does not re-tile, the key carries H x W as they are
-    key = (ctypes.c_int * 7)(110, 1, 32, 32, 4, 32, 1)
+    key = tune.key(tune.FORWARD, B, C0 + C1, Cout, H, W, ks)        # 32-wide already: the key carries H x W as they are
+    assert key == tune.key(tune.FORWARD, B, C0 + C1, Cout, H, W, ks, sources=2)      # ... and no bit for several input tensors
     assert list(key) == [0 + 10 + 100, B, C0 + C1, Cout, H, W, ks]
-    assert lib.pnsfm_tune_set(key, 1 | (8 << 4), 1) == 0
     g = torch.Generator().manual_seed(1632)
     x0, x1 = torch.randn(B, C0, H, W, generator=g), torch.randn(B, C1, H, W, generator=g)
     w = torch.randn(Cout, C0 + C1, ks, ks, generator=g) * 0.1
@@ -372,12 +356,12 @@ def test_conv1x1_lds_free_pin_falls_back_for_several_sources(emulated_kernels):
     wf, _ = ops.conv2d_pack(w)
     yr = F.conv2d(torch.cat([x0, x1], 1), w, b)
     out = (ctypes.c_int * 8)()
-    y = ops.conv2d_forward_cat([x0, x1], wf, b, Cout, ks)
-    assert ops.conv2d_last_config()[0] != 8, ops.conv2d_last_config()
-    P.check(y, yr, 1e-5, 'fwd (1x1, two sources, variant-8 pin ignored)')
-    P.check(ops.conv2d_forward(torch.cat([x0, x1], 1), wf, b, Cout, ks), yr, 1e-5, 'fwd (1x1, no LDS)')
-    assert lib.pnsfm_conv2d_last_config(out) == 0 and out[0] == 8 and out[1] == 1, list(out)
-    lib.pnsfm_set_conv_variant(0)      # clears the pinned entry
+    with tune.pinned((key, tune.ConvDecision(1, 8))):
+        y = ops.conv2d_forward_cat([x0, x1], wf, b, Cout, ks)
+        assert ops.conv2d_last_config()[0] != 8, ops.conv2d_last_config()
+        P.check(y, yr, 1e-5, 'fwd (1x1, two sources, variant-8 pin ignored)')
+        P.check(ops.conv2d_forward(torch.cat([x0, x1], 1), wf, b, Cout, ks), yr, 1e-5, 'fwd (1x1, no LDS)')
+        assert lib.pnsfm_conv2d_last_config(out) == 0 and out[0] == 8 and out[1] == 1, list(out)
 
 
 @pytest.mark.parametrize('shape', [(1, 64, 64, 4, 32, 3), (2, 33, 70, 5, 16, 3), (1, 130, 20, 9, 8, 3), (2, 16, 96, 3, 64, 1),
@@ -439,21 +423,18 @@ def test_conv2d_wgrad_split_bf16(emulated_kernels, shape):
 @pytest.mark.parametrize('cfg', [(1, 1, 1), (1, 1, 2), (2, 1, 1), (2, 2, 2), (3, 1, 4), (1, 1, 9), (2, 1, 12), (2, 1, 10)])
 @pytest.mark.parametrize('shape', [(1, 64, 128, 8, 32, 3), (2, 48, 160, 5, 40, 3), (1, 32, 100, 6, 24, 5)])
 def test_conv2d_wgrad_split_bf16_pinned(emulated_kernels, shape, cfg):
-    """wgrad3 configurations the autotuner explores on the GPU, pinned through pnsfm_tune_set: cfg = (pixel split, ci tiles per
+    """wgrad3 configurations the autotuner explores on the GPU, pinned (tune.pinned): cfg = (pixel split, ci tiles per
     wave NT, co tiles per workgroup WM; WM | 8 = the build whose register budget lets three workgroups share a CU) -- WM below the
-    layer's maximum turns waves into extra pixel shares (LDS reduction).  The build that ran is read back (wgrad_cases.launched_build):
+    layer's maximum turns waves into extra pixel shares (LDS reduction).  The build that ran is read back (tune.last_config):
     NT = 2 runs as NT = 1 on the 5x5 shape (two ci tiles per wave exist for 1x1 and 3x3 only) and on the Cout = 128, W = 32 shape
     when all four co tiles are asked for (the "tight" re-route of enqueue_wgrad3, which also drops | 8: cfg (2, 1, 12) runs
     <3, 1, 4, 32, OCC 2> there); elsewhere WM | 8 is the OCC = 3 build on the 3x3 shapes with NT = 1, and plain OCC = 2 on the 5x5 one."""
-    import ctypes
     import torch.nn.functional as F
-    from packnet_sfm.hip import _lib, ops
+    from packnet_sfm.hip import _lib, ops, tune
     lib = _lib.get()
     lib.pnsfm_set_conv_math(1)
     split, NT, WM = cfg
     B, Cin, Cout, H, W, ks = shape
-    key = (ctypes.c_int * 7)(2 + 10 + 100, B, Cin, Cout, H * W, W, ks)
-    assert lib.pnsfm_tune_set(key, split, 2 | (NT << 4) | (WM << 6)) == 0
     g = torch.Generator().manual_seed(sum(shape))
     x = torch.randn(B, Cin, H, W, generator=g)
     w = torch.randn(Cout, Cin, ks, ks, generator=g) * 0.1
@@ -462,18 +443,19 @@ def test_conv2d_wgrad_split_bf16_pinned(emulated_kernels, shape, cfg):
     yr = F.conv2d(x, wr, br, padding=ks // 2)
     dy = torch.randn(yr.shape, generator=g)
     yr.backward(dy)
-    dw, db = ops.conv2d_backward_weight(x, dy, ks)
+    with tune.pinned((tune.key(tune.WGRAD, B, Cin, Cout, H, W, ks), tune.WgradDecision(2, split, NT=NT, wm=WM))):
+        dw, db = ops.conv2d_backward_weight(x, dy, ks)
+        last = tune.last_config()
     most = 4 if Cout > 96 else (2 if Cout > 32 else 1)
     WMr = (WM & 7) if (WM & 7) < most else most
     tight = ks == 3 and WMr == 4 and W == 32
     NTr = NT if (ks <= 3 and Cin > 32 and not tight) else 1
     TC = 16 if W == 40 else 32                          # W = 40: three 16-column tiles waste fewer columns than two 32-column ones
-    cfg_ran = ops.conv2d_last_config()
-    assert WC.launched_build(cfg_ran) == (103, ks, NTr, WMr, TC, 0, 3 if (WM & 8 and ks == 3 and NTr == 1 and not tight) else 2), cfg_ran
+    cfg_ran = last.raw
+    assert last.build == (103, ks, NTr, WMr, TC, 0, 3 if (WM & 8 and ks == 3 and NTr == 1 and not tight) else 2), cfg_ran
     assert cfg_ran[4] == WC.clamped_split(WC.launched_tiles(cfg_ran, B, H, W, ks), split), cfg_ran
     P.check(dw, wr.grad, 1e-5, 'wgrad (split-bf16, pinned)')
     P.check(db, br.grad, 1e-5, 'dbias (split-bf16, pinned)')
-    lib.pnsfm_set_wgrad_variant(-1)      # clears the pinned entry
 
 
 # every configuration on the first two shapes, a rotating 3 of 5 on the others (CPU-suite time)
@@ -483,13 +465,12 @@ def test_conv2d_wgrad_split_bf16_pinned(emulated_kernels, shape, cfg):
                                        if i < 2 or (i + j) % 5 in (0, 2, 3)])
 def test_conv2d_wgrad_nine_taps(emulated_kernels, shape, cfg):
     """The nine-taps-per-workgroup 3x3 weight gradient on the 16x16x32 MFMA (csrc/conv2d_wgrad4.hip) vs torch, pinned through
-    pnsfm_tune_set (variant 3): cfg = (pixel split, ci tiles per workgroup, tile width in 8-pixel groups, tile rows; 0 = the
+    tune.pinned (kernel 3): cfg = (pixel split, ci tiles per workgroup, tile width in 8-pixel groups, tile rows; 0 = the
     library's choice).  Widths of 3 / 4 / 5 groups incl. ragged last tiles (W = 80 with 32-column tiles), W % 8 == 4 (masked half
     groups: 20, 4), one-group images, 6-row tiles whose last k-step is partly empty, heights that do not fill the tile rows,
     odd channel counts, direct stores (one split) and the two-stage reduction."""
-    import ctypes
     import torch.nn.functional as F
-    from packnet_sfm.hip import _lib, ops
+    from packnet_sfm.hip import _lib, ops, tune
     lib = _lib.get()
     lib.pnsfm_set_conv_math(1)
     split, WCI, TG, TR = cfg
@@ -498,8 +479,6 @@ def test_conv2d_wgrad_nine_taps(emulated_kernels, shape, cfg):
         TG = 0                      # narrow images have one legal width (3 groups)
     elif TR == 6:
         TR = 0                      # 6-row tiles exist for 3-group tiles only
-    key = (ctypes.c_int * 7)(2 + 10 + 100, B, Cin, Cout, H * W, W, ks)
-    assert lib.pnsfm_tune_set(key, split, 3 | ((WCI | (TG << 4) | (TR << 8)) << 4)) == 0
     g = torch.Generator().manual_seed(sum(shape))
     x = torch.randn(B, Cin, H, W, generator=g)
     w = torch.randn(Cout, Cin, ks, ks, generator=g) * 0.1
@@ -508,15 +487,15 @@ def test_conv2d_wgrad_nine_taps(emulated_kernels, shape, cfg):
     yr = F.conv2d(x, wr, br, padding=ks // 2)
     dy = torch.randn(yr.shape, generator=g)
     yr.backward(dy)
-    dw, db = ops.conv2d_backward_weight(x, dy, ks)
-    cfg_ran = ops.conv2d_last_config()
-    build = WC.launched_build(cfg_ran)
+    with tune.pinned((tune.key(tune.WGRAD, B, Cin, Cout, H, W, ks), tune.WgradDecision(3, split, WCI=WCI, TG=TG, TR=TR))):
+        dw, db = ops.conv2d_backward_weight(x, dy, ks)
+        last = tune.last_config()
+    cfg_ran, build = last.raw, last.build
     assert build[0] == 104 and build[1] == WCI and build[4] == (1 if W % 8 else 0), cfg_ran
     assert build[2] == (3 if W <= 24 else (TG or build[2])) and build[3] == (TR or build[3]) and build[2:4] in ((3, 4), (3, 6), (4, 4), (5, 4)), cfg_ran
     assert cfg_ran[4] == WC.clamped_split(WC.launched_tiles(cfg_ran, B, H, W, ks), split), cfg_ran
     P.check(dw, wr.grad, 1e-5, 'wgrad (nine taps)')
     P.check(db, br.grad, 1e-5, 'dbias (nine taps)')
-    lib.pnsfm_set_wgrad_variant(-1)      # clears the pinned entry
 
 
 def test_wgrad_ladder_table_is_sound():
@@ -848,43 +827,39 @@ def test_conv_gn_act_fused_block(emulated_kernels, shape, variant):
     """The Conv2D block as one autograd node (hip.functional.ConvGnActFn; since round 6 its two bodies are single calls into the block
     sequencer, csrc/seq/pnsfm_seq.cpp) against the two-node form (conv, then GroupNorm + activation) and against torch: output and every
     gradient.  Channels per group 4 / 8 / 16 / 32, ragged tiles, the ping-pong kernel (7), three workgroups per CU (6), the f32 kernels (0)."""
-    import ctypes
     import torch.nn.functional as F
-    from packnet_sfm.hip import _lib, functional as HF, ops
+    from packnet_sfm.hip import _lib, functional as HF, ops, tune
     lib = _lib.get()
     B, Cin, Cout, H, W, ks = shape
     bx3 = variant >= 3 and Cin >= 16
     lib.pnsfm_set_conv_math(1 if variant >= 3 else 0)
     lib.pnsfm_set_conv_variant(variant if variant < 7 else 3)
-    if variant == 7 and bx3:
-        for kind, K, M in ((0, Cin, Cout), (1, Cout, Cin)):
-            key = (ctypes.c_int * 7)(kind + 10 + 100, B, K, M, H, W, ks)
-            assert lib.pnsfm_tune_set(key, 1 | (7 << 4), 1) == 0
-    g = torch.Generator().manual_seed(sum(shape) + variant)
-    x = torch.randn(B, Cin, H, W, generator=g)
-    w = torch.randn(Cout, Cin, ks, ks, generator=g) * 0.2
-    b = torch.randn(Cout, generator=g)
-    gamma, beta = torch.rand(Cout, generator=g) + 0.5, torch.randn(Cout, generator=g) * 0.1
-    dout = torch.randn(B, Cout, H, W, generator=g)
-    res = {}
-    for fused in (True, False):
-        HF.set_conv_gn_fuse(fused)
-        leaves = [t.clone().requires_grad_(True) for t in (x, w, b, gamma, beta)]
-        out = HF.conv2d_gn_act(leaves[0], leaves[1], leaves[2], leaves[3], leaves[4], HF.PackedConvWeight(), 16, 1e-5, ops.ACT_ELU)
-        out.backward(dout)
-        res[fused] = [out.detach()] + [t.grad for t in leaves]
-    HF.set_conv_gn_fuse(True)
-    ref = [t.clone().requires_grad_(True) for t in (x, w, b, gamma, beta)]
-    o = F.elu(F.group_norm(F.conv2d(ref[0], ref[1], ref[2], padding=ks // 2), 16, ref[3], ref[4], 1e-5))
-    o.backward(dout)
-    names = ('out', 'dx', 'dw', 'db', 'dgamma', 'dbeta')
-    for n, a, c, r in zip(names, res[True], res[False], [o.detach()] + [t.grad for t in ref]):
-        # (the conv bias in front of a GroupNorm has a mathematically zero gradient: round-off in every implementation)
-        if n == 'db':
-            continue
-        P.check(a, c, 2e-5, n + ' fused vs two nodes')
-        P.check(a, r, 1e-4, n + ' vs torch')
-    lib.pnsfm_set_conv_variant(0)
+    pins = [(tune.key(kind, B, K, M, H, W, ks), tune.ConvDecision(1, 7)) for kind, K, M in ((0, Cin, Cout), (1, Cout, Cin))] if variant == 7 and bx3 else []
+    with tune.pinned(*pins):
+        g = torch.Generator().manual_seed(sum(shape) + variant)
+        x = torch.randn(B, Cin, H, W, generator=g)
+        w = torch.randn(Cout, Cin, ks, ks, generator=g) * 0.2
+        b = torch.randn(Cout, generator=g)
+        gamma, beta = torch.rand(Cout, generator=g) + 0.5, torch.randn(Cout, generator=g) * 0.1
+        dout = torch.randn(B, Cout, H, W, generator=g)
+        res = {}
+        for fused in (True, False):
+            HF.set_conv_gn_fuse(fused)
+            leaves = [t.clone().requires_grad_(True) for t in (x, w, b, gamma, beta)]
+            out = HF.conv2d_gn_act(leaves[0], leaves[1], leaves[2], leaves[3], leaves[4], HF.PackedConvWeight(), 16, 1e-5, ops.ACT_ELU)
+            out.backward(dout)
+            res[fused] = [out.detach()] + [t.grad for t in leaves]
+        HF.set_conv_gn_fuse(True)
+        ref = [t.clone().requires_grad_(True) for t in (x, w, b, gamma, beta)]
+        o = F.elu(F.group_norm(F.conv2d(ref[0], ref[1], ref[2], padding=ks // 2), 16, ref[3], ref[4], 1e-5))
+        o.backward(dout)
+        names = ('out', 'dx', 'dw', 'db', 'dgamma', 'dbeta')
+        for n, a, c, r in zip(names, res[True], res[False], [o.detach()] + [t.grad for t in ref]):
+            # (the conv bias in front of a GroupNorm has a mathematically zero gradient: round-off in every implementation)
+            if n == 'db':
+                continue
+            P.check(a, c, 2e-5, n + ' fused vs two nodes')
+            P.check(a, r, 1e-4, n + ' vs torch')
 
 
 def test_flat_adam_fused_tail(emulated_kernels):
@@ -1207,13 +1182,12 @@ WGRAD_CAT_PINNED = [((32, 16), 32, 1, 6, 20, 2, 4), ((32, 32, 16), 48, 2, 5, 40,
 
 
 def _check_wgrad_cat_pinned(device, case, kernel, tol):
-    """ops.conv2d_backward_weight_cat with the decision pinned through pnsfm_tune_set (multi-source key: kind 2 + 10 + 100 + 1000) to
+    """ops.conv2d_backward_weight_cat with the decision pinned (tune.pinned; multi-source key: tune.key(..., sources=n)) to
     kernel 3 (nine taps, two ci tiles per workgroup, library tile width) or 2 (wgrad3, one ci tile per wave), vs F.conv2d's autograd on
     the concatenated tensor.  The tile counts are worked out here so that the pinned split is one the kernels keep
     (conv2d_wgrad_bx3.h clamps it to the tile count); the build and the split that ran are read back (pnsfm_conv2d_last_config)."""
-    import ctypes
     import torch.nn.functional as F
-    from packnet_sfm.hip import _lib, ops
+    from packnet_sfm.hip import _lib, ops, tune
     lib = _lib.get()
     lib.pnsfm_set_conv_math(1)
     Cs, Cout, B, H, W, split, TR = case
@@ -1222,8 +1196,8 @@ def _check_wgrad_cat_pinned(device, case, kernel, tol):
     tiles4 = B * -(-W // (8 * TG)) * -(-H // (TR or 4))                                    # nine taps: TR x 8 TG pixel tiles
     tiles3 = B * -(-W // 16) * -(-H // 4)                                                  # wgrad3: 4 x 16 (both widths: 16 wastes fewer columns / W % 8 == 4)
     assert split <= (tiles4 if kernel == 3 else tiles3), 'the pinned pixel split would be clamped'
-    key = (ctypes.c_int * 7)(2 + 10 + 100 + 1000, B, Cin, Cout, H * W, W, 3)
-    assert lib.pnsfm_tune_set(key, split, (3 | ((2 | (TR << 8)) << 4)) if kernel == 3 else (2 | (1 << 4))) == 0
+    key = tune.key(tune.WGRAD, B, Cin, Cout, H, W, 3, sources=len(Cs))
+    dec = tune.WgradDecision(3, split, WCI=2, TR=TR) if kernel == 3 else tune.WgradDecision(2, split, NT=1)
     g = torch.Generator().manual_seed(Cin + Cout + H + W)
     xs = [torch.randn(B, c, H, W, generator=g) for c in Cs]
     w = torch.randn(Cout, Cin, 3, 3, generator=g) * 0.1
@@ -1232,10 +1206,10 @@ def _check_wgrad_cat_pinned(device, case, kernel, tol):
     yr = F.conv2d(torch.cat(xs, 1), wr, br, padding=1)
     dy = torch.randn(yr.shape, generator=g)
     yr.backward(dy)
-    try:
+    with tune.pinned((key, dec)):
         dw, db = ops.conv2d_backward_weight_cat([t.to(device) for t in xs], dy.to(device), 3)
-        cfg_ran = ops.conv2d_last_config()
-        build = WC.launched_build(cfg_ran)
+        last = tune.last_config()
+        cfg_ran, build = last.raw, last.build
         if kernel == 3:
             assert build == (104, 2, TG, TR or build[3], 1 if W % 8 else 0) and build[3] in (4, 6), cfg_ran
         else:
@@ -1243,8 +1217,6 @@ def _check_wgrad_cat_pinned(device, case, kernel, tol):
         assert cfg_ran[4] == split, cfg_ran
         P.check(dw, wr.grad, tol, 'wgrad (cat, kernel %d)' % kernel)
         P.check(db, br.grad, tol, 'dbias (cat, kernel %d)' % kernel)
-    finally:
-        lib.pnsfm_set_wgrad_variant(-1)      # clears the pinned entry
 
 
 @pytest.mark.parametrize('kernel', [3, 2])
@@ -1261,26 +1233,21 @@ def test_conv2d_wgrad_cat_pinned_kernel(emulated_kernels, case, kernel):
 def test_conv2d_backward_data_addend(emulated_kernels, shape, cfg):
     """Round 5: dx = backward-data + addend in the launch's epilogue (un-split) / in the second stage of a K-split launch, for a dense
     addend and for a channel slice of a wider tensor: the bits of the separate elementwise sum."""
-    import ctypes
-    from packnet_sfm.hip import _lib, ops
+    from packnet_sfm.hip import _lib, ops, tune
     lib = _lib.get()
     NT, variant, narrow, split = cfg
     lib.pnsfm_set_conv_math(1)
     B, Cin, Cout, H, W, ks = shape
-    key = (ctypes.c_int * 7)(1 + 10 + 100, B, Cout, Cin, H, W, ks)
-    assert lib.pnsfm_tune_set(key, NT | (variant << 4) | (narrow << 8), split) == 0
     g = torch.Generator().manual_seed(sum(shape) + sum(cfg))
     w = torch.randn(Cout, Cin, ks, ks, generator=g) * 0.1
     _, wb = ops.conv2d_pack(w)
     dy = torch.randn(B, Cout, H, W, generator=g)
     wide = torch.randn(B, Cin + 7, H, W, generator=g)
-    try:
+    with tune.pinned((tune.key(tune.BACKWARD_DATA, B, Cout, Cin, H, W, ks), tune.ConvDecision(NT, variant, narrow, split=split))):
         plain = ops.conv2d_backward_data(dy, wb, Cin, ks)
         for addend in (wide[:, :Cin].contiguous(), wide[:, 5:5 + Cin], wide[:, 5:5 + Cin].permute(0, 1, 3, 2).contiguous().permute(0, 1, 3, 2)):
             got = ops.conv2d_backward_data(dy, wb, Cin, ks, addend=addend)
             assert torch.equal(got, plain + addend)
-    finally:
-        lib.pnsfm_set_conv_variant(0)      # clears the pinned entries
 
 
 def test_gradient_taps_match_the_plain_graph(emulated_kernels):
@@ -1452,3 +1419,22 @@ def test_conv_nodes_sequencer_and_python_bodies(emulated_kernels, Cs, tap, gn):
         e = P.err(v, r, floor=dw_max if (gn and n == 'db') else 0.0)
         print('%s %s tap=%s gn=%s: %.3e' % (n, Cs, tap, gn, e))
         assert e <= tol, '%s vs torch: relative error %.3e > %.1e' % (n, e, tol)
+
+
+# ---- tuning key, decision codec and their Python face (packnet_sfm/hip/tune.py): the case table of tests/tune_cases.py
+def test_tune_codec_round_trips_every_database_line():
+    TC.check_codec_round_trip()
+
+
+def test_tune_codec_matches_recorded_configurations():
+    TC.check_codec_against_recorded_configurations()
+
+
+def test_tune_key_reproduces_database_lines(emulated_kernels):
+    TC.check_key_reproduces_database_lines()
+
+
+@pytest.mark.parametrize('case', TC.LAUNCH_CASES, ids=TC.LAUNCH_IDS)
+def test_tune_launch_case_emulated(emulated_kernels, case):
+    """One pinned launch per key rule (1e-5: this file's tolerance for every one of these kernels)."""
+    TC.run_launch_case('cpu', case, 1e-5, 1e-5)

@@ -5,17 +5,17 @@
   conv2d_wgrad4_kernel<WCI, TG, TR, MASKED>           16 builds             (csrc/conv2d_wgrad4.hip: enqueue_wgrad4)
   conv2d_wgrad_kernel<MT> at stride 2                 2 builds x 2 tile modes (csrc/conv2d.hip: enqueue_wgrad_generic)
 
--- pinned through pnsfm_tune_set and checked against a float64 unfold + matmul on the CPU.  A case states the build it must launch;
-run_case() reads the build that DID launch back through pnsfm_conv2d_last_config (a pin that the library re-routes or drops fails
+-- pinned (packnet_sfm.hip.tune) and checked against a float64 unfold + matmul on the CPU.  A case states the build it must launch;
+run_case() reads the build that DID launch back through tune.last_config (a pin that the library re-routes or drops fails
 there, before any number is compared), so the table's coverage of the ladders is proven by the library, not by a copy of its dispatch.
 
 Bounds (tests/test_gpu_round3.py: the project's own measure at the training step's reduction lengths):
   max |dW - dW64| / sum |dY||X| <= 16 * 2^-24      max |db - db64| / sum |dY| <= 1.5e-7
 A kernel that drops one of the six bf16 piece products is off by ~2^-16 of |dy||x| on the elements it hits: 250 x the bound."""
-import ctypes
-
 import torch
 import torch.nn.functional as F
+
+from packnet_sfm.hip import tune
 
 DW_BOUND = 16 * 2.0 ** -24
 DB_BOUND = 1.5e-7
@@ -42,23 +42,8 @@ def wgrad_fp64(x, dy, ks, stride=1):
 
 
 # ------------------------------------------------------------------------------------------------ the read-back
-def launched_build(cfg):
-    """The eight ints of pnsfm_conv2d_last_config after a weight-gradient launch (include/pnsfm.h) -> the build that ran:
-    (103, KS, NT, WM, TC, masked, OCC) | (104, WCI, TG, TR, masked) | (100, stride, MT, tile mode) | (102,) | (105, MT)."""
-    code = cfg[0]
-    if code == 103:
-        return (103, cfg[5] >> 8, cfg[1], cfg[2], cfg[3], (cfg[5] >> 4) & 1, cfg[5] & 15)
-    if code == 104:
-        return (104, cfg[1], cfg[2], cfg[3], (cfg[5] >> 4) & 1)
-    if code == 100:
-        return (100, cfg[1], cfg[2], cfg[5])
-    if code == 105:
-        return (105, cfg[2])
-    return (code,)
-
-
 def launched_tiles(cfg, B, H, W, ks):
-    """Pixel tiles of the launch `cfg` describes (the unit the pixel split divides), from the tile shape it reports.  H, W: the map of
+    """Pixel tiles of the launch `cfg` (the eight ints of pnsfm_conv2d_last_config: tune.last_config().raw) describes (the unit the pixel split divides), from the tile shape it reports.  H, W: the map of
     dY; a 1x1 layer's map is handed to wgrad3 as 32-wide rows of the flattened image when that is exact."""
     code = cfg[0]
     if code == 103:
@@ -85,18 +70,17 @@ def clamped_split(tiles, split):
 
 # ------------------------------------------------------------------------------------------------ the table
 # A case: id, shape (B, Cin, Cout, H, W, ks) with H, W the map of x, srcs (channel counts of a multi-source launch, or None), stride,
-# dec = (v0, v1) of pnsfm_tune_set (v0 = pixel split; v1 per the codec table of csrc/conv2d.hip), build = what launched_build() must
-# return.
-def _case(name, shape, v1, split, build, srcs=None, stride=1):
-    return dict(id=name, shape=shape, srcs=srcs, stride=stride, dec=(split, v1), build=build)
+# dec = the tune.WgradDecision to pin (`kernel`: one without its pixel split), build = what tune.last_config().build must return.
+def _case(name, shape, kernel, split, build, srcs=None, stride=1):
+    return dict(id=name, shape=shape, srcs=srcs, stride=stride, dec=kernel._replace(split=split), build=build)
 
 
-def _v3(NT, wm):
-    return 2 | (NT << 4) | (wm << 6)
+def _w3(NT, wm):
+    return tune.WgradDecision(2, NT=NT, wm=wm)
 
 
-def _v4(WCI, TG, TR):
-    return 3 | ((WCI | (TG << 4) | (TR << 8)) << 4)
+def _w4(WCI, TG, TR):
+    return tune.WgradDecision(3, WCI=WCI, TG=TG, TR=TR)
 
 
 # wgrad3.  Cout 24 / 40 / 100 fills 1 / 2 / 4 co tiles per workgroup (all ragged against the 32-row tile); Cin 48 = two 32-channel
@@ -124,11 +108,11 @@ def _wgrad3_cases():
                         continue            # no such build: the request runs <3, 1, 4, 32> (enqueue_wgrad3, "tight")
                     B, H, W, split = maps[ks]
                     out.append(_case('w3-k%d-nt%d-wm%d-tc%d%s' % (ks, NT, WM, TC, 'm' if masked else ''),
-                                     (B, _W3_CIN[NT], _W3_COUT[WM], H, W, ks), _v3(NT, 0), split, (103, ks, NT, WM, TC, masked, 2)))
+                                     (B, _W3_CIN[NT], _W3_COUT[WM], H, W, ks), _w3(NT, 0), split, (103, ks, NT, WM, TC, masked, 2)))
     # the three-workgroups-per-CU builds: wm | 8 on a 3x3 layer, NT = 1, not masked; <3, 1, 4, 32, OCC 3> does not exist
     for WM, TC in ((1, 32), (2, 32), (1, 16), (2, 16), (4, 16)):
         B, H, W, split = _W3_MAP[(TC, 0)][3]
-        out.append(_case('w3-k3-nt1-wm%d-tc%d-occ3' % (WM, TC), (B, 48, _W3_COUT[WM], H, W, 3), _v3(1, 8), split, (103, 3, 1, WM, TC, 0, 3)))
+        out.append(_case('w3-k3-nt1-wm%d-tc%d-occ3' % (WM, TC), (B, 48, _W3_COUT[WM], H, W, 3), _w3(1, 8), split, (103, 3, 1, WM, TC, 0, 3)))
     # WM below the layer's maximum: the same builds as a small Cout, but several co groups and WK = 4 / WM pixel shares per workgroup
     # summed through LDS (one row per kernel size and tile form, both NT, one OCC = 3)
     for ks, NT, wm, key, occ in ((1, 1, 1, (32, 0), 0), (1, 2, 2, (16, 1), 0), (3, 1, 1, (16, 0), 0), (3, 1, 2, (32, 0), 0),
@@ -136,7 +120,7 @@ def _wgrad3_cases():
                                  (5, 1, 1, (16, 1), 0), (5, 1, 2, (32, 0), 0), (7, 1, 2, (16, 0), 0), (7, 1, 1, (32, 0), 0)):
         B, H, W, split = _W3_MAP[key][ks]
         out.append(_case('w3-k%d-nt%d-wm%d-tc%d%s%s-cout100' % (ks, NT, wm, key[0], 'm' if key[1] else '', '-occ3' if occ else ''),
-                         (B, _W3_CIN[NT], 100, H, W, ks), _v3(NT, wm | occ), split, (103, ks, NT, wm, key[0], key[1], 3 if occ else 2)))
+                         (B, _W3_CIN[NT], 100, H, W, ks), _w3(NT, wm | occ), split, (103, ks, NT, wm, key[0], key[1], 3 if occ else 2)))
     return out
 
 
@@ -161,7 +145,7 @@ def _wgrad4_cases():
             Cout = 100 if (WCI + TG + masked) % 2 else 40
             pinTG = 0 if W <= 24 else TG      # narrow images have one legal width (3 groups); the tile rows are always pinned
             out.append(_case('w4-wci%d-tg%d-tr%d%s' % (WCI, TG, TR, 'm' if masked else ''), (B, 40, Cout, H, W, 3),
-                             _v4(WCI, pinTG, TR), split, (104, WCI, TG, TR, masked)))
+                             _w4(WCI, pinTG, TR), split, (104, WCI, TG, TR, masked)))
     return out
 
 
@@ -169,10 +153,10 @@ def _cat_cases():
     # several input tensors (key kind + 1000): 32 + 48 channels -- the second tensor starts inside the launch's second 32-channel tile
     # row of workgroups -- and 64 + 16 for the 64-channel tiles of NT = 2
     return [
-        _case('cat-w3-k3-nt2-wm2-tc16', (3, 80, 40, 6, 48, 3), _v3(2, 0), 4, (103, 3, 2, 2, 16, 0, 2), srcs=(64, 16)),
-        _case('cat-w3-k3-nt1-wm2-tc32-occ3', (3, 80, 40, 9, 32, 3), _v3(1, 8), 2, (103, 3, 1, 2, 32, 0, 3), srcs=(32, 48)),
-        _case('cat-w3-k5-nt1-wm1-tc16m', (3, 80, 24, 9, 20, 5), _v3(1, 0), 4, (103, 5, 1, 1, 16, 1, 2), srcs=(32, 48)),
-        _case('cat-w4-wci2-tg4-tr4m', (3, 80, 40, 9, 44, 3), _v4(2, 4, 4), 4, (104, 2, 4, 4, 1), srcs=(32, 48)),
+        _case('cat-w3-k3-nt2-wm2-tc16', (3, 80, 40, 6, 48, 3), _w3(2, 0), 4, (103, 3, 2, 2, 16, 0, 2), srcs=(64, 16)),
+        _case('cat-w3-k3-nt1-wm2-tc32-occ3', (3, 80, 40, 9, 32, 3), _w3(1, 8), 2, (103, 3, 1, 2, 32, 0, 3), srcs=(32, 48)),
+        _case('cat-w3-k5-nt1-wm1-tc16m', (3, 80, 24, 9, 20, 5), _w3(1, 0), 4, (103, 5, 1, 1, 16, 1, 2), srcs=(32, 48)),
+        _case('cat-w4-wci2-tg4-tr4m', (3, 80, 40, 9, 44, 3), _w4(2, 4, 4), 4, (104, 2, 4, 4, 1), srcs=(32, 48)),
     ]
 
 
@@ -183,7 +167,7 @@ def _generic_cases():
     for ks, Cout, Wo, B, Ho, split in ((3, 24, 32, 3, 9, 2), (3, 40, 20, 3, 13, 2), (5, 72, 32, 3, 9, 2), (5, 24, 20, 3, 13, 2),
                                        (7, 40, 32, 5, 6, 3), (7, 72, 20, 3, 13, 2), (3, 72, 32, 3, 9, 2), (5, 40, 32, 3, 9, 2)):
         MT, mode = (2 if Cout == 40 else 1), (0 if Wo % 32 == 0 else 1)
-        out.append(_case('gen-s2-k%d-cout%d-mt%d-mode%d' % (ks, Cout, MT, mode), (B, 20, Cout, 2 * Ho, 2 * Wo, ks), 0, split,
+        out.append(_case('gen-s2-k%d-cout%d-mt%d-mode%d' % (ks, Cout, MT, mode), (B, 20, Cout, 2 * Ho, 2 * Wo, ks), tune.WgradDecision(0), split,
                          (100, 2, MT, mode), stride=2))
     return out
 
@@ -216,7 +200,7 @@ def check_table():
     have = {c['build'] for c in CASES if c['build'][0] in (103, 104)}
     assert have == expected_builds(), (sorted(expected_builds() - have), sorted(have - expected_builds()))
     for c in CASES:
-        assert c['dec'][0] > 1, c['id']
+        assert c['dec'].split > 1, c['id']
 
 
 # ------------------------------------------------------------------------------------------------ the checker
@@ -232,7 +216,7 @@ def _slot(shape, device):
 
 
 def _launch(ops, case, xs, dy):
-    """One launch into fresh NaN slots; (dw, db, last_config) after the guard and coverage checks."""
+    """One launch into fresh NaN slots; ((whole, dw), (whole, db), tune.last_config()) -- the caller checks guards and coverage."""
     B, Cin, Cout, H, W, ks = case['shape']
     dev = dy.device
     wdw, dw = _slot((Cout, Cin, ks, ks), dev)
@@ -243,7 +227,7 @@ def _launch(ops, case, xs, dy):
         ops.conv2d_backward_weight_strided(xs[0], dy, ks, 2, dw_out=dw, db_out=db)
     else:
         ops.conv2d_backward_weight(xs[0], dy, ks, dw_out=dw, db_out=db)
-    cfg = ops.conv2d_last_config()
+    cfg = tune.last_config()
     if dev.type == 'cuda':
         torch.cuda.synchronize()
     return (wdw, dw), (wdb, db), cfg
@@ -265,11 +249,8 @@ def run_case(device, case, with_single_split=True, repeat=True):
     B, Cin, Cout, H, W, ks = case['shape']
     S = case['stride']
     Ho, Wo = H // S, W // S
-    split, v1 = case['dec']
-    # the key of the launch: kind 2 + 10 * stride (+ 100 when the split-bf16 kernel supports the shape, + 1000 for several input
-    # tensors), B, Cin, Cout, H*W and W of dY (W = 32 for a stride-1 1x1 layer: the generic kernel's flattened tiling), ks
-    kind = 2 + 10 * S + (100 if S == 1 else 0) + (1000 if case['srcs'] else 0)
-    key = (ctypes.c_int * 7)(kind, B, Cin, Cout, Ho * Wo, 32 if (ks == 1 and S == 1) else Wo, ks)
+    dec = case['dec']
+    split, v1 = dec.encode()
 
     g = torch.Generator().manual_seed(1000 + sum(case['shape']) + 7 * split + (v1 & 1023))
     x = torch.randn(B, Cin, H, W, generator=g) * torch.exp(0.5 * torch.randn(B, Cin, 1, 1, generator=g))
@@ -290,28 +271,31 @@ def run_case(device, case, with_single_split=True, repeat=True):
     prev_math = HF.set_conv_math('bx3')
     lib.pnsfm_set_autotune(0)
     try:
-        assert lib.pnsfm_tune_set(key, split, v1) == 0
-        (wdw, dw), (wdb, db), cfg = _launch(ops, case, xs, dyd)
-        assert launched_build(cfg) == case['build'], 'pinned %r launched %r (last_config %r)' % (case['build'], launched_build(cfg), cfg)
-        tiles = launched_tiles(cfg, B, Ho, Wo, ks)
-        assert cfg[4] == clamped_split(tiles, split), 'splits launched %d, asked %d of %d tiles' % (cfg[4], split, tiles)
-        assert cfg[4] > 1 and tiles % -(-tiles // split) != 0, 'the case has no short last share (%d tiles, %d ways)' % (tiles, split)
-        _check_slot(wdw, dw, 'dW')
-        _check_slot(wdb, db, 'db')
-        e_dw, e_db = errors(dw, db)
-        print('%s: last_config %r  |dW-dW64|/sum|dY||X| %.3e  |db-db64|/sum|dY| %.3e' % (case['id'], cfg, e_dw, e_db))
-        assert e_dw <= DW_BOUND, (e_dw, DW_BOUND)
-        assert e_db <= DB_BOUND, (e_db, DB_BOUND)
-        if repeat:
-            (wdw2, dw2), (wdb2, db2), cfg2 = _launch(ops, case, xs, dyd)
-            assert cfg2 == cfg
-            assert torch.equal(dw2, dw) and torch.equal(db2, db), 'two launches of one build differ: the summation order is not fixed'
+        key = tune.key(tune.WGRAD, B, Cin, Cout, Ho, Wo, ks, S, len(case['srcs'] or (0,)))      # under the arithmetic set above
+        with tune.pinned((key, dec)):
+            (wdw, dw), (wdb, db), last = _launch(ops, case, xs, dyd)
+            cfg = last.raw
+            assert last.build == case['build'], 'pinned %r launched %r (last_config %r)' % (case['build'], last.build, cfg)
+            tiles = launched_tiles(cfg, B, Ho, Wo, ks)
+            assert cfg[4] == clamped_split(tiles, split), 'splits launched %d, asked %d of %d tiles' % (cfg[4], split, tiles)
+            assert cfg[4] > 1 and tiles % -(-tiles // split) != 0, 'the case has no short last share (%d tiles, %d ways)' % (tiles, split)
+            _check_slot(wdw, dw, 'dW')
+            _check_slot(wdb, db, 'db')
+            e_dw, e_db = errors(dw, db)
+            print('%s: last_config %r  |dW-dW64|/sum|dY||X| %.3e  |db-db64|/sum|dY| %.3e' % (case['id'], cfg, e_dw, e_db))
+            assert e_dw <= DW_BOUND, (e_dw, DW_BOUND)
+            assert e_db <= DB_BOUND, (e_db, DB_BOUND)
+            if repeat:
+                (wdw2, dw2), (wdb2, db2), last2 = _launch(ops, case, xs, dyd)
+                assert last2.raw == cfg
+                assert torch.equal(dw2, dw) and torch.equal(db2, db), 'two launches of one build differ: the summation order is not fixed'
         if with_single_split:
-            assert lib.pnsfm_tune_set(key, 1, v1) == 0
-            (wdw1, dw1), (wdb1, db1), cfg1 = _launch(ops, case, xs, dyd)
-            assert launched_build(cfg1) == case['build'] and cfg1[4] == 1, cfg1
-            _check_slot(wdw1, dw1, 'dW (one split)')
-            _check_slot(wdb1, db1, 'db (one split)')
+            with tune.pinned((key, dec._replace(split=1))):
+                (wdw1, dw1), (wdb1, db1), last1 = _launch(ops, case, xs, dyd)
+                cfg1 = last1.raw
+                assert last1.build == case['build'] and cfg1[4] == 1, cfg1
+                _check_slot(wdw1, dw1, 'dW (one split)')
+                _check_slot(wdb1, db1, 'db (one split)')
             e1_dw, e1_db = errors(dw1, db1)
             print('%s: one split  %.3e  %.3e' % (case['id'], e1_dw, e1_db))
             assert e1_dw <= DW_BOUND and e1_db <= DB_BOUND, (e1_dw, e1_db)
@@ -321,6 +305,5 @@ def run_case(device, case, with_single_split=True, repeat=True):
             assert d_dw <= (e_dw + e1_dw) * slack and d_db <= (e_db + e1_db) * slack, (d_dw, e_dw, e1_dw, d_db, e_db, e1_db)
         return e_dw, e_db
     finally:
-        lib.pnsfm_set_wgrad_variant(-1)      # clears the pins
         lib.pnsfm_set_autotune(1)
         HF.set_conv_math(prev_math)

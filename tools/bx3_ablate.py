@@ -8,6 +8,7 @@ import ctypes, os, subprocess, sys
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
 sys.path.insert(0, os.path.join(ROOT, 'packnet-sfm_amd'))
 import torch
+from packnet_sfm.hip import tune
 CS = os.path.join(ROOT, 'packnet-sfm_amd', 'csrc')
 LIB = os.path.join(ROOT, 'tools', 'micro', 'libpnsfm_bx3ablate.so')
 if not os.path.exists(LIB) or '--build' in sys.argv:
@@ -41,8 +42,7 @@ for i in range(0, len(args), 11):
     wp = torch.zeros(n, device='cuda'); y = torch.empty(B, Cout, H, W, device='cuda')
     lib.pnsfm_conv2d_pack_weights(vp(w.data_ptr()), vp(wp.data_ptr()), vp(0), Cin, Cout, ks, vp(0))
     if NT >= 0:
-        key = (ctypes.c_int * 7)(110, B, Cin, Cout, H, W, ks)
-        lib.pnsfm_tune_set(key, NT | (variant << 4) | (narrow << 8) | (tm << 9), split)
+        tune.pin(tune.key(tune.FORWARD, B, Cin, Cout, H, W, ks, lib=lib), tune.ConvDecision(NT, variant, narrow, tm, split), lib=lib)
     fwd = lambda: lib.pnsfm_conv2d_forward(vp(x.data_ptr()), vp(wp.data_ptr()), vp(0), vp(y.data_ptr()), B, Cin, Cout, H, W, ks, vp(0))
     fl = 2.0 * B * Cin * Cout * ks * ks * H * W
     out = []

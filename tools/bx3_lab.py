@@ -1,10 +1,10 @@
-"""GPU lab for the split-bf16 conv kernels: pin (NT, variant, narrow-M, K-split) through pnsfm_tune_set, report the error
+"""GPU lab for the split-bf16 conv kernels: pin (NT, variant, narrow-M, K-split) through hip.tune, report the error
 against MIOpen and the time per launch.  usage: bx3_lab.py [shape-set]"""
-import ctypes, os, sys, itertools
+import os, sys, itertools
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'packnet-sfm_amd'))
 import torch
 import torch.nn.functional as F
-from packnet_sfm.hip import _lib, ops, functional as HF
+from packnet_sfm.hip import _lib, ops, tune, functional as HF
 
 dev = torch.device('cuda:0')
 lib = _lib.get()
@@ -36,8 +36,7 @@ for shape in SHAPES:
         bx3 = variant >= 3
         HF.set_conv_math('bx3' if bx3 else 'f32')
         lib.pnsfm_set_conv_variant(0)
-        key = (ctypes.c_int * 7)(10 + (100 if bx3 else 0), B, Cin, Cout, H, W, ks)
-        lib.pnsfm_tune_set(key, NT | (variant << 4) | (narrow << 8), split)
+        tune.pin(tune.key(tune.FORWARD, B, Cin, Cout, H, W, ks), tune.ConvDecision(NT, variant, narrow, split=split))
         wf, _ = ops.conv2d_pack(w, want_bwd=False)
         errs = []
         for rep in range(3):

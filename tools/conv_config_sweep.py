@@ -1,7 +1,6 @@
 """Check EVERY configuration the conv autotuner may pick for a layer shape against torch's convolution, several
 repetitions each (catches races that only some configurations / timings expose).
 usage: python tools/conv_config_sweep.py [shape ...]   shape = B,Cin,Cout,H,W,ks"""
-import ctypes
 import os
 import sys
 
@@ -9,17 +8,12 @@ ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
 sys.path.insert(0, os.path.join(ROOT, 'packnet-sfm_amd'))
 import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
-from packnet_sfm.hip import _lib, ops  # noqa: E402
+from packnet_sfm.hip import ops, tune  # noqa: E402
 
-lib = _lib.get()
 SHAPES = [tuple(int(v) for v in a.split(',')) for a in sys.argv[1:]] or [
     (1, 3, 64, 64, 96, 5), (1, 64, 64, 64, 96, 7), (1, 64, 64, 32, 48, 3), (1, 256, 64, 32, 48, 7), (1, 128, 128, 16, 24, 3),
     (1, 256, 256, 8, 12, 3), (1, 512, 512, 4, 6, 3), (1, 129, 64, 64, 96, 3), (1, 64, 32, 32, 48, 3), (1, 512, 512, 2, 3, 3),
     (1, 256, 256, 8, 12, 1), (4, 256, 256, 24, 80, 3), (4, 64, 64, 96, 320, 3), (4, 512, 512, 12, 40, 3)]
-
-
-def key(*v):
-    return (ctypes.c_int * 7)(*v)
 
 
 def rel(a, b):
@@ -41,9 +35,9 @@ for (B, Cin, Cout, H, W, ks) in SHAPES:
         for nt in (1, 2):
             for fmt in (0, 1):
                 for split in (1, 2, 3, 4, 8, 16):
-                    cfg = nt | (variant << 4) | (fmt << 8)
-                    lib.pnsfm_tune_set(key(10, B, Cin, Cout, H, W, ks), cfg, split)
-                    lib.pnsfm_tune_set(key(11, B, Cout, Cin, H, W, ks), cfg, split)
+                    cfg = tune.ConvDecision(nt, variant, fmt, split=split)
+                    tune.pin(tune.key(tune.FORWARD, B, Cin, Cout, H, W, ks), cfg)
+                    tune.pin(tune.key(tune.BACKWARD_DATA, B, Cout, Cin, H, W, ks), cfg)
                     for rep in range(3):
                         try:
                             e1 = rel(ops.conv2d_forward(x, wf, None, Cout, ks).double(), yr)
@@ -56,10 +50,9 @@ for (B, Cin, Cout, H, W, ks) in SHAPES:
                         if max(e1, e2) > 2e-5:
                             bad += 1
                             print('  BAD fwd/dgrad', (B, Cin, Cout, H, W, ks), 'variant', variant, 'NT', nt, 'fMT', fmt, 'split', split, 'rep', rep, '%.2e %.2e' % (e1, e2))
-    Wk = 32 if ks == 1 else W
     for variant in (0, 1):
         for split in (1, 2, 3, 5, 8, 16, 40, 120):
-            lib.pnsfm_tune_set(key(12, B, Cin, Cout, H * W, Wk, ks), split, variant)
+            tune.pin(tune.key(tune.WGRAD, B, Cin, Cout, H, W, ks), tune.WgradDecision(variant, split))
             for rep in range(3):
                 try:
                     dw, db = ops.conv2d_backward_weight(x, dy, ks)

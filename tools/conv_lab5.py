@@ -3,12 +3,11 @@ configurations of a candidate variant (default: 7, the ping-pong workgroup of co
     python tools/conv_lab5.py [--variant 7] [--shapes all|body|big] [--g G]
 Prints per shape: tuned ms / TFLOP/s, the best candidate (NT, narrow-M, tile mode, split) ms / TFLOP/s, max |difference|."""
 import argparse
-import ctypes
 import os
 import sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'packnet-sfm_amd'))
 import torch
-from packnet_sfm.hip import _lib, ops
+from packnet_sfm.hip import _lib, ops, tune
 
 ap = argparse.ArgumentParser()
 ap.add_argument('--variant', type=int, default=7)
@@ -51,7 +50,7 @@ for shape in SHAPES:
     w = (torch.randn(Cout, Cin, ks, ks, generator=g) * (2.0 / (Cin * ks * ks)) ** 0.5).to(dev)
     wf, _ = ops.conv2d_pack(w, want_bwd=False)
     gf = 2.0 * B * Cin * Cout * H * W * ks * ks / 1e9
-    key = (ctypes.c_int * 7)(110, B, Cin, Cout, H, W, ks)
+    key = tune.key(tune.FORWARD, B, Cin, Cout, H, W, ks)
     lib.pnsfm_set_conv_variant(3)            # clears pins: the tuned (database / autotuned) configuration
     y0 = ops.conv2d_forward(x, wf, None, Cout, ks)
     base = timeit(lambda: ops.conv2d_forward(x, wf, None, Cout, ks))
@@ -64,7 +63,7 @@ for shape in SHAPES:
                 for split in [int(v) for v in args.splits.split(',')]:
                     if split > max(1, (Cin + 15) // 16):
                         break
-                    lib.pnsfm_tune_set(key, NT | (args.variant << 4) | (narrow << 8) | (tm << 9), split)
+                    tune.pin(key, tune.ConvDecision(NT, args.variant, narrow, tm, split))
                     try:
                         y = ops.conv2d_forward(x, wf, None, Cout, ks)
                     except Exception as e:

@@ -1,9 +1,9 @@
 """Where does a mid-resolution 3x3 layer lose its time?  Launch time of the split-bf16 forward kernel as a function of the K extent
 (input channels) at a fixed tile grid: time = fixed cost per launch/workgroup + slope * K.  usage: conv_scaling_lab.py"""
-import ctypes, os, sys
+import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'packnet-sfm_amd'))
 import torch
-from packnet_sfm.hip import _lib, ops, functional as HF
+from packnet_sfm.hip import _lib, ops, tune, functional as HF
 
 dev = torch.device('cuda:0')
 lib = _lib.get()
@@ -31,8 +31,7 @@ for (B, Cout, H, W, ks) in [(8, 256, 24, 80, 3), (8, 512, 12, 40, 3), (16, 512, 
         for Cin in (32, 64, 128, 256, 512, 1024):
             x = torch.randn(B, Cin, H, W, device=dev)
             w = torch.randn(Cout, Cin, ks, ks, device=dev) * 0.05
-            key = (ctypes.c_int * 7)(110, B, Cin, Cout, H, W, ks)
-            lib.pnsfm_tune_set(key, NT | (variant << 4) | (narrow << 8) | (tm << 9), 1)
+            tune.pin(tune.key(tune.FORWARD, B, Cin, Cout, H, W, ks), tune.ConvDecision(NT, variant, narrow, tm))
             wf, _ = ops.conv2d_pack(w, want_bwd=False)
             ms = timeit(lambda: ops.conv2d_forward(x, wf, None, Cout, ks))
             gf = 2.0 * B * Cin * Cout * H * W * ks * ks / 1e9

@@ -5,6 +5,7 @@ import ctypes, os, subprocess, sys
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
 sys.path.insert(0, os.path.join(ROOT, 'packnet-sfm_amd'))
 import torch
+from packnet_sfm.hip import tune
 CS = os.path.join(ROOT, 'packnet-sfm_amd', 'csrc')
 LIB = os.path.join(ROOT, 'gpurun_out', 'libpnsfm_trace.so')
 if not os.path.exists(LIB):
@@ -20,8 +21,7 @@ x = torch.randn(B, Cin, H, W, device='cuda'); w = torch.randn(Cout, Cin, ks, ks,
 wp = torch.zeros(n, device='cuda'); y = torch.empty(B, Cout, H, W, device='cuda')
 vp = ctypes.c_void_p
 lib.pnsfm_conv2d_pack_weights(vp(w.data_ptr()), vp(wp.data_ptr()), vp(0), Cin, Cout, ks, vp(0))
-key = (ctypes.c_int * 7)(10, B, Cin, Cout, H, W, ks)
-lib.pnsfm_tune_set(key, NT | (2 << 4) | (fMT << 8), split)
+tune.pin(tune.key(tune.FORWARD, B, Cin, Cout, H, W, ks, lib=lib), tune.ConvDecision(NT, 2, fMT, split=split), lib=lib)
 trace = torch.zeros(6 * (1 << 20), dtype=torch.int64, device='cuda')
 lib.pnsfm_debug_set_trace(vp(trace.data_ptr()))
 lib.pnsfm_debug_set_trace_flags(int(os.environ.get('TRACE_FLAGS', '0')))

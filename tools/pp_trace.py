@@ -5,6 +5,7 @@ import ctypes, os, subprocess, sys
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
 sys.path.insert(0, os.path.join(ROOT, 'packnet-sfm_amd'))
 import torch
+from packnet_sfm.hip import tune
 CS = os.path.join(ROOT, 'packnet-sfm_amd', 'csrc')
 LIB = os.path.join(ROOT, 'gpurun_out', 'libpnsfm_pptrace.so')
 srcs = [os.path.join(CS, f) for f in ('api.hip', 'conv2d.hip', 'conv2d_wgrad2.hip', 'conv2d_wgrad3.hip', 'conv2d_wgrad4.hip')]
@@ -20,8 +21,7 @@ for i in range(0, len(args), 10):
     x = torch.randn(B, Cin, H, W, device='cuda'); w = torch.randn(Cout, Cin, ks, ks, device='cuda') * 0.05
     wp = torch.zeros(n, device='cuda'); y = torch.empty(B, Cout, H, W, device='cuda')
     lib.pnsfm_conv2d_pack_weights(vp(w.data_ptr()), vp(wp.data_ptr()), vp(0), Cin, Cout, ks, vp(0))
-    key = (ctypes.c_int * 7)(110, B, Cin, Cout, H, W, ks)
-    lib.pnsfm_tune_set(key, NT | (7 << 4) | (narrow << 8) | (tm << 9), split)
+    tune.pin(tune.key(tune.FORWARD, B, Cin, Cout, H, W, ks, lib=lib), tune.ConvDecision(NT, 7, narrow, tm, split), lib=lib)
     trace = torch.zeros(8 * (1 << 18), dtype=torch.int64, device='cuda')
     lib.pnsfm_debug_set_trace(vp(trace.data_ptr()))
     fwd = lambda: lib.pnsfm_conv2d_forward(vp(x.data_ptr()), vp(wp.data_ptr()), vp(0), vp(y.data_ptr()), B, Cin, Cout, H, W, ks, vp(0))
