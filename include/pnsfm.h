@@ -181,6 +181,30 @@ int pnsfm_resample8(const uint8_t* in, uint8_t* out, const int* kk, const int* b
                     int outH, int outW, int C, int axis, void* stream);
 int pnsfm_jitter_totensor(const uint8_t* img, const void* ops, unsigned long long* lsum_ws, float* out, float* out_orig /*nullable*/,
                           int N, int H, int W, void* stream);
+/* Depth maps and the evaluation transforms (csrc/depth_input.h), since ABI version 5: datasets/augmentations.py:56-98
+ * (resize_depth_preserve), :35-53 (resize_depth), :382-399 (crop_depth) and the ToTensor of datasets/transforms.py:41-93
+ * (validation_transforms / test_transforms).  Device pointers are caller-allocated, the work is enqueued on `stream`, nothing
+ * synchronises, there are no atomics and results are bit-reproducible.
+ * Both resizes read N fp32 maps through a WINDOW: map n, row y, column x of the window is in[n * img_stride + (y0 + y) * row_stride +
+ *   (x0 + x)] (strides in elements; row_stride >= x0 + w, and img_stride >= (y0 + h) * row_stride when N > 1), so crop_depth is index
+ *   arithmetic.  out: contiguous [N][1][H][W] fp32, every element written.  Extents up to 2^24.
+ * pnsfm_depth_resize_preserve: a source pixel is valid when v > 0 (NaN and negative values are dropped); its target is
+ *   ((int)((double)y * sy), (int)((double)x * sx)) with sy = H / h, sx = W / w computed by the caller in double; targets outside
+ *   [0,H) x [0,W) are dropped; where several valid pixels share a target the one that comes LAST in row-major source order wins (numpy's
+ *   fancy assignment); cells without a valid source are 0.  Bit for bit the reference's function, computed as a gather: one thread
+ *   per output pixel scans the (at most ceil(h/H)+1 by ceil(w/W)+1, possibly empty) block of source pixels that map to it.
+ * pnsfm_depth_resize_nearest: out(Y, X) = in(min((int)floor(Y * ify), h - 1), min((int)floor(X * ifx), w - 1)), with
+ *   ify = 1.0 / ((double)H / h) and ifx = 1.0 / ((double)W / w) computed by the caller in exactly that form.  A restatement of
+ *   OpenCV's INTER_NEAREST (what resize_depth calls); OpenCV is not installed where this library is tested, so the rule is NOT
+ *   pinned against the real library.
+ * pnsfm_totensor8: img uint8 NHWC [N][H][W][3] -> out NCHW [N][3][H][W], float32 (out_h16 == 0) or IEEE half (out_h16 != 0): the
+ *   float32 value is float(v) / 255 from the device function pnsfm_jitter_totensor uses for out_orig (bit-identical to it); the half
+ *   value is that float32 rounded once to nearest even. */
+int pnsfm_depth_resize_preserve(const float* in, long long img_stride, long long row_stride, int N, int y0, int x0, int h, int w,
+                                float* out, int H, int W, double sy, double sx, void* stream);
+int pnsfm_depth_resize_nearest(const float* in, long long img_stride, long long row_stride, int N, int y0, int x0, int h, int w,
+                               float* out, int H, int W, double ify, double ifx, void* stream);
+int pnsfm_totensor8(const uint8_t* img, void* out, int out_h16, int N, int H, int W, void* stream);
 
 /* ---- Neural-Ray-Surface projection (softmax expectation over a 41x41 candidate patch) --------------------------------------
  * replaces the core of GenericCamera.project, packnet_sfm/geometry/camera_generic.py:127-192 (patch coordinates with the window

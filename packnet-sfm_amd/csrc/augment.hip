@@ -19,6 +19,7 @@
 //   * hue: RGB -> HSV (colorsys in float with double literals, as Convert.c), H += uint8(hue_factor * 255) mod 256, HSV -> RGB;
 //   * the four operations run in the per-sample order drawn by random.shuffle; ToTensor = float(v) / 255.
 // HBM-bound streaming kernels: 3 B/pixel in, 2 x 12 B/pixel out (jittered + original float32 planes).
+// Depth-map resizing and the plain ToTensor of the evaluation transforms live in depth_input.h, included at the end of this file.
 #include "pnsfm_common.h"
 #include "../../include/pnsfm.h"
 
@@ -165,6 +166,9 @@ __global__ void __launch_bounds__(256) jitter_lsum_kernel(const uint8_t* __restr
   }
 }
 
+// ToTensor of one byte: the ONE definition (this file's jitter kernel and totensor8 of depth_input.h)
+__device__ __forceinline__ float to_unit8(int v) { return (float)v / 255.f; }
+
 // pass 2: the whole sequence, then ToTensor: NHWC uint8 -> two NCHW float32 tensors (jittered, original)
 __global__ void __launch_bounds__(256) jitter_totensor_kernel(const uint8_t* __restrict__ img, const JitterOps* __restrict__ ops,
                                                               const unsigned long long* __restrict__ lsum, float* __restrict__ out,
@@ -179,18 +183,20 @@ __global__ void __launch_bounds__(256) jitter_totensor_kernel(const uint8_t* __r
   float* oo = out_orig ? out_orig + (size_t)n * 3 * HW : nullptr;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += gridDim.x * 256) {
     int r = p[3 * i], g = p[3 * i + 1], b = p[3 * i + 2];
-    if (oo) { oo[i] = (float)r / 255.f; oo[HW + i] = (float)g / 255.f; oo[2 * HW + i] = (float)b / 255.f; }
+    if (oo) { oo[i] = to_unit8(r); oo[HW + i] = to_unit8(g); oo[2 * HW + i] = to_unit8(b); }
     if (j.enabled) {
       apply_ops(j, 0, 4, mean, r, g, b);
       if (j.has_color) { r = color_scale8(r, j.color[0]); g = color_scale8(g, j.color[1]); b = color_scale8(b, j.color[2]); }
     }
-    o[i] = (float)r / 255.f;
-    o[HW + i] = (float)g / 255.f;
-    o[2 * HW + i] = (float)b / 255.f;
+    o[i] = to_unit8(r);
+    o[HW + i] = to_unit8(g);
+    o[2 * HW + i] = to_unit8(b);
   }
 }
 
 }  // namespace pnsfm
+
+#include "depth_input.h"      // depth-map resizing and the plain ToTensor of the evaluation transforms (same input pipeline)
 
 using namespace pnsfm;
 

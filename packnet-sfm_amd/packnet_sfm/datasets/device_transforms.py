@@ -9,8 +9,18 @@ random_color_jitter_transform :254-337, to_tensor_sample :185-226): same keys in
 sample), and BIT-IDENTICAL pixels: the kernels of csrc/augment.hip restate Pillow's integer arithmetic (tests pin them against
 PIL itself).  The frames of a batch share one launch per stage; crop borders are index arithmetic on the uint8 tensor.
 
-Not covered (the reference's host path stays available through the merged package): depth-map resizing
-(resize_depth_preserve), the optional 3x4 'color' matrix of `jittering[4]`, PIL images as input.
+Depth maps ('depth', 'input_depth', 'depth_context': fp32 on the device) follow the images: the same crop window (crop_sample,
+augmentations.py:402-505), then resize_depth_preserve (:56-98) as a gather kernel that is bit-identical to the reference's numpy
+scatter (csrc/depth_input.h; tests pin it against the reference's own outputs), fp32 [B,1,H,W] out; all maps of one source size
+share one launch and the crop is the kernel's window, not a copy.  'input_depth_context' is passed through untouched.
+
+DeviceEvalTransform is the counterpart of `validation_transforms` / `test_transforms` (transforms.py:41-93) and
+get_device_transforms of `get_transforms` (:95-132).  The 'test' mode resizes 'input_depth' with the nearest rule of
+cv2.resize(..., INTER_NEAREST) as restated in include/pnsfm.h; OpenCV is not available where this package is tested, so that one
+rule is NOT pinned against the real library.
+
+Not covered (the reference's host path stays available through the merged package): 'input_depth_context', ragged batches
+(frames of different sizes in one call), the optional 3x4 'color' matrix of `jittering[4]`, PIL images as input.
 """
 import math
 import random
@@ -139,7 +149,8 @@ class DeviceTrainTransform:
         return frames.contiguous()
 
     def __call__(self, sample):
-        """sample: {'rgb': uint8 [B,H,W,3], 'rgb_context': [uint8 [B,H,W,3], ...], 'intrinsics': [B,3,3]} on the device."""
+        """sample: {'rgb': uint8 [B,H,W,3], 'rgb_context': [uint8 [B,H,W,3], ...], 'intrinsics': [B,3,3]} on the device; optionally
+        'depth' / 'input_depth': fp32 [B,h,w] or [B,1,h,w] and 'depth_context': a list of such maps -> fp32 [B,1,H,W] each."""
         out = dict(sample)
         rgb = sample['rgb']
         B, H0, W0, _ = rgb.shape
@@ -170,4 +181,113 @@ class DeviceTrainTransform:
         if ctx:
             out['rgb_context'] = [jit[B * (i + 1):B * (i + 2)] for i in range(len(ctx))]
             out['rgb_context_original'] = [orig[B * (i + 1):B * (i + 2)] for i in range(len(ctx))]
+        # depth maps: the images' crop window (crop_sample = input + supervision), then resize_depth_preserve.  Consumes no random draw.
+        keys = [k for k in ('depth', 'input_depth') if sample.get(k) is not None]
+        dctx = list(sample.get('depth_context') or [])
+        if keys or dctx:
+            maps = depth_maps([sample[k] for k in keys] + dctx, borders, self.image_shape, ops.depth_resize_preserve)
+            for k, m in zip(keys, maps):
+                out[k] = m
+            if dctx:
+                out['depth_context'] = maps[len(keys):]
         return out
+
+
+def depth_maps(maps, borders, image_shape, resize):
+    """crop_depth (borders = (left, top, right, bottom) or ()) + `resize` (ops.depth_resize_preserve / ops.depth_resize_nearest) to
+    image_shape, or the crop alone when image_shape is (), of a list of fp32 [B,h,w] / [B,1,h,w] maps -> a list of fp32 [B,1,H,W].  The
+    crop is the kernel's window; maps of one source size share one launch."""
+    maps = [m[:, 0] if m.dim() == 4 and m.shape[1] == 1 else m for m in maps]
+    for m in maps:
+        if m.dim() != 3 or m.dtype != torch.float32:
+            raise RuntimeError('depth maps must be float32 [B,h,w] or [B,1,h,w], got %s %s' % (m.dtype, tuple(m.shape)))
+    if not image_shape:
+        if borders:
+            l, t, r, b = borders
+            maps = [m[:, t:b, l:r] for m in maps]
+        return [m.unsqueeze(1).contiguous() for m in maps]
+    out = [None] * len(maps)
+    sizes = {}
+    for i, m in enumerate(maps):
+        sizes.setdefault(tuple(m.shape[1:]), []).append(i)
+    for idx in sizes.values():
+        group = torch.cat([maps[i] for i in idx], 0) if len(idx) > 1 else maps[idx[0]].contiguous()
+        window = (borders[1], borders[0], borders[3] - borders[1], borders[2] - borders[0]) if borders else None
+        res = resize(group, image_shape, window)
+        n = 0
+        for i in idx:
+            out[i] = res[n:n + maps[i].shape[0]]
+            n += maps[i].shape[0]
+    return out
+
+
+class DeviceEvalTransform:
+    """`validation_transforms` / `test_transforms` of the reference (datasets/transforms.py:41-93) on the device, as they are:
+    crop_sample_input crops 'rgb', 'rgb_context' and 'input_depth', shifts the principal point of 'intrinsics' and keeps the
+    uncropped matrix in 'intrinsics_full' -- and leaves 'depth' (the ground truth) alone; only 'rgb' is resized (Lanczos), so
+    'rgb_context' keeps its cropped size and 'intrinsics' are NOT rescaled; 'input_depth' is resized with resize_depth_preserve
+    ('validation') or nearest ('test': cv2.resize INTER_NEAREST, restated but not pinned against OpenCV, include/pnsfm.h); ToTensor
+    without '_original' copies and without jitter.
+
+    Parameters
+    ----------
+    mode : 'validation' | 'test'
+    image_shape : (H, W) or ()
+    crop_eval_borders : the reference's config value (see DeviceTrainTransform), or ()
+    dtype : torch.float32 | torch.float16 -- of 'rgb', 'rgb_context', 'depth' and 'input_depth' (what a `--half` evaluation feeds
+            the network, written directly instead of an fp32 tensor and a cast)
+    """
+
+    def __init__(self, mode, image_shape=(), crop_eval_borders=(), dtype=torch.float32):
+        if mode not in ('validation', 'test'):
+            raise ValueError('Unknown mode {}'.format(mode))
+        self.mode = mode
+        self.image_shape = tuple(image_shape)
+        self.crop_spec = tuple(crop_eval_borders)
+        self.dtype = dtype
+        if self.crop_spec and len(self.crop_spec) not in (2, 4):
+            raise NotImplementedError('Crop tuple must have 2 or 4 values.')
+
+    def __call__(self, sample):
+        """sample: {'rgb': uint8 [B,H,W,3]; optionally 'rgb_context': [uint8 [B,H,W,3], ...], 'intrinsics': [B,3,3], 'depth' and
+        'input_depth': fp32 [B,h,w] or [B,1,h,w]} on the device."""
+        out = dict(sample)
+        rgb = sample['rgb']
+        ctx = list(sample.get('rgb_context', []))
+        borders = parse_crop_borders(self.crop_spec, tuple(rgb.shape[1:3])) if self.crop_spec else ()
+        if borders:
+            l, t, r, b = borders
+            rgb = rgb[:, t:b, l:r]
+            ctx = [c[:, t:b, l:r] for c in ctx]
+            if 'intrinsics' in sample:
+                if 'intrinsics_full' not in sample:
+                    out['intrinsics_full'] = sample['intrinsics'].clone()
+                K = sample['intrinsics'].clone()
+                K[:, 0, 2] -= l
+                K[:, 1, 2] -= t
+                out['intrinsics'] = K
+        if self.image_shape:
+            rgb = resize_frames(rgb, self.image_shape)
+        out['rgb'] = ops.totensor8(rgb.contiguous(), self.dtype)
+        if ctx:
+            B = ctx[0].shape[0]
+            allc = ops.totensor8(torch.cat(ctx, 0) if len(ctx) > 1 else ctx[0].contiguous(), self.dtype)
+            out['rgb_context'] = [allc[B * i:B * (i + 1)] for i in range(len(ctx))]
+        if sample.get('input_depth') is not None:
+            resize = ops.depth_resize_preserve if self.mode == 'validation' else ops.depth_resize_nearest
+            out['input_depth'] = depth_maps([sample['input_depth']], borders, self.image_shape, resize)[0].to(self.dtype)
+        if sample.get('depth') is not None:
+            out['depth'] = depth_maps([sample['depth']], (), (), None)[0].to(self.dtype)
+        return out
+
+
+def get_device_transforms(mode, image_shape, jittering, crop_train_borders, crop_eval_borders, **kwargs):
+    """The reference's get_transforms (datasets/transforms.py:95-132) over the device pipeline: 'train' -> DeviceTrainTransform,
+    'validation' | 'test' -> DeviceEvalTransform (fp32; construct it directly for fp16); any other mode raises ValueError.  Extra
+    keyword arguments are ignored, as there."""
+    if mode == 'train':
+        return DeviceTrainTransform(image_shape=image_shape, jittering=jittering, crop_train_borders=crop_train_borders)
+    elif mode in ('validation', 'test'):
+        return DeviceEvalTransform(mode, image_shape=image_shape, crop_eval_borders=crop_eval_borders)
+    else:
+        raise ValueError('Unknown mode {}'.format(mode))

@@ -17,6 +17,8 @@ _p = ctypes.c_void_p
 _i = ctypes.c_int
 _f = ctypes.c_float
 _sz = ctypes.c_size_t
+_ll = ctypes.c_longlong
+_d = ctypes.c_double
 
 # name -> (restype, argtypes); mirrors include/pnsfm.h one to one
 SIGNATURES = {
@@ -100,6 +102,10 @@ SIGNATURES = {
     "pnsfm_adam_segments": (_i, [_p, _i, _i, _p]),
     "pnsfm_resample8": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "pnsfm_jitter_totensor": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p]),
+    # depth maps and the evaluation transforms (csrc/depth_input.h)
+    "pnsfm_depth_resize_preserve": (_i, [_p, _ll, _ll, _i, _i, _i, _i, _i, _p, _i, _i, _d, _d, _p]),
+    "pnsfm_depth_resize_nearest": (_i, [_p, _ll, _ll, _i, _i, _i, _i, _i, _p, _i, _i, _d, _d, _p]),
+    "pnsfm_totensor8": (_i, [_p, _p, _i, _i, _i, _i, _p]),
     "pnsfm_nrs_project_forward": (_i, [_p, _p, _p, _p, _i, _i, _f, _p]),
     "pnsfm_nrs_project_backward": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _f, _p]),
     "pnsfm_sparse_compact_ws_ints": (_sz, [_i]),

@@ -785,6 +785,56 @@ def jitter_totensor(img, ops_records, want_original=True):
     return out, orig
 
 
+def _depth_window(depth, window, what):
+    """depth: fp32 [N,h,w] or [N,1,h,w], contiguous -> (N, row stride, image stride, (y0, x0, h, w)) with the window inside the map."""
+    _chk(depth); _f32(depth)
+    if depth.dim() == 4 and depth.shape[1] == 1:
+        depth = depth[:, 0]
+    if depth.dim() != 3 or depth.numel() == 0:
+        raise RuntimeError("%s: depth maps must be a non-empty [N,h,w] or [N,1,h,w], got %s" % (what, tuple(depth.shape)))
+    N, h0, w0 = depth.shape
+    y0, x0, h, w = (0, 0, h0, w0) if window is None else (int(v) for v in window)
+    if not (0 <= y0 and 0 <= x0 and h >= 1 and w >= 1 and y0 + h <= h0 and x0 + w <= w0):
+        raise RuntimeError("%s: window (y0 %d, x0 %d, h %d, w %d) leaves the %dx%d map" % (what, y0, x0, h, w, h0, w0))
+    return N, w0, h0 * w0, (y0, x0, h, w)
+
+
+def depth_resize_preserve(depth, shape, window=None):
+    """resize_depth_preserve (reference datasets/augmentations.py:56-98) of N maps.  depth: fp32 [N,h,w] or [N,1,h,w]; window = (y0, x0,
+    h, w): the crop_depth window, read in place; shape = (H, W) -> fp32 [N,1,H,W]."""
+    N, row_stride, img_stride, (y0, x0, h, w) = _depth_window(depth, window, "depth_resize_preserve")
+    H, W = int(shape[0]), int(shape[1])
+    out = torch.empty((N, 1, H, W), dtype=torch.float32, device=depth.device)
+    _lib.check(_lib.get().pnsfm_depth_resize_preserve(_ptr(depth), img_stride, row_stride, N, y0, x0, h, w, _ptr(out), H, W, H / h, W / w,
+                                                      _stream(depth)), "depth_resize_preserve")
+    return out
+
+
+def depth_resize_nearest(depth, shape, window=None):
+    """resize_depth (cv2.resize INTER_NEAREST, augmentations.py:35-53) of N maps, by the rule stated in include/pnsfm.h (not pinned
+    against OpenCV itself).  Arguments and result as depth_resize_preserve."""
+    N, row_stride, img_stride, (y0, x0, h, w) = _depth_window(depth, window, "depth_resize_nearest")
+    H, W = int(shape[0]), int(shape[1])
+    out = torch.empty((N, 1, H, W), dtype=torch.float32, device=depth.device)
+    _lib.check(_lib.get().pnsfm_depth_resize_nearest(_ptr(depth), img_stride, row_stride, N, y0, x0, h, w, _ptr(out), H, W,
+                                                     1.0 / (float(H) / h), 1.0 / (float(W) / w), _stream(depth)), "depth_resize_nearest")
+    return out
+
+
+def totensor8(img, dtype=torch.float32):
+    """ToTensor without jitter.  img: uint8 [N,H,W,3] -> [N,3,H,W] float32 (bit-identical to jitter_totensor's original) or float16 (that
+    value rounded once)."""
+    _chk(img)
+    if img.dim() != 4 or img.dtype != torch.uint8 or img.shape[3] != 3 or img.numel() == 0:
+        raise RuntimeError("totensor8: non-empty uint8 [N,H,W,3] image expected")
+    if dtype not in (torch.float32, torch.float16):
+        raise RuntimeError("totensor8: float32 or float16 output, got %s" % dtype)
+    N, H, W, _ = img.shape
+    out = torch.empty((N, 3, H, W), dtype=dtype, device=img.device)
+    _lib.check(_lib.get().pnsfm_totensor8(_ptr(img), _ptr(out), int(dtype == torch.float16), N, H, W, _stream(img)), "totensor8")
+    return out
+
+
 # -------------------------------------------------------------------------------------- sparse tensors (PackNet-SAN)
 def _i32(*tensors):
     for t in tensors:

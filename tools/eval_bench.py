@@ -8,6 +8,8 @@
     python tools/eval_bench.py --metrics         # the tail of an evaluation step (post-process + 4 x depth metrics), KITTI shapes
     python tools/eval_bench.py --metrics-launches fused --calls 12     # N calls of one tail path, for a kernel trace (launch count)
 
+    python tools/eval_bench.py --input           # the input pipeline (device validation / training transforms with depth maps) vs the host
+
 Prints ONE JSON line: per size and path images/s, ms per forward (device events over windows of >= `window` s), host-issue ms per forward,
 conv GFLOP from shapes (as executed, i.e. with the collapsed packing layers, and reference-algorithmic) and achieved conv TFLOP/s."""
 import argparse
@@ -216,6 +218,116 @@ def metrics_launches(a):
     print(json.dumps({'tool': 'eval_bench --metrics-launches', 'path': a.metrics_launches, 'calls': a.calls}))
 
 
+def _host_resize_depth_preserve(depth, shape):
+    """numpy restatement of the reference's resize_depth_preserve (datasets/augmentations.py:56-98), float64 output as there."""
+    import numpy as np
+    h, w = depth.shape
+    ys, xs = np.nonzero(depth > 0)
+    val = depth[ys, xs]
+    ty, tx = (ys * (shape[0] / h)).astype(np.int32), (xs * (shape[1] / w)).astype(np.int32)
+    keep = (ty < shape[0]) & (tx < shape[1])
+    out = np.zeros(shape)
+    out[ty[keep], tx[keep]] = val[keep]
+    return out
+
+
+def input_pipeline(a):
+    """The input pipeline at KITTI shapes (frames and depth maps 375 x 1242 -> 192 x 640, about 5 % of the depth pixels valid), batch 1
+    and batch 4: the device validation transform (fp16 out), the device training transform with 'depth' + 'input_depth' (two context
+    frames, the YAML's jitter), the depth kernel alone with its achieved bytes/s next to this box's streaming-copy rate (measured as
+    bench.py's calibration does), and the host path -- PIL for the images (oracle.augment_oracle), numpy for the depth maps -- per sample
+    on one core."""
+    import random
+
+    import numpy as np
+    from PIL import Image
+
+    from oracle import augment_oracle as AO
+    from packnet_sfm.datasets.device_transforms import DeviceEvalTransform, DeviceTrainTransform
+    from packnet_sfm.hip import ops
+    dev = torch.device('cuda:0')
+    h, w, shape, jitter = 375, 1242, (192, 640), (0.2, 0.2, 0.2, 0.05)
+    result = {'tool': 'eval_bench --input', 'device': torch.cuda.get_device_name(0), 'frames': [h, w], 'image_shape': list(shape),
+              'depth_valid_fraction': 0.05, 'timing': 'device events over windows of >= %.1f s, best of %d; host: perf_counter, one core'
+              % (a.window, a.reps), 'settings': {}}
+    # streaming-copy rate of this box: 1 GiB -> 1 GiB float4 copy, read + write bytes (csrc/calib.hip), best of 3 after a warm-up
+    src = torch.ones((1 << 30) // 4, dtype=torch.float32, device=dev)
+    dst = torch.empty_like(src)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    copy_gbps = 0.0
+    for i in range(4):
+        e0.record()
+        nbytes = ops.calib_copy(src, dst)
+        e1.record()
+        torch.cuda.synchronize()
+        if i:
+            copy_gbps = max(copy_gbps, nbytes / (e0.elapsed_time(e1) * 1e-3) / 1e9)
+    del src, dst
+    torch.cuda.empty_cache()
+    result['streaming_copy_gbps'] = round(copy_gbps, 1)
+    rng = np.random.default_rng(0)
+    for B in (1, 4):
+        fr = rng.integers(0, 256, (3 * B, h, w, 3), dtype=np.uint8)
+        dm = (80 * rng.random((2 * B, h, w))).astype(np.float32)
+        dm[rng.random(dm.shape) > 0.05] = 0
+        K = np.array([[0.58 * w, 0, 0.5 * w], [0, 1.92 * h, 0.5 * h], [0, 0, 1]])
+        sample = {'rgb': torch.from_numpy(fr[:B]).to(dev), 'rgb_context': [torch.from_numpy(fr[B:2 * B]).to(dev), torch.from_numpy(fr[2 * B:]).to(dev)],
+                  'intrinsics': torch.from_numpy(np.stack([K] * B)).to(dev),
+                  'depth': torch.from_numpy(dm[:B]).to(dev), 'input_depth': torch.from_numpy(dm[B:]).to(dev)}
+        val_sample = {k: v for k, v in sample.items() if k != 'rgb_context'}
+        val_t, train_t = DeviceEvalTransform('validation', shape, (), torch.float16), DeviceTrainTransform(shape, jitter, ())
+        both = torch.cat([sample['depth'], sample['input_depth']], 0)
+        paths = {'device_validation_fp16': lambda: val_t(val_sample), 'device_train_depth': lambda: train_t(sample),
+                 'depth_resize_preserve_kernel': lambda: ops.depth_resize_preserve(both, shape)}
+        for fn in paths.values():
+            for _ in range(5):
+                fn()
+        samples = {k: [] for k in paths}
+        for _ in range(a.reps):
+            for k, fn in paths.items():
+                samples[k].append(time_path(fn, a.window))
+        entry = {}
+        for k, v in samples.items():
+            ms, host = min(v)
+            entry[k] = {'ms_per_call': round(ms, 4), 'samples_per_s': round(1e3 * B / ms, 1), 'host_issue_ms': round(host, 4),
+                        'ms_all_windows': [round(s[0], 4) for s in v]}
+        # the depth kernel's bytes from shapes: every source pixel read once, every output pixel written once (fp32)
+        kbytes = 2 * B * (h * w + shape[0] * shape[1]) * 4
+        kern = entry['depth_resize_preserve_kernel']
+        kern.update({'maps': 2 * B, 'bytes': kbytes, 'gbps': round(kbytes / (kern['ms_per_call'] * 1e-3) / 1e9, 1),
+                     'fraction_of_streaming_copy': round(kbytes / (kern['ms_per_call'] * 1e-3) / 1e9 / copy_gbps, 4),
+                     'note': 'ms_per_call is device time between events around back-to-back launches: it includes the launch gap'})
+        del kern['samples_per_s']
+
+        # host path, per sample on one core
+        def host_validation(b):
+            img = AO.to_tensor(AO.resize_image(Image.fromarray(fr[b]), shape)).half()
+            return img, torch.from_numpy(_host_resize_depth_preserve(dm[B + b], shape)).half(), torch.from_numpy(dm[b]).half()
+
+        def host_train(b):
+            s = AO.train_transforms({'rgb': Image.fromarray(fr[b]), 'rgb_context': [Image.fromarray(fr[B + b]), Image.fromarray(fr[2 * B + b])],
+                                     'intrinsics': K.copy()}, shape, jitter, ())
+            s['depth'] = torch.from_numpy(_host_resize_depth_preserve(dm[b], shape)).float()
+            s['input_depth'] = torch.from_numpy(_host_resize_depth_preserve(dm[B + b], shape)).float()
+            return s
+        random.seed(0)
+        torch.set_num_threads(1)
+        for name, fn in (('host_validation_fp16', host_validation), ('host_train_depth', host_train)):
+            fn(0)
+            ts = []
+            for i in range(max(4, a.reps * 2)):
+                t0 = time.perf_counter()
+                fn(i % B)
+                ts.append(1e3 * (time.perf_counter() - t0))
+            ts.sort()
+            entry[name] = {'ms_per_sample': round(ts[len(ts) // 2], 3), 'ms_min': round(ts[0], 3), 'samples_per_s_per_core': round(1e3 / ts[len(ts) // 2], 1)}
+        # same results on both paths (bit for bit: that is what the tests assert at these shapes too)
+        dv, hv = val_t(val_sample), host_validation(0)
+        entry['validation_matches_host'] = bool(torch.equal(dv['rgb'][0].cpu(), hv[0]) and torch.equal(dv['input_depth'][0, 0].cpu(), hv[1]))
+        result['settings']['b%d' % B] = entry
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--sizes', default='192x640x1,192x640x4,384x1280x1')
@@ -228,7 +340,10 @@ def main():
     ap.add_argument('--metrics-launches', choices=('python', 'fused'), help='run --calls calls of one tail path (for a kernel trace)')
     ap.add_argument('--calls', type=int, default=30, help='--metrics: calls per round and path')
     ap.add_argument('--no-forward', action='store_true', help='--metrics: skip the fp16 network forward')
+    ap.add_argument('--input', action='store_true', help='input pipeline at KITTI shapes: device transforms vs the host path')
     a = ap.parse_args()
+    if a.input:
+        return input_pipeline(a)
     if a.metrics_launches:
         return metrics_launches(a)
     if a.metrics:
