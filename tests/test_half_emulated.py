@@ -3,6 +3,7 @@
 import pytest
 
 import half_cases as HC
+import pack3d_cases as PC
 
 
 @pytest.mark.parametrize('ks', [1, 3, 5, 7])
@@ -35,7 +36,9 @@ def test_groupnorm_h16(emulated_kernels, fused, res):
 
 @pytest.mark.parametrize('nf', [4, 8])
 def test_conv3d_h16(emulated_kernels, nf):
-    HC.conv3d_case('cpu', 2, 5, 4, 6, nf)
+    """Every fp16 forward case of tests/pack3d_cases.py (the per-voxel shapes), through the C ABI into NaN-guarded slots."""
+    for case in PC.select(PC.FWD16_CASES, nf=nf):
+        PC.run_forward16('cpu', case)
 
 
 def test_movement_h16(emulated_kernels):

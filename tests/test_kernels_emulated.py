@@ -4,6 +4,7 @@ every kernel without a GPU; the `-m gpu` tests run the same cases on the real gf
 import pytest
 import torch
 
+import pack3d_cases as PC
 import parity_cases as P
 import tune_cases as TC
 import wgrad_cases as WC
@@ -36,24 +37,14 @@ def test_space_to_depth_channel_slice(emulated_kernels):
     assert torch.equal(ops.space_to_depth(tr), F.pixel_unshuffle(tr, 2))
 
 
-@pytest.mark.parametrize('shape', [(2, 3, 4, 16), (1, 5, 6, 8), (2, 4, 2, 24), (1, 2, 4, 12), (3, 1, 2, 4)])
+@pytest.mark.parametrize('shape', PC.SHUFFLE_SHAPES)
 def test_space_to_depth_depth_to_space_16_byte_forms(emulated_kernels, shape):
     """The float4 forms of the two shuffles (csrc/pack3d.hip: W % 8 == 0 for space_to_depth, W % 4 == 0 for depth_to_space, 16-byte
-    aligned tensors) and the per-element fallbacks (W = 12 / 4, a channel slice at an odd offset) vs torch's pixel_unshuffle /
-    pixel_shuffle -- bit-exact, data movement only."""
-    import torch.nn.functional as F
-    from packnet_sfm.hip import ops
-    B, C, H, W = shape
-    x = torch.randn(B, C, H, W, generator=torch.Generator().manual_seed(sum(shape)))
-    y = ops.space_to_depth(x)
-    assert torch.equal(y, F.pixel_unshuffle(x, 2))
-    assert torch.equal(ops.depth_to_space(y), x)
-    z = torch.randn(B, 4 * C, H, W, generator=torch.Generator().manual_seed(1 + sum(shape)))
-    assert torch.equal(ops.depth_to_space(z), F.pixel_shuffle(z, 2))
-    wide = torch.randn(B, C + 3, H, W, generator=torch.Generator().manual_seed(2 + sum(shape)))
-    for lo in (1, 2):                   # a slice that starts 1 / 2 planes in: aligned or not depending on H * W
-        sl = wide[:, lo:lo + C]
-        assert torch.equal(ops.space_to_depth(sl), F.pixel_unshuffle(sl, 2))
+    aligned tensors), the per-element fallbacks (narrow rows, a tensor 1 or 3 elements off a 16-byte boundary), channel slices and the
+    fp16 forms vs torch's pixel_unshuffle / pixel_shuffle -- bit-exact, data movement only, NaN guards around the output: every case of
+    tests/pack3d_cases.py on this base shape."""
+    for case in PC.select(PC.SHUFFLE_CASES, base=shape):
+        PC.run_shuffle('cpu', case)
 
 
 def test_unpack(emulated_kernels):
@@ -513,73 +504,55 @@ def test_wgrad_ladder_case_emulated(emulated_kernels, case):
     WC.run_case('cpu', case, with_single_split=False, repeat=False)
 
 
+def test_pack3d_table_is_sound():
+    """tests/pack3d_cases.py: volume sizes, the kernel form each case's width and slot alignment select, the data gradient's grid
+    sizes against the XCD renumbering, the weight gradient's run length."""
+    PC.check_table()
+
+
+def test_pack3d_error_returns(emulated_kernels):
+    PC.run_rejects('cpu')
+
+
 @pytest.mark.parametrize('nf', [8, 4])
-@pytest.mark.parametrize('shape', [(1, 5, 4, 6), (2, 13, 3, 5), (1, 40, 2, 3), (1, 5, 4, 8), (2, 13, 3, 4), (1, 9, 5, 12)])
+@pytest.mark.parametrize('shape', PC.FWD_SHAPES)
 def test_conv3d_raw(emulated_kernels, shape, nf):
-    """3x3x3 1->8 stencil: forward, data gradient (column-sliding kernel, ragged run lengths along d; W % 4 == 0 runs the
-    four-outputs-per-thread form) and weight/bias gradient (register accumulation + LDS block reduction) vs the oracle on small
-    odd volumes."""
-    from oracle import packnet_oracle as O
-    from packnet_sfm.hip import functional as HF
-    B, D, H, W = shape
-    g = torch.Generator().manual_seed(sum(shape))
-    p = torch.randn(B, D, H, W, generator=g)
-    w3 = 0.3 * torch.randn(nf, 1, 3, 3, 3, generator=g)
-    b3 = torch.randn(nf, generator=g)
-    pr, wr, br = (t.clone().requires_grad_(True) for t in (p, w3, b3))
-    pd, wd, bd = (t.clone().requires_grad_(True) for t in (p, w3, b3))
-    yr = O.conv3d_1to8(pr, wr, br)
-    dy = torch.randn(yr.shape, generator=g)
-    yr.backward(dy)
-    y = HF.conv3d_1to8(pd, wd, bd)
-    y.backward(dy)
-    P.check(y, yr, 1e-5, 'conv3d fwd')
-    P.check(pd.grad, pr.grad, 1e-5, 'conv3d dgrad')
-    P.check(wd.grad, wr.grad, 1e-5, 'conv3d wgrad')
-    P.check(bd.grad, br.grad, 1e-5, 'conv3d dbias')
+    """3x3x3 1->NF stencil, forward: every case of tests/pack3d_cases.py at this shape (per-voxel and four-voxels-per-thread forms,
+    with and without bias, a misaligned p / out) through the C ABI into NaN-guarded slots, per element against float64; then the
+    autograd node (forward, data gradient at the launcher's run, weight / bias gradient) against the same reference and bounds."""
+    for case in PC.select(PC.FWD_CASES, shape=shape, nf=nf):
+        PC.run_forward('cpu', case)
+    PC.run_autograd('cpu', shape, nf)
 
 
 @pytest.mark.parametrize('nf', [8, 4])
-@pytest.mark.parametrize('run', [8, 4, 2])
-@pytest.mark.parametrize('shape', [(1, 19, 3, 5), (2, 8, 2, 70), (1, 33, 4, 6), (1, 3, 5, 7)])
+@pytest.mark.parametrize('run', PC.DGRAD_RUNS)
+@pytest.mark.parametrize('shape', PC.DGRAD_SHAPES)
 def test_conv3d_dgrad_column_kernel(emulated_kernels, monkeypatch, shape, run, nf):
     """Data gradient of the 3x3x3 stencil on the 8- / 4- / 2-plane column kernel (conv3d_dgrad_col_kernel: the outputs of a run stay
     in registers, one pass per feature) -- what every volume of the training step runs; small volumes reach it through
-    PNSFM_CONV3D_LEN.  Ragged last runs, several runs per column, rows that end inside a wave, D < run."""
-    from oracle import packnet_oracle as O
-    from packnet_sfm.hip import ops
-    monkeypatch.setenv('PNSFM_CONV3D_LEN', str(run))
-    B, D, H, W = shape
-    g = torch.Generator().manual_seed(sum(shape) + run)
-    p = torch.randn(B, D, H, W, generator=g).requires_grad_(True)
-    w3 = 0.3 * torch.randn(nf, 1, 3, 3, 3, generator=g)
-    yr = O.conv3d_1to8(p, w3, torch.zeros(nf))
-    dy = torch.randn(yr.shape, generator=g)
-    yr.backward(dy)
-    P.check(ops.conv3d_backward_data(dy, w3), p.grad, 1e-5, 'conv3d dgrad (run %d)' % run)
+    PNSFM_CONV3D_LEN -- and, at runs of 3 and 1, on the sliding kernel.  Ragged last runs, several runs per column, rows that end
+    inside a wave or exactly with it, W = 1, D < run, grids that are no multiple of 8: the table of tests/pack3d_cases.py, per
+    element against float64, NaN guards, a bit-identical second launch."""
+    if run is None:
+        monkeypatch.delenv('PNSFM_CONV3D_LEN', raising=False)
+    else:
+        monkeypatch.setenv('PNSFM_CONV3D_LEN', str(run))
+    (case,) = PC.select(PC.DGRAD_CASES, shape=shape, run=run, nf=nf)
+    PC.run_dgrad('cpu', case)
 
 
 @pytest.mark.parametrize('nf', [8, 4])
-@pytest.mark.parametrize('variant', ['0', '34'])
-@pytest.mark.parametrize('shape', [(1, 40, 2, 3), (2, 13, 3, 70), (1, 5, 4, 6)])
+@pytest.mark.parametrize('variant', PC.WGRAD_VARIANTS)
+@pytest.mark.parametrize('shape', PC.WGRAD_SHAPES)
 def test_conv3d_wgrad_variants(emulated_kernels, monkeypatch, shape, variant, nf):
     """Weight / bias gradient of the 3x3x3 stencil on both builds of the kernel (PNSFM_CONV3D_WGRAD_RING: 0 = round 3's, default =
     three planes in flight, centre loads + lane exchange, packed register pairs): several runs per column with a ragged last one,
-    rows that end inside a wave, two images."""
-    from oracle import packnet_oracle as O
-    from packnet_sfm.hip import ops
+    rows that end inside a wave, one voxel, three images -- the table of tests/pack3d_cases.py, per element against float64, NaN
+    guards, a bit-identical second launch."""
     monkeypatch.setenv('PNSFM_CONV3D_WGRAD_RING', variant)
-    B, D, H, W = shape
-    g = torch.Generator().manual_seed(sum(shape) + int(variant))
-    p = torch.randn(B, D, H, W, generator=g)
-    w3 = (0.3 * torch.randn(nf, 1, 3, 3, 3, generator=g)).requires_grad_(True)
-    b3 = torch.randn(nf, generator=g).requires_grad_(True)
-    yr = O.conv3d_1to8(p, w3, b3)
-    dy = torch.randn(yr.shape, generator=g)
-    yr.backward(dy)
-    dw, db = ops.conv3d_backward_weight(p, dy)
-    P.check(dw, w3.grad, 1e-5, 'conv3d wgrad (variant %s)' % variant)
-    P.check(db, b3.grad, 1e-5, 'conv3d dbias (variant %s)' % variant)
+    (case,) = PC.select(PC.WGRAD_CASES, shape=shape, variant=variant, nf=nf)
+    PC.run_wgrad('cpu', case)
 
 
 @pytest.mark.parametrize('shape', [(2, 5, 7, 9), (1, 19, 4, 70), (1, 64, 3, 5)])

@@ -204,14 +204,16 @@ def check_table():
 
 
 # ------------------------------------------------------------------------------------------------ the checker
-def _slot(shape, device):
-    """A NaN-filled gradient slot in the middle of a larger NaN-filled 1-D tensor: (whole tensor, view of the slot)."""
+def _slot(shape, device, dtype=torch.float32, offset=0):
+    """A NaN-filled slot inside a larger NaN-filled 1-D tensor, GUARD elements of NaN either side: (whole tensor, view of the slot).
+    offset: elements by which the slot starts past the guard (tests/pack3d_cases.py: a float32 slot 1, 2 or 3 elements off a
+    16-byte boundary)."""
     n = 1
     for s in shape:
         n *= s
-    whole = torch.full((GUARD + n + GUARD,), float('nan'), dtype=torch.float32, device=device)
-    slot = whole[GUARD:GUARD + n].view(shape)
-    assert slot.data_ptr() % 16 == 0 and slot.is_contiguous()
+    whole = torch.full((GUARD + offset + n + GUARD,), float('nan'), dtype=dtype, device=device)
+    slot = whole[GUARD + offset:GUARD + offset + n].view(shape)
+    assert whole.data_ptr() % 16 == 0 and slot.data_ptr() % 16 == (GUARD + offset) * whole.element_size() % 16 and slot.is_contiguous()
     return whole, slot
 
 
@@ -235,7 +237,9 @@ def _launch(ops, case, xs, dy):
 
 def _check_slot(whole, slot, what):
     n = slot.numel()
-    assert bool(torch.isnan(whole[:GUARD]).all()) and bool(torch.isnan(whole[GUARD + n:]).all()), '%s: store outside the gradient slot' % what
+    lo = (slot.data_ptr() - whole.data_ptr()) // whole.element_size()
+    assert lo >= GUARD and whole.numel() - (lo + n) >= GUARD
+    assert bool(torch.isnan(whole[:lo]).all()) and bool(torch.isnan(whole[lo + n:]).all()), '%s: store outside the slot' % what
     assert not bool(torch.isnan(slot).any()), '%s: %d elements never written' % (what, int(torch.isnan(slot).sum()))
 
 
