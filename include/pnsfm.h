@@ -553,6 +553,36 @@ int pnsfm_depth_metrics(const void* gt, int gt_h16, const void* pred, int pred_h
                         float* sampled /*nullable*/, int B, int Hg, int Wg, int Hp, int Wp, float min_depth, float max_depth, int y1,
                         int y2, int x1, int x2, int scale_output, int use_gt_scale, int pred_is_inverse, void* stream);
 
+/* ---- depth output: colour-mapped inverse depth and 16-bit depth values (csrc/depth_output.h), since ABI version 6 ---------------
+ * What the reference's scripts/infer.py:86-107, utils/save.py:49-66 and loggers/wandb_logger.py produce per image on the host, for a
+ * batch on the device.  Maps are contiguous [B][1][H][W], frames [B][3][H][W], fp32 (`_h16` flag 0) or IEEE fp16 (flag 1, processed as
+ * the .float() copy); arithmetic is fp32 with contraction off and IEEE division.  A fixed number of launches whatever B and the image
+ * size (6 with the select, 1 with a caller-supplied normaliser), no device->host copy, no synchronisation, no float atomics:
+ * bit-reproducible.  Every output element is written.  Forward only.  NaN inputs: unspecified.
+ * pnsfm_viz_inv_depth (utils/depth.py:66-100, viz_inv_depth as numpy 2.2 / matplotlib 3.10 evaluate it on a float32 map):
+ *   per image, n = H W, or with filter_zeros the number of values > 0;  q = fp32(percentile) / fp32(100);
+ *   v = fp32(n - 1) q (numpy's virtual index for its default method 'linear');  k = floor(v), gamma = v - k;
+ *   a, b = the order statistics of rank k and k + 1 (both rank n-1 when v >= n-1, both rank 0 when v < 0), exact, by a radix select
+ *   with integer histograms;  d = b - a;  normaliser = gamma < 0.5 ? a + d gamma : b - d (1 - gamma);
+ *   x = clip(inv / (normaliser + fp32(1e-6)), 0, 1);  index = trunc(x N), with x N == N mapped to N - 1.
+ *   use_normalizer != 0: no select, the divisor is fp32(normalizer + 1e-6) with the sum formed in double.  percentile must lie in
+ *   [0, 100], H W must not exceed 2^24 (the fp32 sample count must be exact), 1 <= N <= 256: an error code otherwise.  An image without a selected
+ *   value (filter_zeros, no value > 0) gets normaliser 0, where the reference raises.
+ *   lut8: uint8 [N][3], the colour table as bytes (rint(table 255), formed by the caller).  out: uint8 [B][H][W][3] = lut8[index], or
+ *   with rgb != NULL [B][2 H][W][3] with the frame on top (infer.py's concatenation), a frame byte being value 255 in fp32 rounded half
+ *   to even and saturated to [0, 255].  bgr != 0 swaps the channel order of both halves.  The byte conversions restate what cv2.imwrite
+ *   does with infer.py's float image; OpenCV is not installed where this library is tested, so that rule is NOT pinned against the
+ *   real library.  index (nullable): uint8 [B][H][W], the table index of every pixel.
+ *   ws: the workspace of pnsfm_viz_inv_depth_ws_bytes(B) bytes, 8-byte aligned, no initialisation needed; after the call its first B
+ *   floats are the normalisers of the images.
+ * pnsfm_depth_png16 (utils/depth.py:35-63 write_depth's .png branch on inv2depth, :103-120): out[i] = min(trunc((1 / max(inv[i], 1e-6))
+ *   256), 65535), n elements, uint16 -- the values of the 16-bit depth .png, saturated where the file cannot hold them.  One launch. */
+size_t pnsfm_viz_inv_depth_ws_bytes(int B);
+int pnsfm_viz_inv_depth(const void* inv, int inv_h16, const void* rgb /*nullable*/, int rgb_h16, const uint8_t* lut8, int N, uint8_t* out,
+                        uint8_t* index /*nullable*/, void* ws, int B, int H, int W, float percentile, int filter_zeros,
+                        int use_normalizer, double normalizer, int bgr, void* stream);
+int pnsfm_depth_png16(const void* inv, int inv_h16, uint16_t* out, size_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -170,3 +170,4 @@ int pnsfm_supervised_loss_backward(const float* pred, const float* gt, const dou
 }  // extern "C"
 
 #include "depth_eval.h"      // depth evaluation: post-processing and metrics (same streaming-reduction family)
+#include "depth_output.h"    // depth output: colour-mapped inverse depth and 16-bit depth values (reuses depth_eval.h's select)

@@ -86,6 +86,10 @@ SIGNATURES = {
     "pnsfm_post_process_inv_depth": (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _p]),
     "pnsfm_depth_metrics_ws_bytes": (_sz, [_i]),
     "pnsfm_depth_metrics": (_i, [_p, _i, _p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _i, _i, _i, _i, _i, _i, _i, _p]),
+    # depth output (csrc/depth_output.h)
+    "pnsfm_viz_inv_depth_ws_bytes": (_sz, [_i]),
+    "pnsfm_viz_inv_depth": (_i, [_p, _i, _p, _i, _p, _i, _p, _p, _p, _i, _i, _i, _f, _i, _i, _d, _i, _p]),
+    "pnsfm_depth_png16": (_i, [_p, _i, _p, _sz, _p]),
     "pnsfm_photometric_l1_forward": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p]),
     "pnsfm_photometric_l1_backward": (_i, [_p, _p, _p, _p, _f, _p, _i, _i, _i, _i, _i, _i, _p]),
     "pnsfm_smoothness_forward": (_i, [_p, _p, _p, _i, _i, _i, _p]),

@@ -1699,3 +1699,29 @@ def depth_metrics(gt, pred, min_depth, max_depth, window=None, scale_output='res
         return metrics
     B = gt.shape[0]
     return metrics, rows, (ws[:2 * B].view(torch.float32).reshape(B, 2) if use_gt_scale else None), sampled
+
+
+# ---- depth output (include/pnsfm.h "depth output"; csrc/depth_output.h) -------------------------------------------------------------
+def viz_inv_depth_u8(inv, lut8, rgb=None, normalizer=None, percentile=95, filter_zeros=False, bgr=False, details=False):
+    """The reference's viz_inv_depth (utils/depth.py:66-100) for a batch, as bytes, in a fixed number of launches and without a host
+    sync.  inv [B,1,H,W] and rgb [B,3,H,W] | None: fp32 or fp16 (arithmetic is fp32: an fp16 map gives the result of its .float()
+    copy); lut8: uint8 [N,3] on inv's device, the colour table as bytes (rint(table * 255)), 1 <= N <= 256.  normalizer: None -- the
+    `percentile` of each image's values (of its values > 0 with filter_zeros), exactly np.percentile's float32 result -- or a float.
+    -> uint8 [B,H,W,3] = lut8[index], or with rgb [B,2H,W,3] with the frame on top (what scripts/infer.py concatenates); bgr swaps
+    the channel order of both halves.
+    details=True -> (out, index uint8 [B,H,W] = the table index of every pixel, normalisers fp32 [B])."""
+    if torch.is_grad_enabled() and (inv.requires_grad or (rgb is not None and rgb.requires_grad)):
+        raise NotImplementedError("the depth-output kernels are forward only (inference and logging run under torch.no_grad())")
+    out, index, ws = ops.viz_inv_depth(inv.contiguous(), rgb.contiguous() if rgb is not None else None, lut8.contiguous(), percentile,
+                                       filter_zeros, None if normalizer is None else float(normalizer), bgr, want_index=details)
+    if not details:
+        return out
+    return out, index, ws[:inv.shape[0]].view(torch.float32)
+
+
+def depth_png16(inv):
+    """The values write_depth's .png branch stores for inv2depth(inv) (utils/depth.py:35-63): uint16, inv's shape,
+    min(trunc((1 / max(inv, 1e-6)) * 256), 65535); fp32 or fp16 storage, fp32 arithmetic, one launch."""
+    if torch.is_grad_enabled() and inv.requires_grad:
+        raise NotImplementedError("the depth-output kernels are forward only (inference and logging run under torch.no_grad())")
+    return ops.depth_png16(inv.contiguous())

@@ -723,6 +723,56 @@ def depth_metrics(gt, pred, min_depth, max_depth, window, scale_output, use_gt_s
     return metrics, rows, ws, sampled
 
 
+# ---------------------------------------------------------------------------------- depth output
+VIZ_MAX_PIXELS = 1 << 24
+
+
+def viz_inv_depth_check(B, H, W, N, percentile):
+    """The argument rules of pnsfm_viz_inv_depth that do not need a tensor (the library refuses the same with an error code)."""
+    if B < 1 or H < 1 or W < 1:
+        raise RuntimeError("viz_inv_depth: empty tensor [%d,1,%d,%d]" % (B, H, W))
+    if H * W > VIZ_MAX_PIXELS:
+        raise RuntimeError("viz_inv_depth: %d x %d pixels are above 2^24 (the fp32 sample count must be exact)" % (H, W))
+    if not 1 <= N <= 256:
+        raise RuntimeError("viz_inv_depth: colour table of %d rows (1..256)" % N)
+    if not 0.0 <= float(percentile) <= 100.0:
+        raise ValueError("Percentiles must be in the range [0, 100]")
+
+
+def viz_inv_depth(inv, rgb, lut8, percentile, filter_zeros, normalizer, bgr, want_index=False):
+    """inv [B,1,H,W], rgb [B,3,H,W] | None (fp32 or fp16 each), lut8 uint8 [N,3] on inv's device; normalizer: float | None.
+    -> (out uint8 [B,H,W,3] or [B,2H,W,3] with the frame on top, index uint8 [B,H,W] | None, ws int32 words whose first B words are
+    the fp32 normalisers), all on inv's device; nothing is copied to the host."""
+    _chk(inv, rgb, lut8); _f32_or_h16(inv); _b1hw(inv, "viz_inv_depth: inv_depth")
+    B, _, H, W = inv.shape
+    if lut8.dtype != torch.uint8 or lut8.dim() != 2 or lut8.shape[1] != 3:
+        raise RuntimeError("viz_inv_depth: the colour table must be uint8 [N,3], got %s %s" % (lut8.dtype, tuple(lut8.shape)))
+    viz_inv_depth_check(B, H, W, lut8.shape[0], percentile)
+    if rgb is not None:
+        _f32_or_h16(rgb)
+        if tuple(rgb.shape) != (B, 3, H, W):
+            raise RuntimeError("viz_inv_depth: rgb %s does not match inv_depth %s" % (tuple(rgb.shape), tuple(inv.shape)))
+    lib = _lib.get()
+    out = torch.empty((B, 2 * H if rgb is not None else H, W, 3), dtype=torch.uint8, device=inv.device)
+    index = torch.empty((B, H, W), dtype=torch.uint8, device=inv.device) if want_index else None
+    ws = torch.empty((int(lib.pnsfm_viz_inv_depth_ws_bytes(B)) // 8,), dtype=torch.float64, device=inv.device).view(torch.int32)
+    _lib.check(lib.pnsfm_viz_inv_depth(_ptr(inv), int(inv.dtype == torch.float16), _ptr(rgb), int(rgb is not None and rgb.dtype == torch.float16),
+                                       _ptr(lut8), lut8.shape[0], _ptr(out), _ptr(index), _ptr(ws), B, H, W, float(percentile),
+                                       int(bool(filter_zeros)), int(normalizer is not None), float(normalizer or 0.0), int(bool(bgr)),
+                                       _stream(inv)), "viz_inv_depth")
+    return out, index, ws
+
+
+def depth_png16(inv):
+    """inv: fp32 or fp16, any shape -> uint16 of the same shape: min(trunc((1 / max(inv, 1e-6)) * 256), 65535) (one launch)."""
+    _chk(inv); _f32_or_h16(inv)
+    if inv.numel() == 0:
+        raise RuntimeError("depth_png16: empty tensor")
+    out = torch.empty(inv.shape, dtype=torch.uint16, device=inv.device)
+    _lib.check(_lib.get().pnsfm_depth_png16(_ptr(inv), int(inv.dtype == torch.float16), _ptr(out), inv.numel(), _stream(inv)), "depth_png16")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ NRS
 def nrs_project_forward(direction, ray, temperature):
     """direction, ray: [3,h,w] -> (coords [h,w,2] = expected (row, col), stat [h,w,2] for backward)."""

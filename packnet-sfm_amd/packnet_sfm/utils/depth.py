@@ -151,6 +151,121 @@ def evaluate_depth(config, gt, inv_depth, inv_depth_flipped=None, modes=('', '_p
     return {'metrics': metrics, 'inv_depth': inv_depth_pp}
 
 
+# ---- depth output: the picture and the depth file's values (csrc/depth_output.h) ------------------------------------------------
+_LUT8_CACHE = {}          # (colormap name, device) -> uint8 [N,3] tensor
+
+
+def colormap_lut8(colormap, device):
+    """uint8 [N,3] on `device`: rint(table * 255) of a matplotlib colormap name (resolved at call time to
+    matplotlib.colormaps[name](arange(N))[:, :3]; the device table is cached per (name, device)) or of an [N,3] array / tensor of
+    floats in [0, 1]."""
+    import numpy as np
+    device = torch.device(device)
+    if isinstance(colormap, str):
+        key = (colormap, device)
+        if key not in _LUT8_CACHE:
+            import matplotlib
+            cmap = matplotlib.colormaps[colormap]
+            _LUT8_CACHE[key] = colormap_lut8(cmap(np.arange(cmap.N))[:, :3], device)
+        return _LUT8_CACHE[key]
+    table = colormap.detach().cpu().numpy() if torch.is_tensor(colormap) else np.asarray(colormap)
+    table = table.astype(np.float64)
+    if table.ndim != 2 or table.shape[1] != 3 or not 1 <= table.shape[0] <= 256:
+        raise ValueError('a colour table must be [N,3] with 1 <= N <= 256, got {}'.format(tuple(table.shape)))
+    return torch.from_numpy(np.clip(np.rint(table * 255), 0, 255).astype(np.uint8)).to(device)
+
+
+def _percentile_f32(values, percentile):
+    """np.percentile(values, percentile) of a float32 vector, restated operation by operation in float32 (numpy 2.2, method
+    'linear') -- the arithmetic csrc/depth_output.h runs; 0 for an empty vector (np.percentile raises there)."""
+    import numpy as np
+    f = np.float32
+    n = values.size
+    if n == 0:
+        return f(0)
+    s = np.sort(values)
+    q = f(percentile) / f(100)
+    v = f(n - 1) * q
+    k = np.floor(v)
+    gamma = v - k
+    if v >= f(n - 1):
+        lo = hi = s[n - 1]
+    elif v < 0:
+        lo = hi = s[0]
+    else:
+        lo, hi = s[int(k)], s[int(k) + 1]
+    d = hi - lo
+    return lo + d * gamma if gamma < f(0.5) else hi - d * (f(1) - gamma)
+
+
+def _viz_inv_depth_host(inv, rgb, lut8, normalizer, percentile, filter_zeros, bgr):
+    """viz_inv_depth_u8 for CPU tensors: the formula of include/pnsfm.h ("depth output") in numpy, float32 throughout."""
+    import numpy as np
+    f = np.float32
+    x = inv.detach().float().numpy()[:, 0]
+    lut = lut8.numpy()
+    N = lut.shape[0]
+    B, H, W = x.shape
+    norms = np.zeros((B,), np.float32)
+    index = np.zeros((B, H, W), np.uint8)
+    with np.errstate(all='ignore'):
+        for b in range(B):
+            if normalizer is None:
+                norms[b] = _percentile_f32(x[b][x[b] > 0] if filter_zeros else x[b].ravel(), percentile)
+                divisor = norms[b] + f(1e-6)
+            else:
+                norms[b] = f(normalizer)
+                divisor = f(float(normalizer) + 1e-6)
+            xa = np.clip(x[b] / divisor, f(0), f(1)) * f(N)
+            xa[xa == N] = N - 1
+            index[b] = xa.astype(np.int64).astype(np.uint8)
+    pic = lut[index.astype(np.int64)]
+    if rgb is not None:
+        frame = np.rint(rgb.detach().float().numpy() * f(255))
+        frame = np.clip(frame, 0, 255).astype(np.uint8).transpose(0, 2, 3, 1)
+        pic = np.concatenate([frame, pic], 1)
+    if bgr:
+        pic = pic[..., ::-1]
+    return torch.from_numpy(np.ascontiguousarray(pic)), torch.from_numpy(index), torch.from_numpy(norms)
+
+
+def viz_inv_depth_u8(inv_depth, rgb=None, normalizer=None, percentile=95, colormap='plasma', filter_zeros=False, bgr=False,
+                     details=False):
+    """The reference's viz_inv_depth(...) * 255 as bytes, for a batch: inv_depth [B,1,H,W] (fp32 or fp16) -> uint8 [B,H,W,3]; with
+    rgb [B,3,H,W] -> [B,2H,W,3], the frame on top of the picture (what scripts/infer.py concatenates and writes); bgr=True gives the
+    channel order cv2.imwrite wants.  normalizer None: each image is divided by its own `percentile` (np.percentile's float32
+    result; of its values > 0 with filter_zeros -- an image without one gets 0).  colormap: a matplotlib name or an [N,3] table of
+    floats in [0, 1], N <= 256.  The bytes are rint(value * 255), which is what cv2.imwrite stores for the reference's float image.
+    Device tensors: hip.functional.viz_inv_depth_u8 (a fixed number of launches, no host sync, the result stays on the device);
+    CPU tensors: the same formula in numpy.  details=True -> (out, index uint8 [B,H,W], normalisers fp32 [B])."""
+    if not 0.0 <= float(percentile) <= 100.0:
+        raise ValueError('Percentiles must be in the range [0, 100]')
+    if inv_depth.dim() != 4 or inv_depth.shape[1] != 1:
+        raise ValueError('inv_depth must be [B,1,H,W], got {}'.format(tuple(inv_depth.shape)))
+    if rgb is not None and tuple(rgb.shape) != (inv_depth.shape[0], 3) + tuple(inv_depth.shape[2:]):
+        raise ValueError('rgb {} does not match inv_depth {}'.format(tuple(rgb.shape), tuple(inv_depth.shape)))
+    lut8 = colormap_lut8(colormap, inv_depth.device)
+    if _on_kernels(inv_depth) and (rgb is None or _on_kernels(rgb)):
+        from packnet_sfm.hip import functional as HF
+        res = HF.viz_inv_depth_u8(inv_depth, lut8, rgb=rgb, normalizer=normalizer, percentile=percentile, filter_zeros=filter_zeros,
+                                  bgr=bgr, details=details)
+    else:
+        from packnet_sfm.hip import ops
+        ops.viz_inv_depth_check(inv_depth.shape[0], inv_depth.shape[2], inv_depth.shape[3], lut8.shape[0], percentile)
+        res = _viz_inv_depth_host(inv_depth, rgb, lut8, normalizer, percentile, filter_zeros, bgr)
+        res = res if details else res[0]
+    return res
+
+
+def depth_png16(inv_depth):
+    """uint16, inv_depth's shape: the values the reference's write_depth(filename.png, inv2depth(inv_depth)) stores --
+    (depth * 256).int() -- saturated at 65535.  Device tensors: one kernel launch; CPU tensors: the same formula in torch."""
+    if _on_kernels(inv_depth):
+        from packnet_sfm.hip import functional as HF
+        return HF.depth_png16(inv_depth)
+    return (inv2depth(inv_depth.detach().float()) * 256).int().clamp(max=65535).to(torch.uint16)
+
+
 # names of the reference's module of the same path that the hot path does not re-implement (packnet_sfm/_merge.py)
 from packnet_sfm._merge import reference_fallback as _reference_fallback  # noqa: E402
 __getattr__ = _reference_fallback(__name__, __file__)

@@ -10,6 +10,9 @@
 
     python tools/eval_bench.py --input           # the input pipeline (device validation / training transforms with depth maps) vs the host
 
+    python tools/eval_bench.py --output          # the picture of an inference step (frame over colour-mapped inverse depth): host vs device
+    python tools/eval_bench.py --output-launches --calls 12            # N calls of the device path, for a kernel trace (launch count)
+
 Prints ONE JSON line: per size and path images/s, ms per forward (device events over windows of >= `window` s), host-issue ms per forward,
 conv GFLOP from shapes (as executed, i.e. with the collapsed packing layers, and reference-algorithmic) and achieved conv TFLOP/s."""
 import argparse
@@ -328,6 +331,125 @@ def input_pipeline(a):
     print(json.dumps(result))
 
 
+def _host_viz():
+    """(viz_inv_depth, where it comes from, the colormap argument for the device path).  The reference's own function when a checkout
+    is on the path and loads; otherwise its numpy restatement (np.percentile, in-place divide, clip, colormap call), which the tests
+    hold equal to it -- with matplotlib's plasma, or without matplotlib with the same table from tests/golden/viz.pt."""
+    import numpy as np
+    try:
+        from packnet_sfm.utils import depth as D
+        return D.viz_inv_depth, 'reference checkout', 'plasma'
+    except Exception:
+        pass
+    try:
+        import matplotlib
+        cm, source, colormap = matplotlib.colormaps['plasma'], 'numpy restatement, matplotlib colormap call', 'plasma'
+    except ImportError:
+        table = torch.load(os.path.join(ROOT, 'tests', 'golden', 'viz.pt'), weights_only=False)['plasma'].numpy()
+
+        def cm(x):
+            xa = x * 256
+            xa[xa == 256] = 255
+            return table[xa.astype(int)]
+        source, colormap = 'numpy restatement, plasma table of tests/golden/viz.pt', table
+
+    def viz_inv_depth(inv_depth, percentile=95):
+        x = inv_depth.squeeze(0).detach().cpu().numpy()
+        normalizer = np.percentile(x, percentile)
+        x /= (normalizer + 1e-6)
+        return cm(np.clip(x, 0., 1.0))[:, :, :3]
+    return viz_inv_depth, source, colormap
+
+
+def output_path(a):
+    """The picture an inference step writes (scripts/infer.py:97-107: the frame on top of viz_inv_depth, as bytes), fp32 maps and
+    frames: (a) the host path exactly as infer.py composes it, per image -- frame and map copied to the host, viz_inv_depth(...) *
+    255, the concatenation, the cast to uint8 (rint, what cv2.imwrite does with the float image) -- against (b) the device path --
+    utils.depth.viz_inv_depth_u8 with rgb for the batch, then the device->host copy of the uint8 panel.  Both end with the bytes on
+    the host, so both are timed on the host clock: windows of >= `window` s, alternated, best of `reps`.  The panels must be equal."""
+    import numpy as np
+
+    from packnet_sfm.utils import depth as D
+    dev = torch.device('cuda:0')
+    viz_inv_depth, source, colormap = _host_viz()
+    result = {'tool': 'eval_bench --output', 'device': torch.cuda.get_device_name(0), 'host_function': source, 'dtype': 'fp32',
+              'timing': 'host clock over windows of >= %.1f s, alternated, best of %d; both paths end with the uint8 panel on the host'
+              % (a.window, a.reps),
+              'launches_per_call': {'memset': 1, 'kernels': 5, 'note': 'fixed by csrc/depth_output.h whatever the batch and image size; counted with --output-launches under a kernel trace'},
+              'sizes': {}}
+
+    def window(fn):
+        """(ms per call, ms per call spent in fn's first stage) over one window; fn returns its first stage's seconds."""
+        torch.cuda.synchronize()
+        n, first = 0, 0.0
+        t0 = time.perf_counter()
+        while True:
+            first += fn()
+            n += 1
+            t = time.perf_counter() - t0
+            if t >= a.window and n >= 3:
+                return 1e3 * t / n, 1e3 * first / n
+
+    for spec in a.sizes.split(','):
+        H, W, B = (int(v) for v in spec.split('x'))
+        g = torch.Generator(device=dev).manual_seed(0)
+        image = torch.rand((B, 3, H, W), device=dev, generator=g)
+        pred = 1.0 / (2 + 70 * torch.rand((B, 1, H, W), device=dev, generator=g))
+        panels = {}
+
+        def host():
+            t0 = time.perf_counter()
+            out = []
+            for b in range(B):
+                rgb = image[b].permute(1, 2, 0).detach().cpu().numpy() * 255
+                viz = viz_inv_depth(pred[b]) * 255
+                out.append(np.clip(np.rint(np.concatenate([rgb, viz], 0)), 0, 255).astype(np.uint8))
+            panels['host'] = out
+            return time.perf_counter() - t0
+
+        def device():
+            t0 = time.perf_counter()
+            out = D.viz_inv_depth_u8(pred, rgb=image, colormap=colormap)
+            t1 = time.perf_counter()
+            panels['device'] = out.cpu().numpy()
+            return t1 - t0
+        paths = {'host': host, 'device': device}
+        with torch.no_grad():
+            for fn in paths.values():
+                for _ in range(5):
+                    fn()
+            equal = all(np.array_equal(panels['host'][b], panels['device'][b]) for b in range(B))
+            assert equal, 'the host and the device panel differ at %s' % spec
+            samples = {k: [] for k in paths}
+            for _ in range(a.reps):
+                for k, fn in paths.items():
+                    samples[k].append(window(fn))
+        hm, dm = min(samples['host']), min(samples['device'])
+        result['sizes']['%dx%d_b%d' % (H, W, B)] = {
+            'host_ms_per_image': round(hm[0] / B, 4), 'device_ms_per_image': round(dm[0] / B, 4),
+            'device_ms_per_call': round(dm[0], 4), 'device_host_issue_ms_per_call': round(dm[1], 4),
+            'device_host_issue_share': round(dm[1] / dm[0], 3), 'host_over_device': round(hm[0] / dm[0], 2), 'panels_equal': equal,
+            'host_ms_per_call_all_windows': [round(s[0], 4) for s in samples['host']],
+            'device_ms_per_call_all_windows': [round(s[0], 4) for s in samples['device']]}
+    print(json.dumps(result))
+
+
+def output_launches(a):
+    """`--calls` calls of the device path of --output at 192x640 batch 4 (frame and map, fp32), for `rocprofv3 --kernel-trace`: launches
+    per call = (kernels traced with --calls n2) - (with --calls n1), over n2 - n1."""
+    from packnet_sfm.utils import depth as D
+    dev = torch.device('cuda:0')
+    colormap = _host_viz()[2]
+    with torch.no_grad():
+        g = torch.Generator(device=dev).manual_seed(0)
+        image = torch.rand((4, 3, 192, 640), device=dev, generator=g)
+        pred = 1.0 / (2 + 70 * torch.rand((4, 1, 192, 640), device=dev, generator=g))
+        for _ in range(a.calls):
+            D.viz_inv_depth_u8(pred, rgb=image, colormap=colormap)
+        torch.cuda.synchronize()
+    print(json.dumps({'tool': 'eval_bench --output-launches', 'calls': a.calls}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--sizes', default='192x640x1,192x640x4,384x1280x1')
@@ -341,7 +463,13 @@ def main():
     ap.add_argument('--calls', type=int, default=30, help='--metrics: calls per round and path')
     ap.add_argument('--no-forward', action='store_true', help='--metrics: skip the fp16 network forward')
     ap.add_argument('--input', action='store_true', help='input pipeline at KITTI shapes: device transforms vs the host path')
+    ap.add_argument('--output', action='store_true', help='the picture of an inference step at --sizes: host path vs viz_inv_depth_u8')
+    ap.add_argument('--output-launches', action='store_true', help='run --calls calls of the device path of --output (for a kernel trace)')
     a = ap.parse_args()
+    if a.output_launches:
+        return output_launches(a)
+    if a.output:
+        return output_path(a)
     if a.input:
         return input_pipeline(a)
     if a.metrics_launches:
