@@ -583,6 +583,22 @@ int pnsfm_viz_inv_depth(const void* inv, int inv_h16, const void* rgb /*nullable
                         int use_normalizer, double normalizer, int bgr, void* stream);
 int pnsfm_depth_png16(const void* inv, int inv_h16, uint16_t* out, size_t n, void* stream);
 
+/* ---- velocity supervision: the loss on the translation norms of the predicted poses (csrc/velocity.h), since ABI version 7 -------
+ * replaces VelocityLoss.forward (losses/velocity_loss.py:33-37) and the weighted sum of VelSupModel.forward (models/VelSupModel.py:
+ * 47-51): p[j,b] = |pred_j[b, :3, 3]|_2, g[j,b] = |gt_j[b, :3, 3]|_2, L = (1/J) sum_j mean_b |p[j,b] - g[j,b]|.
+ * pred, gt: HOST tables of J device pointers, each to a contiguous [B,4,4] row-major fp32 matrix stack (Pose.mat; nothing is stacked:
+ * the J tensors stay where they are); only column 3, rows 0..2 of a matrix is read.  1 <= J <= 8: an error code with a
+ * pnsfm_last_error message otherwise.  fp32 only; all arithmetic is fp32.  One launch each way, fixed summation order, no atomics:
+ * bit-reproducible.  Both norms are formed by one device function, so bit-equal translations give p == g exactly.
+ * forward: out2 = {L, loss_in[0] + weight L} (loss_in nullable: then weight L).
+ * backward: upstream: 1 float = d/d(out2[1]); dpred: [J,B,4,4], EVERY entry written: dpred_j[b, :3, 3] = upstream weight
+ * sign(p - g) / (B J) pred_j[b, :3, 3] / p, all other entries 0.  Where p == 0 the gradient is 0 (torch.norm's backward; never 0/0);
+ * where p == g it is 0 (sign(0) = 0).  NaN inputs: unspecified. */
+int pnsfm_velocity_loss_forward(const float* const* pred, const float* const* gt, int J, int B, float weight,
+                                const float* loss_in /*nullable*/, float* out2, void* stream);
+int pnsfm_velocity_loss_backward(const float* const* pred, const float* const* gt, int J, int B, float weight, const float* upstream,
+                                 float* dpred, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

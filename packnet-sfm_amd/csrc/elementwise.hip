@@ -5,6 +5,7 @@
 //                 /root/reference/packnet_sfm/geometry/pose_utils.py:8-52 (euler2mat, pose_vec2mat) and
 //                 /root/reference/packnet_sfm/geometry/pose.py:40-46 (Pose.from_vec); ~85 tiny ATen launches
 //                 (slices, sin/cos, stacks, bmm, cat + their backward) become one launch each way.
+//  velocity_loss: the velocity-supervision term on those matrices' translations lives in velocity.h, included at the end of this file.
 //  adam_step    : torch.optim.Adam (amsgrad=False) on one flat parameter group, as configured by
 //                 /root/reference/packnet_sfm/models/model_wrapper.py:128-149 and stepped at
 //                 /root/reference/packnet_sfm/trainers/horovod_trainer.py:93 (28 B/parameter of HBM traffic).
@@ -556,3 +557,5 @@ int pnsfm_pack_bias_eff_backward(const float* g, const float* Ssum, const float*
 }
 
 }  // extern "C"
+
+#include "velocity.h"      // velocity supervision: the loss on the pose matrices' translation norms (same [B,4,4] layout)

@@ -90,6 +90,9 @@ SIGNATURES = {
     "pnsfm_viz_inv_depth_ws_bytes": (_sz, [_i]),
     "pnsfm_viz_inv_depth": (_i, [_p, _i, _p, _i, _p, _i, _p, _p, _p, _i, _i, _i, _f, _i, _i, _d, _i, _p]),
     "pnsfm_depth_png16": (_i, [_p, _i, _p, _sz, _p]),
+    # velocity supervision (csrc/velocity.h)
+    "pnsfm_velocity_loss_forward": (_i, [_p, _p, _i, _i, _f, _p, _p, _p]),
+    "pnsfm_velocity_loss_backward": (_i, [_p, _p, _i, _i, _f, _p, _p, _p]),
     "pnsfm_photometric_l1_forward": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p]),
     "pnsfm_photometric_l1_backward": (_i, [_p, _p, _p, _p, _f, _p, _i, _i, _i, _i, _i, _i, _p]),
     "pnsfm_smoothness_forward": (_i, [_p, _p, _p, _i, _i, _i, _p]),

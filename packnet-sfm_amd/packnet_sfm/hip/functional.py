@@ -1366,6 +1366,57 @@ def loss_combine(photometric, smoothness, weight):
     return LossCombineFn.apply(float(weight), len(photometric), *photometric, *smoothness)
 
 
+class VelocityLossFn(Function):
+    """Velocity supervision on J predicted [B,4,4] stacks (csrc/velocity.h; the reference's losses/velocity_loss.py:33-37 plus the
+    weighted sum of models/VelSupModel.py:47-51, about 20 ATen launches each way): L = (1/J) sum_j mean_b | |t_pred| - |t_gt| |, one
+    launch each way.  Returns (loss_in + weight * L, L) as 0-dim tensors; only the first carries a gradient."""
+
+    @staticmethod
+    def forward(ctx, weight, J, *tensors):
+        pred, gt = list(tensors[:J]), list(tensors[J:2 * J])
+        loss_in = tensors[2 * J] if len(tensors) > 2 * J else None
+        ctx.meta = (float(weight), J, None if loss_in is None else tuple(loss_in.shape))
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(*pred, *gt)
+        out = ops.velocity_loss_forward(pred, gt, weight, None if loss_in is None else loss_in.detach().reshape(1))
+        total, L = out[1], out[0]
+        ctx.mark_non_differentiable(L)
+        return total, L
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _gl):
+        weight, J, in_shape = ctx.meta
+        n_in = 2 * J + (in_shape is not None)
+        if g is None:
+            return (None,) * (2 + n_in)
+        saved = ctx.saved_tensors
+        d = ops.velocity_loss_backward(list(saved[:J]), list(saved[J:]), weight, g.reshape(1).contiguous())
+        grads = tuple(d[j] if ctx.needs_input_grad[2 + j] else None for j in range(J)) + (None,) * J
+        if in_shape is not None:
+            grads += (g.reshape(in_shape),)
+        return (None, None) + grads
+
+
+def velocity_loss(pred_mats, gt_mats, weight=1.0, loss_in=None):
+    """(loss_in + weight * L, L) for lists of J predicted and J ground-truth [B,4,4] transforms: 0-dim tensors, the second without
+    gradient (the metric); without loss_in the first is weight * L.  Predictions and loss_in are float32; ground-truth poses may
+    arrive as float64 (dataset poses) and are cast once.  The gradient reaches the predicted matrices and loss_in."""
+    pred_mats, gt_mats = list(pred_mats), list(gt_mats)
+    for j, t in enumerate(pred_mats):
+        if not torch.is_tensor(t) or t.dtype != torch.float32:
+            raise TypeError('velocity_loss: pred_mats[%d] must be a float32 tensor, got %s' % (j, getattr(t, 'dtype', type(t))))
+    for j, t in enumerate(gt_mats):
+        if not torch.is_tensor(t) or t.dtype not in (torch.float32, torch.float64):
+            raise TypeError('velocity_loss: gt_mats[%d] must be a float32 or float64 tensor, got %s' % (j, getattr(t, 'dtype', type(t))))
+    if loss_in is not None and (not torch.is_tensor(loss_in) or loss_in.dtype != torch.float32 or loss_in.numel() != 1):
+        raise TypeError('velocity_loss: loss_in must be a float32 tensor of one element, got %s'
+                        % (getattr(loss_in, 'dtype', type(loss_in)),))
+    gt_mats = [t.detach().to(torch.float32).contiguous() for t in gt_mats]
+    extra = () if loss_in is None else (loss_in,)
+    return VelocityLossFn.apply(float(weight), len(pred_mats), *[t.contiguous() for t in pred_mats], *gt_mats, *extra)
+
+
 class SupervisedLossFn(Function):
     """One scale of the supervised inverse-depth loss (l1 / mse / abs_rel / berhu / silog, optionally only where gt > 0)."""
 

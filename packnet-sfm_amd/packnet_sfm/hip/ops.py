@@ -471,6 +471,44 @@ def loss_combine_backward(g, n, ns, weight):
     return dout
 
 
+# ------------------------------------------------------------------------------- velocity supervision
+def _velocity_tables(pred_mats, gt_mats):
+    """The two host tables of device pointers (include/pnsfm.h "velocity supervision") for lists of [B,4,4] fp32 stacks."""
+    J = len(pred_mats)
+    if J < 1 or len(gt_mats) != J:
+        raise ValueError("velocity_loss needs as many ground-truth stacks as predicted ones, at least one (got %d, %d)" % (len(gt_mats), J))
+    ts = list(pred_mats) + list(gt_mats)
+    _chk(*ts); _f32(*ts)
+    B = pred_mats[0].shape[0]
+    for t in ts:
+        if tuple(t.shape) != (B, 4, 4):
+            raise ValueError("velocity_loss needs [B,4,4] stacks of one batch size, got %s" % (tuple(t.shape),))
+    n = max(J, 1)                                  # the library checks J against its maximum: pass every pointer through
+    P = (ctypes.c_void_p * n)(*[t.data_ptr() for t in pred_mats])
+    G = (ctypes.c_void_p * n)(*[t.data_ptr() for t in gt_mats])
+    return P, G, J, B
+
+
+def velocity_loss_forward(pred_mats, gt_mats, weight, loss_in=None):
+    """pred_mats / gt_mats: lists of J [B,4,4] stacks -> out2 = (L, loss_in + weight * L); loss_in: 1-element device tensor or None."""
+    P, G, J, B = _velocity_tables(pred_mats, gt_mats)
+    _chk(pred_mats[0], loss_in); _f32(loss_in)
+    out = torch.empty((2,), dtype=torch.float32, device=pred_mats[0].device)
+    _lib.check(_lib.get().pnsfm_velocity_loss_forward(ctypes.byref(P), ctypes.byref(G), J, B, float(weight), _ptr(loss_in), _ptr(out),
+                                                      _stream(out)), "velocity_loss_forward")
+    return out
+
+
+def velocity_loss_backward(pred_mats, gt_mats, weight, upstream):
+    """upstream: 1-element device tensor = d/d(out2[1]) -> [J,B,4,4]: the gradient of every predicted stack, all entries written."""
+    P, G, J, B = _velocity_tables(pred_mats, gt_mats)
+    _chk(pred_mats[0], upstream); _f32(upstream)
+    dpred = torch.empty((J, B, 4, 4), dtype=torch.float32, device=upstream.device)
+    _lib.check(_lib.get().pnsfm_velocity_loss_backward(ctypes.byref(P), ctypes.byref(G), J, B, float(weight), _ptr(upstream),
+                                                       _ptr(dpred), _stream(dpred)), "velocity_loss_backward")
+    return dpred
+
+
 # ------------------------------------------------------------------------------------------ invdepth
 def invdepth_act_forward(x, min_depth):
     _chk(x); _f32(x)
