@@ -122,90 +122,6 @@ __device__ __forceinline__ float pad_coordinate(float x, int size, int mode, flo
   return x;
 }
 
-// The bilinear sample of the three channels of context image (j, b) at the projection of target pixel (u, v): the body of
-// view_synthesis_fwd_kernel.  (Round 5 also called it from photometric kernels that computed the warped images in their tile loaders;
-// measured -0.3 % twice, profiles/r05_ab_loss_fuse.txt, removed in round 6.)
-__device__ __forceinline__ void warp_sample3(const Cam& cam, const float* Tm, float rho, int u, int v, int H, int W, int pad_mode,
-                                             const float* __restrict__ rb, float (&out)[3]) {
-  const int HW = H * W;
-  Proj q;
-  project_pixel(cam, Tm, rho, u, v, H, W, q);
-  out[0] = out[1] = out[2] = 0.f;
-  float mx, my;
-  q.ix = pad_coordinate(q.ix, W, pad_mode, mx);
-  q.iy = pad_coordinate(q.iy, H, pad_mode, my);
-  if (q.ix > -1.f && q.ix < (float)W && q.iy > -1.f && q.iy < (float)H) {
-    const float fx0 = floorf(q.ix), fy0 = floorf(q.iy);
-    const int x0 = (int)fx0, y0 = (int)fy0, x1 = x0 + 1, y1 = y0 + 1;
-    const float ax = q.ix - fx0, ay = q.iy - fy0;
-    const float wnw = (1.f - ax) * (1.f - ay), wne = ax * (1.f - ay), wsw = (1.f - ax) * ay, wse = ax * ay;
-    const bool vx0 = x0 >= 0 && x0 < W, vx1 = x1 >= 0 && x1 < W, vy0 = y0 >= 0 && y0 < H, vy1 = y1 >= 0 && y1 < H;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float* rc = rb + (size_t)c * HW;
-      float acc = 0.f;
-      if (vx0 && vy0) acc += rc[y0 * W + x0] * wnw;
-      if (vx1 && vy0) acc += rc[y0 * W + x1] * wne;
-      if (vx0 && vy1) acc += rc[y1 * W + x0] * wsw;
-      if (vx1 && vy1) acc += rc[y1 * W + x1] * wse;
-      out[c] = acc;
-    }
-  }
-}
-
-// Backward of warp_sample3 for one target pixel and one context image: g[c] = d loss / d warped[c] -> the pixel's contribution to
-// d loss / d inv_depth (returned) and to the 12 entries of d loss / d T[:3, :4] (gT): the body of view_synthesis_bwd_kernel.
-__device__ __forceinline__ float warp_backward3(const Cam& cam, const float* Tm, float rho, int u, int v, int H, int W, int pad_mode,
-                                                const float* __restrict__ rb, const float (&g)[3], float (&gT)[12]) {
-  const int HW = H * W;
-  Proj q;
-  project_pixel(cam, Tm, rho, u, v, H, W, q);
-  float gix = 0.f, giy = 0.f;
-  float mx, my;
-  q.ix = pad_coordinate(q.ix, W, pad_mode, mx);
-  q.iy = pad_coordinate(q.iy, H, pad_mode, my);
-  if (q.ix > -1.f && q.ix < (float)W && q.iy > -1.f && q.iy < (float)H) {
-    const float fx0 = floorf(q.ix), fy0 = floorf(q.iy);
-    const int x0 = (int)fx0, y0 = (int)fy0, x1 = x0 + 1, y1 = y0 + 1;
-    const float ax = q.ix - fx0, ay = q.iy - fy0;
-    const bool vx0 = x0 >= 0 && x0 < W, vx1 = x1 >= 0 && x1 < W, vy0 = y0 >= 0 && y0 < H, vy1 = y1 >= 0 && y1 < H;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float* rc = rb + (size_t)c * HW;
-      const float nw = (vx0 && vy0) ? rc[y0 * W + x0] : 0.f;
-      const float ne = (vx1 && vy0) ? rc[y0 * W + x1] : 0.f;
-      const float sw = (vx0 && vy1) ? rc[y1 * W + x0] : 0.f;
-      const float se = (vx1 && vy1) ? rc[y1 * W + x1] : 0.f;
-      gix += g[c] * ((ne - nw) * (1.f - ay) + (se - sw) * ay);
-      giy += g[c] * ((sw - nw) * (1.f - ax) + (se - ne) * ax);
-    }
-  }
-  gix *= mx;
-  giy *= my;
-  const float iz = 1.f / q.z;
-  float gp[3];
-  gp[0] = gix * iz;
-  gp[1] = giy * iz;
-  gp[2] = (q.p[2] >= 1e-5f) ? -(gix * q.p[0] + giy * q.p[1]) * iz * iz : 0.f;
-  float gXr[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) gXr[i] = cam.rk[0 + i] * gp[0] + cam.rk[3 + i] * gp[1] + cam.rk[6 + i] * gp[2];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    gT[4 * i + 0] = gXr[i] * q.X[0];
-    gT[4 * i + 1] = gXr[i] * q.X[1];
-    gT[4 * i + 2] = gXr[i] * q.X[2];
-    gT[4 * i + 3] = gXr[i];
-  }
-  float gd = 0.f;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float gX = Tm[0 + k] * gXr[0] + Tm[4 + k] * gXr[1] + Tm[8 + k] * gXr[2];
-    gd += q.ray[k] * gX;
-  }
-  return rho >= 1e-6f ? -gd * q.d * q.d : 0.f;
-}
-
 // grid: (ceil(HW/256), B, J)
 __global__ void __launch_bounds__(256) view_synthesis_fwd_kernel(const float* __restrict__ inv_depth, const float* __restrict__ ref,
                                                                   const float* __restrict__ K, const float* __restrict__ refK,
