@@ -96,6 +96,25 @@ int pnsfm_conv2d_forward_strided(const float* x, const float* wp_fwd, const floa
 int pnsfm_conv2d_backward_weight_strided(const float* x, const float* dy, float* dw, float* dbias /*nullable*/,
                                          int B, int Cin, int Cout, int Hin, int Win, int ks, int stride, void* stream);
 
+/* Row windows (stride 1, k = 3 | 5 | 7, one input tensor): the border strips of the collapsed packing block
+ * (networks/layers/packnet/layers01.py: PackLayerConv3d._conv_collapsed) keep only the r = k/2 frame rows of a strip of 2r rows, so the
+ * convolution is computed for those rows alone.  The map the launch TILES has H rows (y of _forward_rows, dx of _backward_data_rows,
+ * dy of _backward_weight_rows), the map it READS has Hi rows (x, dy, x); tiled row j of sample b reads rows j - k/2 .. j + k/2 of the
+ * read map, shifted down by yshift for the samples b >= shift_from_b; rows outside [0, Hi) are zero, like the padding.
+ *   forward, H = r, Hi = 2r:        leading half (yshift 0) = top frame rows, zero above; trailing half (yshift r) = bottom frame rows
+ *   backward-data, H = 2r, Hi = r:  the same window transposed: yshift -r for the trailing half
+ *   weight gradient, H = r, Hi = 2r: the pixel loop runs over dy's grid; yshift as forward
+ * The arithmetic per output element is that of the plain entry points (same K order).  The 1x1 and stem kernels take no row
+ * window: such a launch fails with a message.  A row-window launch has its own tuning key (pnsfm_tune_key_rows); without a decision
+ * under it, it takes the K split (forward / backward-data) or the whole decision (weight gradient) of the plain launch over the
+ * full strip of max(H, Hi) rows, so that its results are that launch's bit for bit -- the rows it leaves out only ever added zeros. */
+int pnsfm_conv2d_forward_rows(const float* x, const float* wp_fwd, const float* bias /*nullable*/, float* y, int B, int Cin, int Cout,
+                              int H, int Hi, int W, int ks, int yshift, int shift_from_b, void* stream);
+int pnsfm_conv2d_backward_data_rows(const float* dy, const float* wp_bwd, float* dx, int B, int Cin, int Cout, int H, int Hi, int W,
+                                    int ks, int yshift, int shift_from_b, void* stream);
+int pnsfm_conv2d_backward_weight_rows(const float* x, const float* dy, float* dw, float* dbias /*nullable*/, int B, int Cin, int Cout,
+                                      int H, int Hi, int W, int ks, int yshift, int shift_from_b, void* stream);
+
 /* Runtime autotuning of the conv kernels' tiling / split factors (default on; env PNSFM_AUTOTUNE=0 turns it off).
  * The first call for a new shape times the candidate configurations on the caller's stream (it synchronises), like
  * `torch.backends.cudnn.benchmark = True` in the reference (trainers/horovod_trainer.py:19). */
@@ -146,9 +165,12 @@ int pnsfm_tune_set(const int* key7, int v0, int v1);
  * _backward_weight_cat).  Depends on the arithmetic mode in force (pnsfm_set_conv_math).  Pure host query: no pointers, no launch;
  * non-zero (message in pnsfm_last_error) for a shape the launch would refuse. */
 int pnsfm_tune_key(int kind, int B, int Cin, int Cout, int H, int W, int ks, int stride, int nsrc, int* key7);
+/* ... of a row-window launch (pnsfm_conv2d_*_rows): H rows tiled, Hi rows read.  key7[0] carries 10000 * Hi on top of the plain
+ * launch's kind, so the plain launch of the same (B, Cin, Cout, H, W, ks) keeps its own decision. */
+int pnsfm_tune_key_rows(int kind, int B, int Cin, int Cout, int H, int Hi, int W, int ks, int* key7);
 /* What the calling thread's most recent forward / backward-data launch actually ran: out8 = {variant (0..2 f32 stagings, 3..6
  * split-bf16 LDS plans, 7 ping-pong workgroup, 8 the 1x1 kernel without LDS), pixel tiles per wave NT, M tiles per wave MT, taps per weight stage G, K-split,
- * tile mode (0 classic, 1 16-wide rectangles, 2 row bands), workgroups, LDS bytes}.  A pinned configuration that does not fit
+ * tile mode (0 classic, 1 16-wide rectangles, 2 row bands, 3 short-map rectangles: all rows of a map of < 4 rows), workgroups, LDS bytes}.  A pinned configuration that does not fit
  * a shape silently falls back to the heuristic one; tests that pin a variant assert on this.  A backward-weight call that ran the
  * stem's kernel (3 input channels, 5x5) leaves {105, 0, MT, 0, pixel splits, 0, workgroups, 0}.
  * Every backward-weight call leaves the kernel build it LAUNCHED (written where the template instantiation is chosen: a decision the

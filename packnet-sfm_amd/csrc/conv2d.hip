@@ -78,6 +78,7 @@ static bool conv_geom_fixed(int B, int Cin, int Cout, int H, int W, int ks, int 
   g.DMA = DMA;
   g.stem = 0;
   g.TW = g.TH = 0;
+  g.tm = tm;
   if (tm != 0 && DMA < 3) return false;
   const int HW = H * W;
   g.MT = conv_pick_MT(Cout);
@@ -90,12 +91,16 @@ static bool conv_geom_fixed(int B, int Cin, int Cout, int H, int W, int ks, int 
   g.CI = Cin <= 8 ? 8 : 16;    // K-chunk: multiple of 8 channels = whole batches of 4 MFMA k-steps
   g.mode = (W % 32 == 0) ? 0 : 1;
   g.NT = NT;
-  if (tm == 1 || tm == 2) {
+  if (tm == 1 || tm == 2 || tm == 3) {
     // (on 32-multiple widths the default tiles already are 32 x 4*NT rectangles; the 16 x 8*NT ones are offered there for the 5x5 /
     // 7x7 layers only: 22 x 22 staged pixels instead of 14 x 38 for 256 outputs of a 7x7, which also fits the register prefetch)
-    if (W % 32 == 0 && (tm == 2 || ks < 5)) return false;
-    g.TW = tm == 1 ? 16 : W;
-    g.TH = tm == 1 ? 8 * NT : (128 * NT) / W;
+    if (tm != 3 && W % 32 == 0 && (tm == 2 || ks < 5)) return false;
+    // tm 3, maps of fewer than 4 rows (the frame rows of the packing block's border strips: 1 or 2): all H rows x 128*NT / H columns.
+    // The 4*NT-row tiles of the classic tiling leave half or three quarters of their slots past the map there, and the linear runs'
+    // full-width patches do not fit the LDS at the widths of the high-resolution strips.
+    if (tm == 3 && (H >= 4 || W < 32)) return false;
+    g.TW = tm == 1 ? 16 : (tm == 2 ? W : std::min((128 * NT) / H, round_up(W, 16)));
+    g.TH = tm == 1 ? 8 * NT : (tm == 2 ? (128 * NT) / W : H);
     if (g.TH < 1 || (tm == 1 && W < 16)) return false;
     if (g.TH > H) g.TH = H;
     // useful share of the tile grid: slots that hold a pixel of the image (a bad quantisation loses to the linear runs)
@@ -330,7 +335,8 @@ static void tune_db_append(const std::array<int, 7>& k, const std::array<int, 2>
 //   key kind            v0                                                      v1
 //   x0 / x1  forward,   NT | variant << 4 | forceMT << 8 | tm << 9              K-split
 //     backward-data       NT 1 | 2: 32-pixel tiles per wave; variant 0..8: the kernel (file header); forceMT 1: 32-row M
-//                         tiles where 64 would fit; tm 0 | 1 | 2: classic tiles, 16-wide rectangles, row bands
+//                         tiles where 64 would fit; tm 0 | 1 | 2 | 3: classic tiles, 16-wide rectangles, row bands, short-map
+//                         rectangles (all H < 4 rows x 128 NT / H columns)
 //   x2  weight gradient pixel split                                             kernel | parameters << 4
 //                         kernel 0  generic f32 (the stem's own kernel where it applies)    0
 //                         kernel 1  tap-major (conv2d_wgrad2.hip)                           1
@@ -435,7 +441,8 @@ struct ConvArgs {
   float* y;           // [B][Cout][H][W]
   float* ws;          // K-split launches: [splitK][B][Cout][H][W] partial outputs (stream scratch), summed by conv_splitk_reduce_kernel
   int B, Cin, Cout, H, W, KS;   // H, W: OUTPUT size
-  int S, Hi, Wi;                // stride (1 | 2) and INPUT size (Hi = H, Wi = W when S == 1)
+  int S, Hi, Wi;                // stride (1 | 2) and INPUT size (Wi = W when S == 1; Hi = H too unless the launch is a row window)
+  int yshift, shift_from_b;     // row window (ConvRows, pnsfm_common.h): patch rows of samples >= shift_from_b start yshift rows lower (0: off)
   int CI, mode, tiles_x, tiles_per_img, PH, PW, KP, MP, nchunks, chunks_per_split, splitK;
   int TW, TH;         // mode 2 (split-bf16 kernels): tile width / height in output pixels
   int pstride;        // DMA variants: floats between the two patch buffers
@@ -626,6 +633,7 @@ __global__ void __launch_bounds__(256) conv2d_mfma_kernel(ConvArgs a) {
       boff[nt] = ((yy - r0) * a.PW + ox[nt]) * S;
     }
   }
+  if (b >= a.shift_from_b) py0 += a.yshift;      // row window (ConvRows): 0 for every other launch
 
   f32x16 acc[MT][NT];
 #pragma unroll
@@ -912,6 +920,7 @@ __global__ void __launch_bounds__(256) conv2d_pipe_kernel(ConvArgs a) {
       boff[nt] = ((yy - r0) * a.PW + ox[nt]) * S;
     }
   }
+  if (b >= a.shift_from_b) py0 += a.yshift;      // row window (ConvRows): 0 for every other launch
 
   f32x16 acc[MT][NT];
 #pragma unroll
@@ -1129,7 +1138,7 @@ struct ConvGnOut {
 
 static int enqueue_conv(const ConvGeom& g, const float* x, const float* wp, const float* bias, float* y, int B, int Cin,
                         int Cout, int H, int W, int ks, hipStream_t stream, const char* what, int S, int Hi, int Wi,
-                        const ConvSrc* ms = nullptr, ConvGnOut* gn = nullptr) {
+                        const ConvSrc* ms = nullptr, ConvGnOut* gn = nullptr, const ConvRows* rows = nullptr) {
   ConvArgs a;
   a.addend = gn ? gn->addend : nullptr; a.addend_bs = gn ? gn->addend_bs : 0;
   a.x = x; a.wp = wp; a.bias = bias; a.y = y;
@@ -1140,6 +1149,9 @@ static int enqueue_conv(const ConvGeom& g, const float* x, const float* wp, cons
   if (a.addend && g.DMA < 3) { set_error("%s: an addend needs the split-bf16 kernels (>= 16 channels of dy, 'bx3' arithmetic)", what); return -1; }
   a.B = B; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W; a.KS = ks;
   a.S = S; a.Hi = Hi; a.Wi = Wi;
+  a.yshift = rows ? rows->yshift : 0; a.shift_from_b = rows ? rows->shift_from_b : 0;
+  // the kernels without a row window (LDS-free 1x1, the stem's own) refuse one instead of ignoring it
+  if (rows && (g.DMA == 8 || g.stem)) { set_error("%s: the 1x1 / stem kernels take no row window", what); return -1; }
   a.CI = g.CI; a.mode = g.mode; a.tiles_x = g.tiles_x; a.tiles_per_img = g.tiles_per_img;
   a.TW = g.TW; a.TH = g.TH;
   a.PH = g.PH; a.PW = g.PW; a.KP = g.KP; a.MP = g.MP; a.nchunks = g.nchunks;
@@ -1269,12 +1281,18 @@ static void for_split_candidates(int tiles, int base_blocks, long floor_blocks, 
 // stream and returns the fastest (`g`, the heuristic geometry, when nothing could be timed).  (g_tune_mu held)
 static ConvDecision conv_tune(const ConvGeom& g, const std::array<int, 7>& key, bool bx3, const float* x, const float* wp,
                               const float* bias, float* y, int B, int Cin, int Cout, int H, int W, int ks, hipStream_t stream,
-                              const char* what, int kind_tag, int S, int Hi, int Wi, const ConvSrc* ms) {
-  static const int kSplits[] = {1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 48, 64};
+                              const char* what, int kind_tag, int S, int Hi, int Wi, const ConvSrc* ms, const ConvRows* rows,
+                              int fixed_split = 0) {
+  // fixed_split > 0 (a row window, launch_conv): the K split is given -- only the kernel, the tiles and the M tile are timed
+  static const int kAllSplits[] = {1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 48, 64};
+  const int kOneSplit[] = {fixed_split};
+  const int* const kSplits = fixed_split > 0 ? kOneSplit : kAllSplits;
+  const int nSplits = fixed_split > 0 ? 1 : (int)(sizeof kAllSplits / sizeof kAllSplits[0]);
   float best_ms = 1e30f;
   ConvDecision best = {g.NT, g.DMA, 0, 0, g.splitK};
   const int nMT = (conv_pick_MT(Cout) == 2) ? 2 : 1;
   const int nTM = (bx3 && (W % 32 != 0 || ks >= 5)) ? (W % 32 != 0 ? 3 : 2) : 1;       // tile modes (rectangles / row bands) exist for the split-bf16 kernels
+  const int nTMs = bx3 && H < 4 ? 4 : nTM;      // ... and the short-map rectangles (tm 3) for maps of fewer than 4 rows
   // PNSFM_PP: which launches may take the ping-pong workgroup (variant 7): bit 0 forward, bit 1 backward-data (default 3: both)
   static const int pp_mask = [] { const char* e = getenv("PNSFM_PP"); return (e && e[0]) ? atoi(e) : 3; }();
   const bool pp_on = ((pp_mask >> (kind_tag & 1)) & 1) != 0;
@@ -1287,18 +1305,20 @@ static ConvDecision conv_tune(const ConvGeom& g, const std::array<int, 7>& key, 
   } else {
     for (int v = 0; v <= 2; ++v) vars[nVar++] = v;
   }
-  for (int cfgt = 0; cfgt < 2 * nVar * nMT * nTM; ++cfgt) {
+  for (int cfgt = 0; cfgt < 2 * nVar * nMT * nTMs; ++cfgt) {
     const int cfg = cfgt % (2 * nVar * nMT), tm = cfgt / (2 * nVar * nMT);
+    if (tm >= nTM && tm != 3) continue;
     const int NT = 2 - (cfg & 1), DA = vars[(cfg >> 1) % nVar], fMT = cfg / (2 * nVar);
     int last_split = -1;
-    for (int want : kSplits) {
+    for (int si = 0; si < nSplits; ++si) {
+      const int want = kSplits[si];
       ConvGeom c;
       if (!conv_geom_fixed(B, Cin, Cout, H, W, ks, NT, want, c, DA, S, fMT, tm)) break;
       if (c.splitK == last_split) continue;
       last_split = c.splitK;
       const long blocks = (long)B * c.tiles_per_img * (c.MP / (32 * c.MT)) * c.splitK;
-      if (c.splitK > 1 && blocks > 24L * 256 * 4) break;      // already far more blocks than the chip holds
-      const float tms = time_on_stream(stream, 2, [&]() { return enqueue_conv(c, x, wp, bias, y, B, Cin, Cout, H, W, ks, stream, what, S, Hi, Wi, ms); });
+      if (c.splitK > 1 && blocks > 24L * 256 * 4 && fixed_split <= 0) break;      // already far more blocks than the chip holds
+      const float tms = time_on_stream(stream, 2, [&]() { return enqueue_conv(c, x, wp, bias, y, B, Cin, Cout, H, W, ks, stream, what, S, Hi, Wi, ms, nullptr, rows); });
       const ConvDecision cand = {NT, DA, fMT, tm, c.splitK};
       tune_log(key, cand.encode()[0], cand.split, tms);
       if (tms > 0.f && tms < best_ms) { best_ms = tms; best = cand; }
@@ -1320,8 +1340,11 @@ void conv_last_config_set(int code, int p1, int p2, int p3, int splits, int p5, 
 // tuning decision: the one place that forms that key (launch_conv looks it up, pnsfm_tune_key reports it).  H, W: the OUTPUT map, in
 // and out -- a 1x1 stride-1 layer has no halo, any pixel order works, so a map whose width is not a multiple of 32 is tiled as 32-wide
 // rows of the flattened image when that is exact (whole 2-D tiles instead of linear runs whose patches span full-width rows).
+// key[0] of a row-window launch (forward, backward-data, weight gradient): + kRowsKey * Hi, the rows of the map it reads
+static const int kRowsKey = 10000;
+
 static int conv_tune_key(const char* what, int kind_tag, int B, int Cin, int Cout, int& H, int& W, int ks, int S, ConvGeom& g,
-                         std::array<int, 7>& key) {
+                         std::array<int, 7>& key, const ConvRows* rows = nullptr) {
   if (B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) { set_error("%s: bad shape", what); return -1; }
   if (ks != 1 && ks != 3 && ks != 5 && ks != 7) { set_error("%s: unsupported kernel size %d", what, ks); return -1; }
   if (S != 1 && S != 2) { set_error("%s: unsupported stride %d", what, S); return -1; }
@@ -1329,16 +1352,46 @@ static int conv_tune_key(const char* what, int kind_tag, int B, int Cin, int Cou
   g = conv_geom(B, Cin, Cout, H, W, ks, S);
   if (g.smem_bytes > (g.DMA >= 2 ? kMaxSmemPipe : kMaxSmem)) { set_error("%s: image too wide for the LDS halo patch (W=%d)", what, W); return -1; }
   key = {kind_tag + 10 * S + (conv_use_bx3(Cin, ks) ? 100 : 0), B, Cin, Cout, H, W, ks};
+  if (rows) {
+    // a row window is not the plain launch of the same (B, Cin, Cout, H, W, ks): its key carries the rows it reads (kRowsKey * Hi)
+    if (S != 1 || ks < 3 || g.stem) { set_error("%s: a row window needs a stride-1 3x3 / 5x5 / 7x7 layer the stem kernel does not take", what); return -1; }
+    if (rows->Hi <= 0 || rows->shift_from_b < 0) { set_error("%s: bad row window", what); return -1; }
+    key[0] += kRowsKey * rows->Hi;
+  }
   return 0;
 }
 
 static int launch_conv(const float* x, const float* wp, const float* bias, float* y, int B, int Cin, int Cout,
                        int H, int W, int ks, hipStream_t stream, const char* what, int kind_tag, int S = 1, int Hi = 0,
-                       int Wi = 0, const ConvSrc* ms = nullptr, ConvGnOut* gn = nullptr) {
+                       int Wi = 0, const ConvSrc* ms = nullptr, ConvGnOut* gn = nullptr, const ConvRows* rows = nullptr) {
   ConvGeom g;
   std::array<int, 7> key;
-  if (conv_tune_key(what, kind_tag, B, Cin, Cout, H, W, ks, S, g, key)) return -1;
-  if (S == 1) { Hi = H; Wi = W; }
+  if (conv_tune_key(what, kind_tag, B, Cin, Cout, H, W, ks, S, g, key, rows)) return -1;
+  if (S == 1) { Hi = rows ? rows->Hi : H; Wi = W; }
+  // A row window is cut out of a full strip (the plain launch over max(H, Hi) rows): it splits K the way that launch does -- by its
+  // decision if it has one, else by its heuristic -- so every element it computes is the full strip's sum bit for bit, whatever
+  // kernel and tiles the window settles on; a decision under the window's own key (a pin, a database line) is taken as it stands.
+  int strip_split = 0;
+  std::array<int, 7> strip_key;
+  if (rows) {
+    int Hf = std::max(H, rows->Hi), Wf = W;
+    ConvGeom gf;
+    if (conv_tune_key(what, kind_tag, B, Cin, Cout, Hf, Wf, ks, S, gf, strip_key)) return -1;
+    strip_split = gf.splitK;
+    {
+      const bool tune = autotune_enabled();
+      std::lock_guard<std::mutex> lk(g_tune_mu);
+      if (const std::array<int, 2>* pd = tune_lookup(strip_key, tune)) {
+        const ConvDecision d = ConvDecision::decode(*pd);
+        ConvGeom t;
+        if ((d.variant >= 3) == conv_use_bx3(Cin, ks) && d.variant != 8 &&
+            conv_geom_fixed(B, Cin, Cout, Hf, Wf, ks, d.NT, d.split, t, d.variant, S, d.forceMT, d.tm))
+          strip_split = t.splitK;
+      }
+    }
+    ConvGeom t;
+    if (conv_geom_fixed(B, Cin, Cout, H, W, ks, g.NT, strip_split, t, g.DMA, S)) g = t;
+  }
   {
     // tuned / pinned configuration of this shape: the autotuner's result, a PNSFM_TUNE_DB line or pnsfm_tune_set (tests pin
     // configurations the un-tuned heuristics would not pick; that works in every build, the timing search needs a GPU)
@@ -1349,7 +1402,7 @@ static int launch_conv(const float* x, const float* wp, const float* bias, float
 #ifndef PNSFM_EMU
     // (a shape first seen inside a hipGraph capture cannot be timed -- timing synchronises: un-tuned default, not cached)
     if (!dec && tune && !stream_capturing(stream)) {
-      const ConvDecision best = conv_tune(g, key, bx3, x, wp, bias, y, B, Cin, Cout, H, W, ks, stream, what, kind_tag, S, Hi, Wi, ms);
+      const ConvDecision best = conv_tune(g, key, bx3, x, wp, bias, y, B, Cin, Cout, H, W, ks, stream, what, kind_tag, S, Hi, Wi, ms, rows, strip_split);
       dec = &g_tuned.emplace(key, best.encode()).first->second;
       tune_db_append(key, *dec);
     }
@@ -1369,9 +1422,9 @@ static int launch_conv(const float* x, const float* wp, const float* bias, float
 #endif
   const double flops = 2.0 * Cout * (double)Cin * ks * ks * (double)B * H * W;   // useful flops (output pixels)
   const int meta[9] = {B, Cin, Cout, H, W, ks, g.splitK, (int)(B * g.tiles_per_img * (g.MP / (32 * g.MT)) * g.splitK), g.DMA};
-  g_last_conv = {g.DMA, g.NT, g.MT, g.G, g.splitK, g.mode == 2 ? (g.TW == 16 ? 1 : 2) : 0, meta[7], (int)g.smem_bytes};
+  g_last_conv = {g.DMA, g.NT, g.MT, g.G, g.splitK, g.mode == 2 ? g.tm : 0, meta[7], (int)g.smem_bytes};
   prof_begin(0, flops, stream, meta);
-  const int rc = enqueue_conv(g, x, wp, bias, y, B, Cin, Cout, H, W, ks, stream, what, S, Hi, Wi, ms, gn);
+  const int rc = enqueue_conv(g, x, wp, bias, y, B, Cin, Cout, H, W, ks, stream, what, S, Hi, Wi, ms, gn, rows);
   prof_end(0, stream);
   return rc;
 }
@@ -1705,6 +1758,7 @@ struct WgradArgs {
   int PT, mode, tiles_x, tiles_per_img, PH, PW, NCI, total_tiles, tiles_per_split, splitP;
   int cstride;  // true H*W of dY (channel stride); H, W above are the TILING dims (k=1 flattens the image to 32-wide rows)
   int S, Hi, Wi; // stride and INPUT (x) size; dY / the pixel tiles live on the OUTPUT grid
+  int rows, yshift, shift_from_b;  // row window (ConvRows): x has Hi != H rows at stride 1; patch rows of samples >= shift_from_b start yshift lower
   int vec4, PTlog;
   float invPW, invPS;
   size_t zstride;  // pixel-split launch: floats between the partial [dw | dbias] slabs of consecutive splits (0: un-split)
@@ -1724,7 +1778,7 @@ __global__ void __launch_bounds__(256) conv2d_wgrad_kernel(WgradArgs a) {
   const int lane = tid & 63, wave = tid >> 6, half = lane >> 5, l32 = lane & 31;
   const int P = a.KS >> 1, KK = a.KS * a.KS;
   const int H = a.H, W = a.W, HW = a.cstride;
-  const int S = a.S, Hi = a.Hi, Wi = a.Wi, HWi = a.S == 1 ? a.cstride : a.Hi * a.Wi;
+  const int S = a.S, Hi = a.Hi, Wi = a.Wi, HWi = (a.S == 1 && !a.rows) ? a.cstride : a.Hi * a.Wi;
   const int N = a.Cin * KK;
 
   const int n0 = blockIdx.x * 128;
@@ -1767,6 +1821,7 @@ __global__ void __launch_bounds__(256) conv2d_wgrad_kernel(WgradArgs a) {
       py0 = r0 * S - P;
       px0 = -P;
     }
+    if (b >= a.shift_from_b) py0 += a.yshift;
     __syncthreads();  // previous tile fully consumed
     // ---- dY tile [BM][PT] (zero for channels / pixels outside the tensor); branch-free, batched loads
     const float* dyb = a.dy + (size_t)b * a.Cout * HW;
@@ -2065,6 +2120,7 @@ int pnsfm_conv2d_forward_cat(const float* x0, int C0, const float* x1, int C1, c
 struct WgradPlan {
   const float* x; const float* dy; float* dw; float* dbias;
   const ConvSrc* ms;               // several input tensors (null: one): only the split-bf16 kernels read them
+  const ConvRows* rows;            // row window (null: none): x has rows->Hi rows, dY H0; the generic, split-bf16 and nine-taps kernels take it
   hipStream_t s;
   int B, Cin, Cout, ks, S;
   int H0, W0;                      // true size of dY
@@ -2086,7 +2142,13 @@ static int wgrad_plan_init(WgradPlan& p, int H, int W, int Hi, int Wi) {
   if (S != 1 && S != 2) { set_error("backward_weight: unsupported stride %d", S); return -1; }
   const int KK = ks * ks, N = Cin * KK, HW = H * W;
   p.H0 = H; p.W0 = W;                                        // (the 1x1 path below re-tiles H, W)
-  p.v2_ok = S == 1 && wgrad2_supported(Cin, Cout, p.H0, p.W0, ks);
+  const ConvRows* rows = p.rows;
+  if (rows) {
+    if (S != 1 || ks < 3 || p.ms) { set_error("backward_weight: a row window needs a stride-1 3x3 / 5x5 / 7x7 layer with one input tensor"); return -1; }
+    if (rows->Hi <= 0 || rows->shift_from_b < 0) { set_error("backward_weight: bad row window"); return -1; }
+    Hi = rows->Hi; Wi = W;
+  }
+  p.v2_ok = S == 1 && !rows && wgrad2_supported(Cin, Cout, p.H0, p.W0, ks);
   WgradArgs& a = p.a;
   a.x = p.x; a.dy = p.dy; a.dw = p.dw; a.dbias = p.dbias;
   a.B = B; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W; a.KS = ks;
@@ -2098,6 +2160,7 @@ static int wgrad_plan_init(WgradPlan& p, int H, int W, int Hi, int Wi) {
     Hi = H; Wi = W;
   }
   a.Hi = Hi; a.Wi = Wi;
+  a.rows = rows ? 1 : 0; a.yshift = rows ? rows->yshift : 0; a.shift_from_b = rows ? rows->shift_from_b : 0;
   p.MT = conv_pick_MT(Cout);
   const int BM = 32 * p.MT;
   a.mode = (W % 32 == 0) ? 0 : 1;
@@ -2158,13 +2221,15 @@ static int wgrad_plan_init(WgradPlan& p, int H, int W, int Hi, int Wi) {
   const size_t kWgradScratchBudget = (size_t)128 << 20;
   p.max_split_f32 = (int)std::max<size_t>(1, kWgradScratchBudget / (((size_t)Cout * N + Cout) * sizeof(float)));
   p.stem_wg = !p.ms && wgrad_stem5_supported(B, Cin, Cout, p.H0, p.W0, ks, S);      // the 3-channel 5x5 stem: its own kernel
+  if (rows && p.stem_wg) { set_error("backward_weight: the stem kernel takes no row window"); return -1; }
   // split-bf16 kernel (conv2d_wgrad3.hip): part of the split arithmetic mode (pnsfm_set_conv_math), the default there.  A 1x1 layer
   // has no halo, so its map is handed over as 32-wide rows of the flattened image when that is exact (whole 16/32-column tiles
   // instead of ragged ones for W = 40, 80)
   const bool flat3 = ks == 1 && (p.H0 * p.W0) % 32 == 0;
   p.H3 = flat3 ? (p.H0 * p.W0) / 32 : p.H0;
   p.W3 = flat3 ? 32 : p.W0;
-  p.v3_ok = S == 1 && conv_math() == 1 && wgrad3_supported(Cin, Cout, p.H3, p.W3, ks) && wgrad3_fits(B, Cin, Cout, p.H3, p.W3);
+  p.v3_ok = S == 1 && conv_math() == 1 && wgrad3_supported(Cin, Cout, p.H3, p.W3, ks) &&
+            wgrad3_fits(B, Cin, Cout, rows ? std::max(p.H3, rows->Hi) : p.H3, p.W3);
   // nine-taps kernel (conv2d_wgrad4.hip): 3x3 only; chosen by the autotuner / a pinned decision (kernel 3)
   p.v4_ok = p.v3_ok && ks == 3 && wgrad4_supported(Cin, Cout, p.H0, p.W0, ks);
   if (p.ms && !p.v3_ok) { set_error("backward_weight: several input tensors need the split-bf16 weight-gradient kernel"); return -1; }
@@ -2241,8 +2306,8 @@ static int enqueue_wgrad_generic(const WgradPlan& p, int split) {
 static int wgrad_enqueue(const WgradPlan& p) {
   const WgradDecision& d = p.run;
   switch (d.kernel) {
-    case 3: return enqueue_wgrad4(p.x, p.dy, p.dw, p.dbias, p.B, p.Cin, p.Cout, p.H0, p.W0, d.split, d.cfg4(), p.s, p.ms);
-    case 2: return enqueue_wgrad3(p.x, p.dy, p.dw, p.dbias, p.B, p.Cin, p.Cout, p.H3, p.W3, p.ks, d.split, d.NT, d.wm, p.s, p.ms);
+    case 3: return enqueue_wgrad4(p.x, p.dy, p.dw, p.dbias, p.B, p.Cin, p.Cout, p.H0, p.W0, d.split, d.cfg4(), p.s, p.ms, p.rows);
+    case 2: return enqueue_wgrad3(p.x, p.dy, p.dw, p.dbias, p.B, p.Cin, p.Cout, p.H3, p.W3, p.ks, d.split, d.NT, d.wm, p.s, p.ms, p.rows);
     case 1: return enqueue_wgrad2(p.x, p.dy, p.dw, p.dbias, p.B, p.Cin, p.Cout, p.H0, p.W0, p.ks, d.split, p.s);
     default: return enqueue_wgrad_generic(p, d.split);
   }
@@ -2307,11 +2372,12 @@ static WgradDecision wgrad_tune(const WgradPlan& p, const std::array<int, 7>& ke
         });
   }
   if (p.v4_ok) {     // nine-taps kernel: ci tiles per workgroup x tile width x pixel splits around two workgroups per CU
+    const int H4 = p.rows ? p.rows->Hi : H0;      // (a row window's tiles walk the full strip's grid: conv2d_wgrad4.hip)
     for (int WCI = 1; WCI <= 2; ++WCI)
       for (int tgi = 0; tgi < (W0 > 24 ? 2 : 1); ++tgi) {
-        const int TG = W0 > 24 ? 4 + tgi : 3, TR = TG == 3 ? wgrad4_TR(H0, 0) : 4;
+        const int TG = W0 > 24 ? 4 + tgi : 3, TR = TG == 3 ? wgrad4_TR(H4, 0) : 4;
         if (W0 > 24 && round_up(W0, 8 * TG) > round_up(W0, 8 * (9 - TG)) + 8) continue;      // clearly the more wasteful width
-        for_split_candidates(wgrad4_total_tiles(B, H0, W0, TG, TR), wgrad4_base_blocks(Cin, Cout, WCI), 200, 16L * 256, [&](int split) {
+        for_split_candidates(wgrad4_total_tiles(B, H4, W0, TG, TR), wgrad4_base_blocks(Cin, Cout, WCI), 200, 16L * 256, [&](int split) {
           time_candidate({3, split, 1, 0, WCI, TG, TR});
           return true;
         });
@@ -2322,16 +2388,17 @@ static WgradDecision wgrad_tune(const WgradPlan& p, const std::array<int, 7>& ke
 #endif
 
 // The key of a weight-gradient plan's tuning decision (wgrad_impl looks it up, pnsfm_tune_key reports it): + 100 where the split-bf16
-// kernel takes the shape under the arithmetic mode in force, + 1000 for several input tensors; H*W of dY and the width the generic
-// kernel tiles (32 for a stride-1 1x1 layer, wgrad_plan_init) in place of H and W.
+// kernel takes the shape under the arithmetic mode in force, + 1000 for several input tensors, + kRowsKey * Hi for a row window; H*W of
+// dY and the width the generic kernel tiles (32 for a stride-1 1x1 layer, wgrad_plan_init) in place of H and W.
 static std::array<int, 7> wgrad_tune_key(const WgradPlan& p) {
-  return {2 + 10 * p.S + (p.v3_ok ? 100 : 0) + (p.ms ? 1000 : 0), p.B, p.Cin, p.Cout, p.a.cstride, p.a.W, p.ks};
+  return {2 + 10 * p.S + (p.v3_ok ? 100 : 0) + (p.ms ? 1000 : 0) + (p.rows ? kRowsKey * p.rows->Hi : 0), p.B, p.Cin, p.Cout, p.a.cstride,
+          p.a.W, p.ks};
 }
 
 static int wgrad_impl(const float* x, const float* dy, float* dw, float* dbias, int B, int Cin, int Cout, int H, int W,
-                      int ks, int S, int Hi, int Wi, void* stream, const ConvSrc* ms = nullptr) {
+                      int ks, int S, int Hi, int Wi, void* stream, const ConvSrc* ms = nullptr, const ConvRows* rows = nullptr) {
   WgradPlan p;
-  p.x = x; p.dy = dy; p.dw = dw; p.dbias = dbias; p.ms = ms; p.s = (hipStream_t)stream;
+  p.x = x; p.dy = dy; p.dw = dw; p.dbias = dbias; p.ms = ms; p.rows = rows; p.s = (hipStream_t)stream;
   p.B = B; p.Cin = Cin; p.Cout = Cout; p.ks = ks; p.S = S;
   if (wgrad_plan_init(p, H, W, Hi, Wi)) return -1;
   p.run = wgrad_default(p);
@@ -2342,6 +2409,20 @@ static int wgrad_impl(const float* x, const float* dy, float* dw, float* dbias, 
     const bool tune = autotune_enabled();
     std::lock_guard<std::mutex> lk(g_tune_mu);
     const std::array<int, 2>* dec = tune_lookup(key, tune);
+    // A row window without a decision of its own runs the decision of the full strip it is cut from (dY of rows->Hi rows, all but H of
+    // them zero): the same kernel, tiles and pixel split meet the non-zero rows in the same order, so the gradient is the full strip's
+    // bit for bit (the skipped k-steps and rows only ever added zeros).
+    std::array<int, 2> strip_dec;
+    if (!dec && p.rows) {
+      WgradPlan q = {};
+      q.B = p.B; q.Cin = p.Cin; q.Cout = p.Cout; q.ks = p.ks; q.S = 1;
+      if (!wgrad_plan_init(q, p.rows->Hi, p.W0, p.rows->Hi, p.W0)) {
+        if (const std::array<int, 2>* pd = tune_lookup(wgrad_tune_key(q), tune)) {
+          strip_dec = *pd;
+          dec = &strip_dec;
+        }
+      }
+    }
 #ifndef PNSFM_EMU
     // (first seen inside a hipGraph capture: keep the analytic split -- timing would synchronise)
     if (!dec && tune && !stream_capturing(p.s)) {
@@ -2392,6 +2473,34 @@ int pnsfm_conv2d_backward_weight_strided(const float* x, const float* dy, float*
   return wgrad_impl(x, dy, dw, dbias, B, Cin, Cout, Ho, Wo, ks, stride, Hin, Win, stream);
 }
 
+// ---- row windows (ConvRows, pnsfm_common.h): the stride-1 convolution of a map of Hi rows on an output grid of H rows
+static bool conv_rows_ok(const char* what, int B, int H, int Hi, int shift_from_b) {
+  if (H <= 0 || Hi <= 0 || shift_from_b < 0 || shift_from_b > B) { set_error("%s: bad row window (H=%d, Hi=%d, shift_from_b=%d)", what, H, Hi, shift_from_b); return false; }
+  return true;
+}
+
+int pnsfm_conv2d_forward_rows(const float* x, const float* wp_fwd, const float* bias, float* y, int B, int Cin, int Cout, int H,
+                              int Hi, int W, int ks, int yshift, int shift_from_b, void* stream) {
+  if (!conv_rows_ok("conv2d_forward_rows", B, H, Hi, shift_from_b)) return -1;
+  const ConvRows rows = {Hi, yshift, shift_from_b};
+  return launch_conv(x, wp_fwd, bias, y, B, Cin, Cout, H, W, ks, (hipStream_t)stream, "conv2d_forward_rows", 0, 1, 0, 0, nullptr, nullptr, &rows);
+}
+
+int pnsfm_conv2d_backward_data_rows(const float* dy, const float* wp_bwd, float* dx, int B, int Cin, int Cout, int H, int Hi, int W,
+                                    int ks, int yshift, int shift_from_b, void* stream) {
+  if (!conv_rows_ok("conv2d_backward_data_rows", B, H, Hi, shift_from_b)) return -1;
+  const ConvRows rows = {Hi, yshift, shift_from_b};
+  return launch_conv(dy, wp_bwd, nullptr, dx, B, Cout, Cin, H, W, ks, (hipStream_t)stream, "conv2d_backward_data_rows", 1, 1, 0, 0, nullptr, nullptr,
+                     &rows);
+}
+
+int pnsfm_conv2d_backward_weight_rows(const float* x, const float* dy, float* dw, float* dbias, int B, int Cin, int Cout, int H,
+                                      int Hi, int W, int ks, int yshift, int shift_from_b, void* stream) {
+  if (!conv_rows_ok("conv2d_backward_weight_rows", B, H, Hi, shift_from_b)) return -1;
+  const ConvRows rows = {Hi, yshift, shift_from_b};
+  return wgrad_impl(x, dy, dw, dbias, B, Cin, Cout, H, W, ks, 1, Hi, W, stream, nullptr, &rows);
+}
+
 int pnsfm_set_autotune(int on) {
   g_autotune = on ? 1 : 0;
   return 0;
@@ -2420,6 +2529,26 @@ int pnsfm_tune_key(int kind, int B, int Cin, int Cout, int H, int W, int ks, int
     p.ms = nsrc > 1 ? &ms : nullptr;
     p.B = B; p.Cin = Cin; p.Cout = Cout; p.ks = ks; p.S = stride;
     if (wgrad_plan_init(p, H, W, H * stride, W * stride)) return -1;
+    key = wgrad_tune_key(p);
+  }
+  for (int i = 0; i < 7; ++i) key7[i] = key[i];
+  return 0;
+}
+
+int pnsfm_tune_key_rows(int kind, int B, int Cin, int Cout, int H, int Hi, int W, int ks, int* key7) {
+  if (!key7) { set_error("tune_key_rows: null key"); return -1; }
+  if (kind < 0 || kind > 2) { set_error("tune_key_rows: no launch of kind %d", kind); return -1; }
+  const ConvRows rows = {Hi, 0, 0};
+  std::array<int, 7> key;
+  if (kind < 2) {
+    ConvGeom g;
+    if (conv_tune_key("tune_key_rows", kind, B, Cin, Cout, H, W, ks, 1, g, key, &rows)) return -1;
+  } else {
+    if (B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) { set_error("tune_key_rows: bad shape"); return -1; }
+    WgradPlan p = {};
+    p.rows = &rows;
+    p.B = B; p.Cin = Cin; p.Cout = Cout; p.ks = ks; p.S = 1;
+    if (wgrad_plan_init(p, H, W, Hi, W)) return -1;
     key = wgrad_tune_key(p);
   }
   for (int i = 0; i < 7; ++i) key7[i] = key[i];

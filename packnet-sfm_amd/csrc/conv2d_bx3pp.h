@@ -123,6 +123,7 @@ __global__ void __launch_bounds__(512) conv2d_bx3pp_kernel(ConvArgs a) {
       boff[nt] = ((yy - r0) * a.PW + ox[nt]) * S;
     }
   }
+  if (b >= a.shift_from_b) py0 += a.yshift;      // row window (ConvRows): 0 for every other launch
 
   f32x16 acc[MT][NT];
 #pragma unroll

@@ -74,6 +74,7 @@ __global__ void __launch_bounds__(256, OCC) conv2d_wgrad3_kernel(Wgrad3Args a) {
   const int lane = tid & 63, wave = PNSFM_UNIFORM(tid >> 6), half = lane >> 5, l32 = lane & 31;
   const int wm = wave % WM, wk = wave / WM;
   const int H = a.H, W = a.W, HW = H * W;
+  const int Hx = a.Hx, HWx = Hx * W;      // x: [B][Cin][Hx][W] (Hx = H unless the launch is a row window)
   // logical block ((ci tile, kernel row), co group, pixel split): first index fastest -- the workgroups of one pixel split read the
   // same dY and X -- and a contiguous range of that order per XCD (pnsfm_common.h)
   const unsigned Lb = a.g.bmap == 2 ? pnsfm_xcd_logical_block(blockIdx.x, gridDim.x) : blockIdx.x;
@@ -123,7 +124,7 @@ __global__ void __launch_bounds__(256, OCC) conv2d_wgrad3_kernel(Wgrad3Args a) {
     if (ci0 < a.C01) { xs = a.x1; Cs = a.C01 - a.C0; lci0 = ci0 - a.C0; }
     else { xs = a.x2; Cs = a.Cin - a.C01; lci0 = ci0 - a.C01; }
   }
-  const pnsfm_buf xbuf = pnsfm_make_buf(xs, (unsigned)((size_t)a.B * Cs * HW * 4));
+  const pnsfm_buf xbuf = pnsfm_make_buf(xs, (unsigned)((size_t)a.B * Cs * HWx * 4));
   const pnsfm_buf dybuf = pnsfm_make_buf(a.dy, (unsigned)((size_t)a.B * a.Cout * HW * 4));
 
   // patch items of this thread: (channel, row, 8-column group); LDS slot and lane part of the global offset are fixed
@@ -137,15 +138,16 @@ __global__ void __launch_bounds__(256, OCC) conv2d_wgrad3_kernel(Wgrad3Args a) {
     it_lds[it] = (ci * CS + r * RS + 8 * g) * 2;
     it_ry[it] = r + ky - P;                       // image row = y0 + it_ry
     it_gx[it] = 8 * g - 8;                        // image column = x0 + it_gx
-    it_lane[it] = ((lci0 + ci) * HW + it_ry[it] * W + it_gx[it]) * 4;
+    it_lane[it] = ((lci0 + ci) * HWx + it_ry[it] * W + it_gx[it]) * 4;
   }
   float raw[PDX][NIT][8];
   auto load_patch = [&](float (&rw)[NIT][8], const Cur& c) {
-    const int sbase = (c.b * Cs * HW + c.y0 * W + c.x0) * 4;
+    const int xy0 = c.y0 + (c.b >= a.shift_from_b ? a.yshift : 0);      // (row window: first x row of the tile)
+    const int sbase = (c.b * Cs * HWx + xy0 * W + c.x0) * 4;
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
-      const int yy = c.y0 + it_ry[it], xx = c.x0 + it_gx[it];
-      const bool ok = yy >= 0 && yy < H && xx >= 0 && xx < W;
+      const int yy = xy0 + it_ry[it], xx = c.x0 + it_gx[it];
+      const bool ok = yy >= 0 && yy < Hx && xx >= 0 && xx < W;
       const unsigned off = ok ? (unsigned)(sbase + it_lane[it]) : PNSFM_DMA_INVALID;
       // MASKED (W % 8 == 4): the upper 4 pixels of the group may lie past the row end -- they get their own range check
       const unsigned off4 = (MASKED && xx + 4 >= W) ? PNSFM_DMA_INVALID : off + 16u;
@@ -314,7 +316,9 @@ __global__ void __launch_bounds__(256, OCC) conv2d_wgrad3_kernel(Wgrad3Args a) {
           }
           const int dt = (i + RD) / KPW, ni = (i + RD) % KPW;       // dt <= 2
           if (t + dt < t_end && !(abl & 32)) load_a(araw[slot], cur[dt], wk + WK * ni);
-          kstep(A, wk + WK * i);
+          // (a k-step whose tile row lies past the map holds zeros of dY only: skipped -- wave-uniform.  The 4-row tiles of a map of
+          // one or two rows, the frame rows of the packing block's border strips, would spend most of their MFMAs there)
+          if (cur[0].y0 + (wk + WK * i) / SEG < H) kstep(A, wk + WK * i);
         }
         cur[0] = cur[1]; cur[1] = cur[2]; advance(cur[2]);
       }
@@ -501,7 +505,7 @@ static int launch_wgrad3(const Wgrad3Args& a, dim3 grid, hipStream_t s) {
 }
 
 int enqueue_wgrad3(const float* x, const float* dy, float* dw, float* dbias, int B, int Cin, int Cout, int H, int W, int ks,
-                   int split, int NT, int WMwant, hipStream_t s, const ConvSrc* ms) {
+                   int split, int NT, int WMwant, hipStream_t s, const ConvSrc* ms, const ConvRows* rows) {
   if (!wgrad3_supported(Cin, Cout, H, W, ks)) { set_error("conv2d_backward_weight (split-bf16): unsupported shape"); return -1; }
   if (NT != 2 || !wgrad3_nt2_ok(Cin, ks)) NT = 1;
   if (ms && NT == 2 && !conv_src_aligned(*ms, Cin, 64)) NT = 1;     // a 64-channel tile would straddle two tensors
@@ -518,7 +522,7 @@ int enqueue_wgrad3(const float* x, const float* dy, float* dw, float* dbias, int
   const int co_groups = ceil_div(ceil_div(Cout, 32), WM);
   Wgrad3Args a;
   const int splitP = wgrad_bx3_begin(a, "split-bf16", x, dy, dw, dbias, B, Cin, Cout, H, W, ks, 4, tc, co_groups * WM * 32,
-                                     ci_tiles * 32 * NT, split, s, ms);
+                                     ci_tiles * 32 * NT, split, s, ms, rows);
   if (splitP < 0) return -1;
   a.g = {ci_tiles, ci_tiles * ks, co_groups, block_map_mode()};
   dim3 grid(ci_tiles * ks * co_groups * splitP);

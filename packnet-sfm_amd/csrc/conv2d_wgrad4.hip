@@ -68,6 +68,11 @@ __global__ void __launch_bounds__(256, 2) conv2d_wgrad4_kernel(Wgrad4Args a) {
   const int lane = tid & 63, wave = PNSFM_UNIFORM(tid >> 6), l16 = lane & 15, j = lane >> 4;
   const int wci = wave % WCI, wco = wave / WCI;
   const int H = a.H, W = a.W, HW = H * W;
+  // Row window (ConvRows): H stays the FULL strip -- x's rows and the grid the tiles walk -- and dY holds Hd of those rows: row y of the
+  // grid is dY row y - dsh (dsh = yshift for the samples >= shift_from_b), zero outside [0, Hd).  A k-step packs 4 pixel groups that may
+  // come from two tile rows, so only on the full strip's grid do the non-zero rows of dY keep the k slots, and the gradient the bits,
+  // of the full-strip launch; what the window saves is the loads of the zero rows and every k-step that holds nothing else.
+  const int Hd = a.Hx, HWd = Hd * W;
   // logical block (ci tile, co group, pixel split): ci tile fastest -- the workgroups of one pixel split read the same dY and X
   // -- and a contiguous range of that order per XCD (pnsfm_common.h)
   const unsigned Lb = a.g.bmap == 2 ? pnsfm_xcd_logical_block(blockIdx.x, gridDim.x) : blockIdx.x;
@@ -116,7 +121,7 @@ __global__ void __launch_bounds__(256, 2) conv2d_wgrad4_kernel(Wgrad4Args a) {
     else { xs = a.x2; Cs = a.Cin - a.C01; lci0 = ci0 - a.C01; }
   }
   const pnsfm_buf xbuf = pnsfm_make_buf(xs, (unsigned)((size_t)a.B * Cs * HW * 4));
-  const pnsfm_buf dybuf = pnsfm_make_buf(a.dy, (unsigned)((size_t)a.B * a.Cout * HW * 4));
+  const pnsfm_buf dybuf = pnsfm_make_buf(a.dy, (unsigned)((size_t)a.B * a.Cout * HWd * 4));
 
   // patch items of this thread: (channel, row, 8-column group); LDS slot and lane part of the global offset are fixed
   int it_lds[NIT], it_ry[NIT], it_gx[NIT], it_lane[NIT];
@@ -171,13 +176,13 @@ __global__ void __launch_bounds__(256, 2) conv2d_wgrad4_kernel(Wgrad4Args a) {
   }
   // A operand: dY[co0 + 16 s + l16][8 pixels of the lane's group] straight from global memory
   float araw[RD][2][8];
-  const int a_lane = (co0 + l16) * HW * 4;
+  const int a_lane = (co0 + l16) * HWd * 4;
   auto load_a = [&](float (&araw)[2][8], const Cur& c, int q) {
-    const int yy = c.y0 + a_row[q], xx = c.x0 + a_col[q];
-    const bool ok = yy < H && xx < W;
+    const int yy = c.y0 + a_row[q] - (c.b >= a.shift_from_b ? a.yshift : 0), xx = c.x0 + a_col[q];
+    const bool ok = yy >= 0 && yy < Hd && xx < W;
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      const unsigned off = ok ? (unsigned)(a_lane + s * 16 * HW * 4 + (c.b * a.Cout * HW + yy * W + xx) * 4) : PNSFM_DMA_INVALID;
+      const unsigned off = ok ? (unsigned)(a_lane + s * 16 * HWd * 4 + (c.b * a.Cout * HWd + yy * W + xx) * 4) : PNSFM_DMA_INVALID;
       const unsigned off4 = (MASKED && xx + 4 >= W) ? PNSFM_DMA_INVALID : off + 16u;
 #pragma unroll
       for (int u = 0; u < 8; ++u) araw[s][u] = pnsfm_buf_load(dybuf, u < 4 ? off + 4u * u : off4 + 4u * (u - 4), 0);
@@ -255,7 +260,12 @@ __global__ void __launch_bounds__(256, 2) conv2d_wgrad4_kernel(Wgrad4Args a) {
       }
       const int dt = (q + RD) / KSTEPS, nq = (q + RD) % KSTEPS;      // dt <= 1 (RD <= KSTEPS)
       if (t + dt < t_end && !(abl & 32)) load_a(araw[slot], cur[dt], nq);
-      kstep(A, q);
+      // (k-step q holds tile rows (4q) / TG .. (4q + 3) / TG: skipped when none of them is a row of dY -- wave-uniform)
+      {
+        const int d0 = cur[0].y0 - (cur[0].b >= a.shift_from_b ? a.yshift : 0);
+        const int gl = 4 * q + 3 < G - 1 ? 4 * q + 3 : G - 1;
+        if (d0 + gl / TG >= 0 && d0 + (4 * q) / TG < Hd) kstep(A, q);
+      }
     }
     cur[0] = cur[1]; cur[1] = cur[2]; advance(cur[2]);
   }
@@ -329,17 +339,20 @@ static int launch_wgrad4(const Wgrad4Args& a, dim3 grid, hipStream_t s) {
 
 // cfg: WCI (1 | 2) | TG << 4 | TR << 8 (0: library choice)
 int enqueue_wgrad4(const float* x, const float* dy, float* dw, float* dbias, int B, int Cin, int Cout, int H, int W, int split,
-                   int cfg, hipStream_t s, const ConvSrc* ms) {
+                   int cfg, hipStream_t s, const ConvSrc* ms, const ConvRows* rows) {
   if (!wgrad4_supported(Cin, Cout, H, W, 3)) { set_error("conv2d_backward_weight (nine taps): unsupported shape"); return -1; }
   const int WCI = (cfg & 15) == 1 ? 1 : 2;
   const int TG = wgrad4_TG(W, (cfg >> 4) & 15);
+  const int Hd = H;
+  if (rows) H = rows->Hi;      // the tiles walk the full strip's grid (kernel: Row window)
   const int TR = TG == 3 ? wgrad4_TR(H, (cfg >> 8) & 15) : 4;      // 6-row tiles exist for the 3-group (W <= 24) tiles only
   const bool masked = W % 8 != 0;
   const int ci_tiles = ceil_div(Cin, 16 * WCI), co_groups = ceil_div(Cout, 32 * (4 / WCI));
   Wgrad4Args a;
   const int splitP = wgrad_bx3_begin(a, "nine taps", x, dy, dw, dbias, B, Cin, Cout, H, W, 3, TR, 8 * TG, co_groups * 32 * (4 / WCI),
-                                     ci_tiles * 16 * WCI, split, s, ms);
+                                     ci_tiles * 16 * WCI, split, s, ms, rows);
   if (splitP < 0) return -1;
+  a.Hx = Hd;      // (this kernel's reading of the field: the rows of dY)
   a.g = {ci_tiles, co_groups, block_map_mode()};
   dim3 grid(ci_tiles * co_groups * splitP);
   int rc = 0;

@@ -33,6 +33,7 @@ struct WgradBx3Args {
   int COP, CIP;      // padded channel extents of the workspace (whole workgroup tiles)
   int B, Cin, Cout, H, W;
   int tiles_x, tiles_per_img, total_tiles, tiles_per_split;
+  int Hx, yshift, shift_from_b;      // row window (ConvRows): x has Hx rows (H: none); the x rows of samples >= shift_from_b start yshift lower
   LAUNCH g;
 };
 
@@ -55,8 +56,13 @@ int launch_wgrad3_reduce(const float* ws, const float* ws_bias, float* dw, float
 template <class Args>
 static inline int wgrad_bx3_begin(Args& a, const char* what, const float* x, const float* dy, float* dw, float* dbias, int B, int Cin,
                                   int Cout, int H, int W, int ks, int tr, int tc, int COP, int CIP, int split, hipStream_t s,
-                                  const ConvSrc* ms) {
-  if (!wgrad3_fits(B, Cin, Cout, H, W)) {
+                                  const ConvSrc* ms, const ConvRows* rows) {
+  if (rows && (ms || ks < 3 || rows->Hi <= 0)) {
+    set_error("conv2d_backward_weight (%s): a row window needs a 3x3 / 5x5 / 7x7 layer with one input tensor", what);
+    return -1;
+  }
+  a.Hx = rows ? rows->Hi : H; a.yshift = rows ? rows->yshift : 0; a.shift_from_b = rows ? rows->shift_from_b : 0;
+  if (!wgrad3_fits(B, Cin, Cout, H > a.Hx ? H : a.Hx, W)) {
     set_error("conv2d_backward_weight (%s): tensor too large for 32-bit buffer offsets", what);
     return -1;
   }

@@ -284,6 +284,13 @@ static inline bool conv_src_aligned(const ConvSrc& ms, int Cin, int granule) {
   return ms.C0 % granule == 0 && (ms.C0 + ms.C1 == Cin || (ms.C0 + ms.C1) % granule == 0);
 }
 
+// Row window of a stride-1 convolution (the border strips of the collapsed packing block): the map the kernel READS has Hi rows where
+// the map it tiles has H, and the patch rows of samples b >= shift_from_b start `yshift` rows further down.  Rows outside [0, Hi) read
+// as zero, as the padding does.  With H = r, Hi = 2r: yshift 0 is the top frame (zero above), yshift r the bottom frame (zero below).
+struct ConvRows {
+  int Hi, yshift, shift_from_b;
+};
+
 // --- conv2d implicit-GEMM geometry (shared by forward / backward-data / packers) -----------
 // GEMM view: M = output channels, N = output pixels, K = (tap, input channel).
 struct ConvGeom {
@@ -292,6 +299,7 @@ struct ConvGeom {
   int CI;             // input channels staged per K-chunk (even, <= 16)
   int mode;           // 0: 2-D pixel tile (4*NT rows x 32 cols), 1: linear run of 128*NT pixels, 2: TW x TH rectangle (split-bf16 kernels)
   int TW, TH;         // mode 2: tile width / height in output pixels (TW * TH <= 128 * NT)
+  int tm;             // the tile mode asked for (0 classic, 1 16-wide rectangles, 2 row bands, 3 short-map rectangles; 1..3 are mode 2)
   int tiles_x, tiles_per_img;
   int PH, PW;         // staged input patch (rows, cols) incl. halo
   int KP, MP;         // padded K-channels / M-channels of the packed weight
@@ -334,7 +342,7 @@ int wgrad3_total_tiles(int B, int H, int W);
 int wgrad3_WM(int Cout, int want);          // co tiles per workgroup (want: 0 = the most the layer fills, or 1 / 2 / 4)
 int wgrad3_base_blocks(int Cin, int Cout, int ks, int NT, int WM);
 int enqueue_wgrad3(const float* x, const float* dy, float* dw, float* dbias, int B, int Cin, int Cout, int H, int W, int ks,
-                   int split, int NT, int WM, hipStream_t stream, const ConvSrc* ms = nullptr);
+                   int split, int NT, int WM, hipStream_t stream, const ConvSrc* ms = nullptr, const ConvRows* rows = nullptr);
 
 // nine-taps-per-workgroup 3x3 weight gradient on the 16x16x32 MFMA (conv2d_wgrad4.hip).  cfg = WCI (ci tiles of 16 channels per
 // workgroup: 1 | 2) | TG << 4 (tile width in 8-pixel groups, 0 = library choice) | TR << 8 (tile rows, 0 = library choice)
@@ -344,7 +352,7 @@ int wgrad4_TR(int H, int want);
 int wgrad4_total_tiles(int B, int H, int W, int TG, int TR);
 int wgrad4_base_blocks(int Cin, int Cout, int WCI);
 int enqueue_wgrad4(const float* x, const float* dy, float* dw, float* dbias, int B, int Cin, int Cout, int H, int W, int split,
-                   int cfg, hipStream_t stream, const ConvSrc* ms = nullptr);
+                   int cfg, hipStream_t stream, const ConvSrc* ms = nullptr, const ConvRows* rows = nullptr);
 
 // more than 64 KB of dynamic LDS needs hipFuncSetAttribute once per kernel AND device: `mask` (one static per kernel
 // instantiation) remembers the devices already done (api.hip).  0 on success.

@@ -40,6 +40,9 @@ SIGNATURES = {
     "pnsfm_conv2d_cat_wgrad_supported": (_i, [_i, _i, _i, _i, _i, _i, _i, _i]),
     "pnsfm_conv2d_forward_strided": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "pnsfm_conv2d_backward_weight_strided": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "pnsfm_conv2d_forward_rows": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "pnsfm_conv2d_backward_data_rows": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "pnsfm_conv2d_backward_weight_rows": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "pnsfm_groupnorm_ws_doubles": (_sz, [_i, _i, _i]),
     "pnsfm_groupnorm_act_forward": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _i, _p]),
     "pnsfm_groupnorm_act_backward": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
@@ -133,6 +136,7 @@ SIGNATURES = {
     "pnsfm_set_wgrad_variant": (_i, [_i]),
     "pnsfm_tune_set": (_i, [ctypes.POINTER(ctypes.c_int), _i, _i]),
     "pnsfm_tune_key": (_i, [_i] * 9 + [ctypes.POINTER(ctypes.c_int)]),
+    "pnsfm_tune_key_rows": (_i, [_i] * 8 + [ctypes.POINTER(ctypes.c_int)]),
     "pnsfm_conv2d_last_config": (_i, [ctypes.POINTER(ctypes.c_int)]),
     "pnsfm_calib_mfma": (_i, [_p, _i, _i, _p]),
     "pnsfm_calib_copy": (_i, [_p, _p, _sz, _p]),

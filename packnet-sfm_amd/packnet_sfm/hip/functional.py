@@ -675,6 +675,52 @@ def conv2d(x, weight, bias, cache):
     return Conv2dFn.apply(weight, bias, cache, torch.is_grad_enabled(), False, False, x)
 
 
+class Conv2dRowsFn(Function):
+    """The stride-1 convolution of the collapsed packing block's batched border strips, computed for the frame rows only.
+    x: [2B, Cin, 2r, w], r = k // 2 -- the leading half the strips whose frame rows are their FIRST r rows (top / left), the trailing half
+    those whose frame rows are their LAST r (bottom / right).  y: [2B, Cout, r, w] = the rows conv2d(x) would hold there (leading half:
+    rows 0..r-1, trailing half: rows r..2r-1), element for element the same sums: the row-window kernels of include/pnsfm.h.  Backward:
+    dx [2B, Cin, 2r, w] from the r rows of dy (no zero rows are staged), the weight gradient over dy's r rows, on the side stream like
+    every other convolution's."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, cache, r, recording=True):
+        x = x.contiguous()
+        need_dx = ctx.needs_input_grad[0]
+        wp_fwd, wp_bwd = cache.get(weight, need_dx)
+        Cout, Cin, ks, _ = weight.shape
+        if ks // 2 != r or x.shape[1] != Cin:
+            raise RuntimeError("conv2d_rows: weight %s does not fit r = %d, input %s" % (tuple(weight.shape), r, tuple(x.shape)))
+        y = ops.conv2d_forward_rows(x, wp_fwd, bias.detach() if bias is not None else None, Cout, ks, r)
+        ctx.save_for_backward(x, wp_bwd if wp_bwd is not None else x.new_empty(0))
+        ctx.meta = (Cin, Cout, ks, bias is not None, r)
+        ctx.params = (weight, bias)
+        _WgradStream.note_use(recording, weight, bias)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        x, wp_bwd = ctx.saved_tensors
+        Cin, Cout, ks, has_bias, r = ctx.meta
+        dy = dy.contiguous()
+        want_w = bool(ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]))
+        detached = _WgradStream.side_ok(*ctx.params)
+        sw, sb = _slots_for(ctx.params[0], ctx.params[1], detached and ctx.needs_input_grad[1])
+        dx, dw, db = _WgradStream.run_beside(
+            dy, want_w, detached, lambda: ops.conv2d_backward_weight_rows(x, dy, ks, r, want_bias=has_bias, dw_out=sw, db_out=sb),
+            (lambda: ops.conv2d_backward_data_rows(dy, wp_bwd, Cin, ks, r)) if ctx.needs_input_grad[0] else None, (x, dy))
+        return dx, dw, db, None, None, None
+
+
+def conv2d_rows(x, weight, bias, cache, r):
+    """Frame rows of conv2d over the batched border strips (Conv2dRowsFn): x [2B, Cin, 2r, w] -> [2B, Cout, r, w]."""
+    if x.dtype == torch.float16:
+        raise NotImplementedError("conv2d_rows: the fp16 forward keeps the full-strip form (conv2d + strip rows dropped at the paste)")
+    _h16_input(x, weight)
+    return Conv2dRowsFn.apply(x, weight, bias, cache, r, torch.is_grad_enabled())
+
+
 # Round 5: gradient taps.  A tensor read by a convolution AND by something else (the encoder feature that is also a decoder skip input;
 # the ResidualConv input read by conv1 and by the 1x1 shortcut; the decoder feature read by the next unpack block and by the InvDepth
 # head) receives two gradients, which autograd adds with an elementwise kernel: 3 passes over the tensor and a launch, 18 times per
@@ -1094,15 +1140,18 @@ def _strip_select_fwd(z, B, r, dim, run):
     return out
 
 
-def _border_paste_fwd(y, o_tb, o_lr, r, lr_t, run):
-    """Pastes in place into y; o_tb / o_lr contiguous.  Returns y."""
+def _border_paste_fwd(y, o_tb, o_lr, r, lr_t, run, rows=False):
+    """Pastes in place into y; o_tb / o_lr contiguous.  Returns y.  rows: the strip results hold their frame rows only (conv2d_rows):
+    o_tb [2B, C, r, w] and, transposed, o_lr [2B, C, r, h]; untransposed column strips keep their 2r columns."""
     B, h, w = y.shape[0], y.shape[2], y.shape[3]
-    if lr_t:                     # [2B, C, 2r, h] holds the column strips transposed
+    if lr_t:                     # [2B, C, 2r | r, h] holds the column strips transposed
         o_lr = o_lr.transpose(2, 3)
+    t0 = 0 if rows else r                      # first frame row of the trailing half of o_tb
+    c0 = 0 if (rows and lr_t) else r           # ... frame column of o_lr
     run([_R(ops.REGION_COPY, y[:, :, r:h - r, :r], o_lr[:B, :, r:h - r, :r]),
-         _R(ops.REGION_COPY, y[:, :, r:h - r, w - r:], o_lr[B:, :, r:h - r, r:]),
+         _R(ops.REGION_COPY, y[:, :, r:h - r, w - r:], o_lr[B:, :, r:h - r, c0:]),
          _R(ops.REGION_COPY, y[:, :, :r], o_tb[:B, :, :r]),
-         _R(ops.REGION_COPY, y[:, :, h - r:], o_tb[B:, :, r:])])
+         _R(ops.REGION_COPY, y[:, :, h - r:], o_tb[B:, :, t0:])])
     return y
 
 
@@ -1188,14 +1237,17 @@ class PackBorderPasteFn(Function):
     """Collapsed packing block, output side: overwrite the r-pixel frame of the interior result y (in place: y is the
     interior conv's own output buffer) with the strip results o_tb [2B,C,2r,w] / o_lr [2B,C,h,2r] (only their outer r
     rows / columns are valid).  Replaces two torch.cat copies forward and a zero-fill + copy backward; one launch forward, one
-    backward (every element of d_tb, d_lr and dy has exactly one writer)."""
+    backward (every element of d_tb, d_lr and dy has exactly one writer).
+    rows: the strips were convolved for their frame rows only (conv2d_rows) -- o_tb [2B,C,r,w], o_lr transposed [2B,C,r,h]: their
+    gradients hold the frame rows and nothing else, so backward zero-fills no inner rows (only the corners of d_lr, which belong to
+    the row strips)."""
 
     @staticmethod
-    def forward(ctx, y, o_tb, o_lr, r, lr_t=False):
-        ctx.r, ctx.lr_t = r, lr_t
+    def forward(ctx, y, o_tb, o_lr, r, lr_t=False, rows=False):
+        ctx.r, ctx.lr_t, ctx.rows = r, lr_t, rows
         o_tb, o_lr = o_tb.contiguous(), o_lr.contiguous()
         s_lr = tuple(o_lr.shape)
-        _border_paste_fwd(y, o_tb, o_lr, r, lr_t, ops.region_ops)
+        _border_paste_fwd(y, o_tb, o_lr, r, lr_t, ops.region_ops, rows)
         ctx.mark_dirty(y)
         ctx.shapes = (tuple(o_tb.shape), s_lr)
         return y
@@ -1209,28 +1261,39 @@ class PackBorderPasteFn(Function):
         s_tb, s_lr = ctx.shapes
         d_tb, d_lr_st, dy = g.new_empty(s_tb), g.new_empty(s_lr), torch.empty_like(g)
         d_lr = d_lr_st.transpose(2, 3) if ctx.lr_t else d_lr_st
-        ops.region_ops([
-            # d_tb [2B,C,2r,w]: leading half rows 0..r-1 <- top frame, rows r.. zero; trailing half rows r.. <- bottom frame, rows ..r-1 zero
-            _R(ops.REGION_COPY, d_tb[:B, :, :r], g[:, :, :r]), _R(ops.REGION_ZERO, d_tb[:B, :, r:]),
-            _R(ops.REGION_COPY, d_tb[B:, :, r:], g[:, :, h - r:]), _R(ops.REGION_ZERO, d_tb[B:, :, :r]),
+        dy_ops = [
             # dy: the interior of g, frame zero (the frame's gradient belongs to the strips)
             _R(ops.REGION_COPY, dy[:, :, r:h - r, r:w - r], g[:, :, r:h - r, r:w - r]),
             _R(ops.REGION_ZERO, dy[:, :, :r]), _R(ops.REGION_ZERO, dy[:, :, h - r:]),
-            _R(ops.REGION_ZERO, dy[:, :, r:h - r, :r]), _R(ops.REGION_ZERO, dy[:, :, r:h - r, w - r:])])
+            _R(ops.REGION_ZERO, dy[:, :, r:h - r, :r]), _R(ops.REGION_ZERO, dy[:, :, r:h - r, w - r:])]
+        if ctx.rows:
+            lr_rows = ctx.lr_t        # (untransposed column strips keep 2r columns: their inner r are zero-filled as before)
+            lr_ops = [_R(ops.REGION_COPY, d_lr[:B, :, r:h - r, :r], g[:, :, r:h - r, :r]),
+                      _R(ops.REGION_COPY, d_lr[B:, :, r:h - r, (0 if lr_rows else r):], g[:, :, r:h - r, w - r:]),
+                      _R(ops.REGION_ZERO, d_lr[:, :, :r]), _R(ops.REGION_ZERO, d_lr[:, :, h - r:])]
+            if not lr_rows:
+                lr_ops += [_R(ops.REGION_ZERO, d_lr[:B, :, r:h - r, r:]), _R(ops.REGION_ZERO, d_lr[B:, :, r:h - r, :r])]
+            # d_tb [2B,C,r,w]: the frame rows of g; one launch covers d_tb, dy and d_lr (<= 12 windows, every element one writer)
+            ops.region_ops([_R(ops.REGION_COPY, d_tb[:B], g[:, :, :r]), _R(ops.REGION_COPY, d_tb[B:], g[:, :, h - r:])] + dy_ops + lr_ops)
+            return dy, d_tb, d_lr_st, None, None, None
+        ops.region_ops([
+            # d_tb [2B,C,2r,w]: leading half rows 0..r-1 <- top frame, rows r.. zero; trailing half rows r.. <- bottom frame, rows ..r-1 zero
+            _R(ops.REGION_COPY, d_tb[:B, :, :r], g[:, :, :r]), _R(ops.REGION_ZERO, d_tb[:B, :, r:]),
+            _R(ops.REGION_COPY, d_tb[B:, :, r:], g[:, :, h - r:]), _R(ops.REGION_ZERO, d_tb[B:, :, :r])] + dy_ops)
         ops.region_ops([
             # d_lr [2B,C,h,2r]: only rows r..h-r-1 of the outer r columns carry gradient (the corners went to the row strips)
             _R(ops.REGION_COPY, d_lr[:B, :, r:h - r, :r], g[:, :, r:h - r, :r]), _R(ops.REGION_ZERO, d_lr[:B, :, r:h - r, r:]),
             _R(ops.REGION_COPY, d_lr[B:, :, r:h - r, r:], g[:, :, r:h - r, w - r:]), _R(ops.REGION_ZERO, d_lr[B:, :, r:h - r, :r]),
             _R(ops.REGION_ZERO, d_lr[:, :, :r]), _R(ops.REGION_ZERO, d_lr[:, :, h - r:])])
-        return dy, d_tb, d_lr_st, None, None
+        return dy, d_tb, d_lr_st, None, None, None
 
 
-def pack_border_paste(y, o_tb, o_lr, r, lr_t=False):
+def pack_border_paste(y, o_tb, o_lr, r, lr_t=False, rows=False):
     if y.dtype == torch.float16:
         if torch.is_grad_enabled() and any(t.requires_grad for t in (y, o_tb, o_lr)):
             raise NotImplementedError(_H16_ONLY_FWD)      # (in place into y: the collapsed fp16 block runs it inside its forward-only node)
-        return _border_paste_fwd(y, o_tb.contiguous(), o_lr.contiguous(), r, lr_t, ops.region_ops_h16)
-    return PackBorderPasteFn.apply(y, o_tb, o_lr, r, lr_t)
+        return _border_paste_fwd(y, o_tb.contiguous(), o_lr.contiguous(), r, lr_t, ops.region_ops_h16, rows)
+    return PackBorderPasteFn.apply(y, o_tb, o_lr, r, lr_t, rows)
 
 
 class InvDepthActFn(Function):

@@ -285,6 +285,57 @@ def conv2d_backward_weight_strided(x, dy, ks, stride, want_bias=True, dw_out=Non
     return dw, db
 
 
+# Row windows (include/pnsfm.h "Row windows"): x [2B, Cin, 2r, W] holds the batched border strips of the collapsed packing block --
+# the leading half the strips whose frame rows are the FIRST r, the trailing half those whose frame rows are the LAST r; only the
+# frame rows are computed: y / dy are [2B, Cout, r, W].
+def _rows_shape(t, r, rows, what):
+    B2, C, H, W = t.shape
+    if r < 1 or H != rows or B2 % 2:
+        raise RuntimeError("%s: expected [2B, C, %d, W] for r = %d, got %s" % (what, rows, r, tuple(t.shape)))
+    return B2, C, W
+
+
+def conv2d_forward_rows(x, wp_fwd, bias, Cout, ks, r):
+    _chk(x, wp_fwd, bias); _f32(x, wp_fwd, bias)
+    B2, Cin, W = _rows_shape(x, r, 2 * r, "conv2d_forward_rows")
+    y = torch.empty((B2, Cout, r, W), dtype=torch.float32, device=x.device)
+    rc = _lib.get().pnsfm_conv2d_forward_rows(_ptr(x), _ptr(wp_fwd), _ptr(bias), _ptr(y), B2, Cin, Cout, r, 2 * r, W, ks, r, B2 // 2,
+                                              _stream(x))
+    _lib.check(rc, "conv2d_forward_rows")
+    return y
+
+
+def conv2d_backward_data_rows(dy, wp_bwd, Cin, ks, r):
+    """dx [2B, Cin, 2r, W] of conv2d_forward_rows from dy [2B, Cout, r, W]."""
+    _chk(dy, wp_bwd); _f32(dy, wp_bwd)
+    B2, Cout, W = _rows_shape(dy, r, r, "conv2d_backward_data_rows")
+    dx = torch.empty((B2, Cin, 2 * r, W), dtype=torch.float32, device=dy.device)
+    rc = _lib.get().pnsfm_conv2d_backward_data_rows(_ptr(dy), _ptr(wp_bwd), _ptr(dx), B2, Cin, Cout, 2 * r, r, W, ks, -r, B2 // 2,
+                                                    _stream(dy))
+    _lib.check(rc, "conv2d_backward_data_rows")
+    return dx
+
+
+def conv2d_backward_weight_rows(x, dy, ks, r, want_bias=True, dw_out=None, db_out=None):
+    """Weight (and bias) gradient of conv2d_forward_rows; dw_out / db_out: gradient slots, as conv2d_backward_weight."""
+    _chk(x, dy); _f32(x, dy)
+    B2, Cin, W = _rows_shape(x, r, 2 * r, "conv2d_backward_weight_rows")
+    if _rows_shape(dy, r, r, "conv2d_backward_weight_rows")[::2] != (B2, W):
+        raise RuntimeError("conv2d_backward_weight_rows: dy %s does not match x %s" % (tuple(dy.shape), tuple(x.shape)))
+    Cout = dy.shape[1]
+    if dw_out is not None:
+        _chk(dw_out, db_out); _f32(dw_out, db_out)
+        if tuple(dw_out.shape) != (Cout, Cin, ks, ks) or (want_bias and (db_out is None or db_out.numel() != Cout)):
+            raise RuntimeError("conv2d_backward_weight_rows: gradient slot has the wrong shape")
+        dw, db = dw_out.view(dw_out.shape), (db_out.view(db_out.shape) if want_bias else None)
+    else:
+        dw, db = _alloc_dw_db(Cout, Cin, ks, want_bias, x.device)
+    rc = _lib.get().pnsfm_conv2d_backward_weight_rows(_ptr(x), _ptr(dy), _ptr(dw), _ptr(db), B2, Cin, Cout, r, 2 * r, W, ks, r, B2 // 2,
+                                                      _stream(x))
+    _lib.check(rc, "conv2d_backward_weight_rows")
+    return dw, db
+
+
 # ------------------------------------------------------------------------------------------- groupnorm
 ACT_NONE, ACT_ELU, ACT_RELU = 0, 1, 2
 GN_MAX_SPLIT = 64     # PNSFM_GN_MAX_SPLIT in include/pnsfm.h

@@ -26,9 +26,17 @@ def key(kind, B, Cin, Cout, H, W, ks, stride=1, sources=1, lib=None):
     return tuple(out)
 
 
+def key_rows(kind, B, Cin, Cout, H, Hi, W, ks, lib=None):
+    """The key of a row-window launch (ops.conv2d_*_rows): B the whole batch of strips, H the rows the launch tiles (y / dx / dY),
+    Hi the rows of the map it reads (x / dY / x).  Differs from key() of the same shape in key[0] (+ 10000 * Hi)."""
+    out = (ctypes.c_int * 7)()
+    _lib.check((lib or _lib.get()).pnsfm_tune_key_rows(kind, B, Cin, Cout, H, Hi, W, ks, out), 'tune_key_rows')
+    return tuple(out)
+
+
 class ConvDecision(collections.namedtuple('ConvDecision', 'NT variant narrow_m tile_mode split')):
     """Forward / backward-data: NT 1 | 2 32-pixel tiles per wave; variant 0..8 the kernel; narrow_m 1: 32-row M tiles where 64 would
-    fit; tile_mode 0 | 1 | 2 classic tiles, 16-wide rectangles, row bands; split: K-split."""
+    fit; tile_mode 0 | 1 | 2 | 3 classic tiles, 16-wide rectangles, row bands, short-map rectangles (maps of < 4 rows); split: K-split."""
     __slots__ = ()
 
     def __new__(cls, NT=1, variant=0, narrow_m=0, tile_mode=0, split=1):
@@ -69,8 +77,14 @@ class WgradDecision(collections.namedtuple('WgradDecision', 'kernel split NT wm 
 
 
 def kind_fields(kind):
-    """key[0] of a database line -> (FORWARD | BACKWARD_DATA | WGRAD, stride, split-bf16 arithmetic, several input tensors)."""
-    return kind % 10, kind // 10 % 10, kind // 100 % 10 == 1, kind >= 1000
+    """key[0] of a database line -> (FORWARD | BACKWARD_DATA | WGRAD, stride, split-bf16 arithmetic, several input tensors).
+    (A row-window launch adds 10000 * Hi: rows_of.)"""
+    return kind % 10, kind // 10 % 10, kind // 100 % 10 == 1, kind // 1000 % 10 == 1
+
+
+def rows_of(kind):
+    """Rows of the map a row-window launch reads (key_rows), 0 for every other launch."""
+    return kind // 10000
 
 
 def decode(kind, v0, v1):

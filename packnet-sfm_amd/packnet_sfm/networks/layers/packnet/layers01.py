@@ -189,6 +189,12 @@ class PackLayerConv3d(nn.Module):
     # row strips' instead of on rows of 2 - 5 pixels (the weight gradient of those fell back to the generic f32 kernel: 28 - 83 TFLOP/s)
     # (+0.5 % images/s, weight-gradient frac 0.366 -> 0.380 same-box: profiles/r06_ab_transposed_column_strips.txt; False = the old form)
     lr_transposed = True
+    # the strip convolutions compute only the r = k//2 frame rows the paste keeps (HF.conv2d_rows: strips [2B, 32C, 2r, w] -> [2B, C, r, w])
+    # instead of all 2r rows of a same-size convolution -- half of the forward GEMM's pixels were dropped at the paste, and half of the
+    # weight gradient's pixels were rows of dy zero-filled a moment earlier.  Row strips always, column strips in their transposed
+    # form (lr_transposed); the fp16 forward keeps the full-strip form.  False = the full-strip form (the A/B switch and the reference
+    # of tests/test_conv_rows_*.py); figures: DESIGN.md
+    strip_frame_rows = True
 
     def __init__(self, in_channels, kernel_size, r=2, d=8):
         super().__init__()
@@ -261,17 +267,21 @@ class PackLayerConv3d(nn.Module):
         # are batched together); only rows/cols whose Conv3d neighbourhood lies inside the strip are kept.  The three
         # helper Functions do the strip gather / select / paste without full-size zero-fills and adds in backward.
         lr_t = bool(self.lr_transposed)
+        rows = bool(self.strip_frame_rows)
         P_main, tb, lr = HF.pack_border_split(P, S, lr_t)
         y = HF.conv2d(P_main, W_eff, bias_eff, self._eff_packed)
-        o_tb = base(HF.strip_select(HF.conv3d_1to8(tb, W3, b3), B, r, 2))        # [2B, C, 2r, w]
+        s_tb = HF.strip_select(HF.conv3d_1to8(tb, W3, b3), B, r, 2)              # [2B, 32C, 2r, w]
+        # [2B, C, r, w] (the frame rows only) or [2B, C, 2r, w]
+        o_tb = HF.conv2d_rows(s_tb, W2, b2, base._packed, r) if rows else base(s_tb)
         if lr_t:
-            # transposed space: strips [2B, C, S, h], Conv3d taps (dz, dx, dy), Conv2d taps (kx, ky); the result [2B, C, 2r, h] is pasted
+            # transposed space: strips [2B, C, S, h], Conv3d taps (dz, dx, dy), Conv2d taps (kx, ky); the result [2B, C, 2r | r, h] is pasted
             # through a transposed view (autograd carries the weight gradients back through the two transpose views)
-            z = HF.conv3d_1to8(lr, W3.transpose(3, 4), b3)
-            o_lr = HF.conv2d(HF.strip_select(z, B, r, 2), W2.transpose(2, 3), b2, self._lr_packed)
+            z = HF.strip_select(HF.conv3d_1to8(lr, W3.transpose(3, 4), b3), B, r, 2)
+            o_lr = (HF.conv2d_rows(z, W2.transpose(2, 3), b2, self._lr_packed, r) if rows else
+                    HF.conv2d(z, W2.transpose(2, 3), b2, self._lr_packed))
         else:
             o_lr = base(HF.strip_select(HF.conv3d_1to8(lr, W3, b3), B, r, 3))    # [2B, C, h, 2r]
-        return HF.pack_border_paste(y, o_tb, o_lr, r, lr_t)
+        return HF.pack_border_paste(y, o_tb, o_lr, r, lr_t, rows)
 
     def forward(self, x):
         P = HF.space_to_depth(x)
