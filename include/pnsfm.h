@@ -621,6 +621,49 @@ int pnsfm_velocity_loss_forward(const float* const* pred, const float* const* gt
 int pnsfm_velocity_loss_backward(const float* const* pred, const float* const* gt, int J, int B, float weight, const float* upstream,
                                  float* dpred, void* stream);
 
+/* ---- ResNet networks: the memory-bound kernels of DepthResNet / PoseResNet (csrc/resnet.h), since ABI version 8 ---------------------
+ * fp32 only.  No atomics, one fixed summation order: bit-reproducible.  Act codes: 0 none, 1 ELU, 2 ReLU, 3 DISP (act_crop only).
+ *
+ * pnsfm_batchnorm_act_forward (torch.nn.BatchNorm2d + the `out += identity; relu(out)` of torchvision's BasicBlock):
+ *   y = act(BN(x) + res), x / res / y: [B,C,HW], res nullable, act 0 or 2.  training != 0: per-channel mean and biased variance over the
+ *   n = B HW values (accumulated in fp64 around the channel's first value); save_stats [2C] DOUBLES = mean | rstd for the backward;
+ *   running_mean / running_var (nullable) <- (1 - momentum) old + momentum new, the variance as var n / (n - 1); num_batches_tracked
+ *   (int64, nullable) += 1; n == 1 is an error ("Expected more than 1 value per channel when training").  training == 0: normalises with
+ *   the running statistics, writes none of them, save_stats may be null.  pnsfm_batchnorm_last_path(): the path the last forward OR
+ *   backward launch took -- 0: one workgroup per channel, one launch (B HW / 4 <= 2048 where HW % 4 == 0, else B HW <= 2048); 1: per-(channel,
+ *   chunk) partial sums in the stream's scratch + an apply launch that adds them in chunk order; 2: eval forward (apply launch alone).
+ * pnsfm_batchnorm_act_backward: g = dy act'(y) from the saved OUTPUT y (read only when act == 2); dres (nullable) = g; dbeta = sum g;
+ *   dgamma = sum g xhat; dx = gamma rstd (g - dbeta / n - xhat dgamma / n); training == 0: dx = gamma rstd g with the running statistics.
+ * pnsfm_maxpool3x3s2_forward (nn.MaxPool2d(3, 2, 1), resnet_encoder.py:92): x [N,H,W] -> y [N,Ho,Wo], Ho = (H - 1) / 2 + 1; arg: the
+ *   window slot ky 3 + kx of the maximum as uint8, the FIRST maximum in row-major window order on ties (ATen's rule; NaN wins).
+ * pnsfm_maxpool3x3s2_backward: dx [N,H,W], every element written: a gather over the <= 4 windows that cover a pixel.
+ * pnsfm_reflect_pad1_forward (nn.ReflectionPad2d(1) of Conv3x3, layers.py:46, with layers.py:57-60 upsample in front when s == 2):
+ *   x [B,C,h,w] -> channels [c0, c0 + C) of y [B,Ctot,s h + 2,Wp] (Ctot > C: the decoder's concatenation is written in place); Wp >= s w + 2
+ *   is the output's row pitch, the columns from s w + 2 on are written as zero (a width the convolution kernels tile well).
+ *   s in {1, 2}; s h < 2 or s w < 2 is an error, as in torch.
+ * pnsfm_reflect_pad1_backward: dx [B,C,h,w] = the sum of the <= 16 elements of dy's channel slice (pitch Wp) that read the pixel, in one fixed order (rows
+ *   outer, columns inner; per up-sampled row its leading-border image, itself, its trailing-border image).
+ * pnsfm_act_crop_forward: y[n,i,j] = act(z[n,i + m,j + m]), z [N,H + 2m,Wz], Wz >= W + 2m, y [N,H,W], m in {0, 1}; DISP(v) = p0 + p1 sigmoid(v)
+ *   (depth_decoder.py:62 + layers.py:12-19: p0 = 1 / max_depth, p1 = 1 / min_depth - 1 / max_depth); p0, p1 ignored otherwise.
+ * pnsfm_act_crop_backward: dz [N,H + 2m,Wz] = dy act'(.) from the saved y inside the crop, zero outside.
+ * pnsfm_affine: y = x s + t, n elements (resnet_encoder.py:88 with s = 1 / 0.225, t = -0.45 / 0.225; its backward is t = 0). */
+int pnsfm_batchnorm_act_forward(const float* x, const float* res /*nullable*/, const float* gamma, const float* beta,
+                                float* running_mean /*nullable*/, float* running_var /*nullable*/, long long* num_batches_tracked /*nullable*/,
+                                float* y, double* save_stats, int B, int C, int HW, float eps, float momentum, int act, int training,
+                                void* stream);
+int pnsfm_batchnorm_act_backward(const float* dy, const float* y, const float* x, const float* gamma, const double* save_stats,
+                                 const float* running_mean, const float* running_var, float* dx, float* dres /*nullable*/, float* dgamma,
+                                 float* dbeta, int B, int C, int HW, float eps, int act, int training, void* stream);
+int pnsfm_batchnorm_last_path(void);
+int pnsfm_maxpool3x3s2_forward(const float* x, float* y, uint8_t* arg, int N, int H, int W, void* stream);
+int pnsfm_maxpool3x3s2_backward(const float* dy, const uint8_t* arg, float* dx, int N, int H, int W, void* stream);
+int pnsfm_reflect_pad1_forward(const float* x, float* y, int B, int C, int h, int w, int s, int Ctot, int c0, int Wp, void* stream);
+int pnsfm_reflect_pad1_backward(const float* dy, float* dx, int B, int C, int h, int w, int s, int Ctot, int c0, int Wp, void* stream);
+int pnsfm_act_crop_forward(const float* z, float* y, int N, int H, int W, int m, int Wz, int act, float p0, float p1, void* stream);
+int pnsfm_act_crop_backward(const float* dy, const float* y, float* dz, int N, int H, int W, int m, int Wz, int act, float p0, float p1,
+                            void* stream);
+int pnsfm_affine(const float* x, float* y, size_t n, float s, float t, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -743,3 +743,5 @@ int pnsfm_set_gn_fused(int on) {
 }
 
 }  // extern "C"
+
+#include "resnet.h"        // the ResNet networks' memory-bound kernels: dense BatchNorm (+ residual, ReLU), max pooling, reflection pad, act + crop

@@ -96,6 +96,17 @@ SIGNATURES = {
     # velocity supervision (csrc/velocity.h)
     "pnsfm_velocity_loss_forward": (_i, [_p, _p, _i, _i, _f, _p, _p, _p]),
     "pnsfm_velocity_loss_backward": (_i, [_p, _p, _i, _i, _f, _p, _p, _p]),
+    # ResNet networks (csrc/resnet.h)
+    "pnsfm_batchnorm_act_forward": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _f, _f, _i, _i, _p]),
+    "pnsfm_batchnorm_act_backward": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _f, _i, _i, _p]),
+    "pnsfm_batchnorm_last_path": (_i, []),
+    "pnsfm_maxpool3x3s2_forward": (_i, [_p, _p, _p, _i, _i, _i, _p]),
+    "pnsfm_maxpool3x3s2_backward": (_i, [_p, _p, _p, _i, _i, _i, _p]),
+    "pnsfm_reflect_pad1_forward": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "pnsfm_reflect_pad1_backward": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "pnsfm_act_crop_forward": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _f, _f, _p]),
+    "pnsfm_act_crop_backward": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _f, _p]),
+    "pnsfm_affine": (_i, [_p, _p, _sz, _f, _f, _p]),
     "pnsfm_photometric_l1_forward": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p]),
     "pnsfm_photometric_l1_backward": (_i, [_p, _p, _p, _p, _f, _p, _i, _i, _i, _i, _i, _i, _p]),
     "pnsfm_smoothness_forward": (_i, [_p, _p, _p, _i, _i, _i, _p]),

@@ -885,7 +885,7 @@ class Conv2dStride2Fn(Function):
     data-gradient is the stride-1 backward-data kernel on dy zero-upsampled onto the input grid."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, cache, recording=True):
+    def forward(ctx, x, weight, bias, cache, recording=True, wgrad_s1=False):
         x = x.contiguous()
         need_dx = ctx.needs_input_grad[0]
         wp_fwd, wp_bwd = cache.get(weight, need_dx)
@@ -893,6 +893,10 @@ class Conv2dStride2Fn(Function):
         y = ops.conv2d_forward_strided(x, wp_fwd, bias.detach() if bias is not None else None, Cout, ks, 2)
         ctx.save_for_backward(x, wp_bwd if wp_bwd is not None else x.new_empty(0))
         ctx.meta = (Cin, Cout, ks, bias is not None)
+        # wgrad_s1: the weight gradient as the STRIDE-1 weight gradient of x with dy zero-upsampled onto the input grid (the tensor the
+        # data gradient builds anyway) -- the same sums, the zeros adding nothing.  For wide layers on short maps (ResNet's layer{2,3,4}.0:
+        # 256 -> 512 channels onto 6x20), whose patch the strided weight-gradient kernel cannot hold in LDS.
+        ctx.wgrad_s1 = bool(wgrad_s1)
         ctx.params = (weight, bias)
         _WgradStream.note_use(recording, weight, bias)
         return y
@@ -906,19 +910,27 @@ class Conv2dStride2Fn(Function):
         want_w = ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2])
         detached = _WgradStream.side_ok(*ctx.params)
 
-        def dgrad():
+        def upsampled():
             B, _, H, W = x.shape
             up = dy.new_zeros((B, Cout, H, W))
             up[:, :, ::2, ::2] = dy                      # dy[y][x] sits at (2y, 2x) of the input grid
-            return ops.conv2d_backward_data(up, wp_bwd, Cin, ks)
+            return up
+
+        if ctx.wgrad_s1:
+            up = upsampled()                             # once, for both gradients
+            dx, dw, db = _WgradStream.run_beside(up, want_w, detached, lambda: ops.conv2d_backward_weight(x, up, ks, want_bias=has_bias),
+                                                 (lambda: ops.conv2d_backward_data(up, wp_bwd, Cin, ks)) if ctx.needs_input_grad[0] else None,
+                                                 (x, up))
+            return dx, dw, db, None, None, None
 
         dx, dw, db = _WgradStream.run_beside(dy, want_w, detached, lambda: ops.conv2d_backward_weight_strided(x, dy, ks, 2, want_bias=has_bias),
-                                             dgrad if ctx.needs_input_grad[0] else None, (x, dy))
-        return dx, dw, db, None, None
+                                             (lambda: ops.conv2d_backward_data(upsampled(), wp_bwd, Cin, ks)) if ctx.needs_input_grad[0] else None,
+                                             (x, dy))
+        return dx, dw, db, None, None, None
 
 
-def conv2d_stride2(x, weight, bias, cache):
-    return Conv2dStride2Fn.apply(x, weight, bias, cache, torch.is_grad_enabled())
+def conv2d_stride2(x, weight, bias, cache, wgrad_s1=False):
+    return Conv2dStride2Fn.apply(x, weight, bias, cache, torch.is_grad_enabled(), wgrad_s1)
 
 
 class GroupNormActFn(Function):
@@ -1397,6 +1409,161 @@ def upsample_nearest(x, size=None, scale_factor=None):
     if size is not None:
         return torch.nn.functional.interpolate(x, size=(H, W), mode='nearest')
     return torch.nn.functional.interpolate(x, scale_factor=scale_factor, mode='nearest')
+
+
+# ---- ResNet networks (csrc/resnet.h): dense BatchNorm (+ residual, ReLU), max pooling, reflection pad, activation + crop -----------------
+_RESNET_NO_H16 = "%s has no fp16 kernels: the fp16 forward covers the depth networks PackNet01 / PackNetSlim01 only; run it in float32"
+
+
+def _no_h16(what, *tensors):
+    if any(t is not None and t.dtype == torch.float16 for t in tensors):
+        raise NotImplementedError(_RESNET_NO_H16 % what)
+
+
+class BatchNormActFn(Function):
+    """y = act(BatchNorm(x) + res), act in {ACT_NONE, ACT_RELU}: nn.BatchNorm2d and the `out += identity; relu(out)` of torchvision's
+    BasicBlock in one launch (two on large maps).  Training mode updates running_mean / running_var / num_batches_tracked on the device.
+    Saved for backward: x, the output y (which the next layer holds anyway) and the [2, C] float64 batch statistics."""
+
+    @staticmethod
+    def forward(ctx, x, res, gamma, beta, running_mean, running_var, num_batches_tracked, eps, momentum, act, training):
+        x = x.contiguous()
+        res = res.contiguous() if res is not None else None
+        y, stats = ops.batchnorm_act_forward(x, res, gamma.detach(), beta.detach(), running_mean, running_var, num_batches_tracked, eps,
+                                             momentum, act, training)
+        ctx.save_for_backward(x, y, gamma, stats if stats is not None else x.new_empty(0))
+        ctx.running = None if training else (running_mean, running_var)
+        ctx.meta = (eps, act, res is not None)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        x, y, gamma, stats = ctx.saved_tensors
+        eps, act, has_res = ctx.meta
+        rm, rv = ctx.running if ctx.running is not None else (None, None)
+        dy = dy.contiguous()
+        want_dres = has_res and ctx.needs_input_grad[1]
+        dx, dres, dgamma, dbeta = ops.batchnorm_act_backward(dy, y, x, gamma.detach(), stats if ctx.running is None else None, rm, rv, eps, act,
+                                                             want_dres)
+        if want_dres and dres is None:
+            dres = dy                       # no activation: the residual's gradient is the upstream gradient itself
+        return dx, (dres if want_dres else None), dgamma, dbeta, None, None, None, None, None, None, None
+
+
+def batchnorm_act(x, bn, act=ops.ACT_NONE, res=None):
+    """act(bn(x) + res) for an nn.BatchNorm2d `bn` (a parameter and buffer container: its own forward is not called)."""
+    _no_h16('batchnorm_act', x, res, bn.weight)
+    if bn.momentum is None or not bn.affine or not bn.track_running_stats:
+        raise NotImplementedError("batchnorm_act: BatchNorm2d(affine=True, track_running_stats=True, momentum=<float>) only")
+    return BatchNormActFn.apply(x, res, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.eps, bn.momentum,
+                                act, bn.training)
+
+
+class MaxPool3x3s2Fn(Function):
+    """nn.MaxPool2d(kernel_size=3, stride=2, padding=1); the arg-max window slot is kept as uint8, the backward is a gather."""
+
+    @staticmethod
+    def forward(ctx, x):
+        y, arg = ops.maxpool3x3s2_forward(x.contiguous())
+        ctx.save_for_backward(arg)
+        ctx.in_shape = tuple(x.shape)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        arg, = ctx.saved_tensors
+        return ops.maxpool3x3s2_backward(dy.contiguous(), arg, ctx.in_shape)
+
+
+def maxpool3x3s2(x):
+    _no_h16('maxpool3x3s2', x)
+    return MaxPool3x3s2Fn.apply(x)
+
+
+class ReflectPad1Fn(Function):
+    """cat([ReflectionPad2d(1)(upsample_nearest(x_i, s_i)) for i], 1): every source is written straight into its channel range of the one
+    output (the padded copy has to be written anyway, so the concatenation costs nothing and the convolution behind it has one source)."""
+
+    @staticmethod
+    def forward(ctx, ups, pitch, *xs):
+        xs = tuple(t.contiguous() for t in xs)
+        ctx.ups = tuple(ups)
+        ctx.shapes = tuple(tuple(t.shape) for t in xs)
+        return ops.reflect_pad1_forward(xs, ctx.ups, pitch)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        return (None, None) + tuple(ops.reflect_pad1_backward(dy.contiguous(), ctx.shapes, ctx.ups, ctx.needs_input_grad[2:]))
+
+
+def reflect_pad1(xs, up=1, pitch=None):
+    """xs: a tensor or a tuple of tensors (their channel concatenation); up: one factor (1 | 2) for all, or one per source; pitch: the
+    output's width where it should exceed W + 2 (zero columns on the right)."""
+    xs = tuple(xs) if isinstance(xs, (tuple, list)) else (xs,)
+    ups = tuple(up) if isinstance(up, (tuple, list)) else (up,) * len(xs)
+    _no_h16('reflect_pad1', *xs)
+    if len(ups) != len(xs):
+        raise ValueError("reflect_pad1: %d sources, %d factors" % (len(xs), len(ups)))
+    return ReflectPad1Fn.apply(ups, pitch, *xs)
+
+
+class ActCropFn(Function):
+    """y = act(z[..., m:H-m, m:W-m]), act in {ACT_NONE, ACT_ELU, ACT_RELU, ACT_DISP}; backward from the saved output."""
+
+    @staticmethod
+    def forward(ctx, z, m, act, p0, p1, width=None):
+        y = ops.act_crop_forward(z.contiguous(), m, act, p0, p1, width)
+        ctx.save_for_backward(y)
+        ctx.meta = (m, act, p0, p1, z.shape[-1])
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        y, = ctx.saved_tensors
+        return ops.act_crop_backward(dy.contiguous(), y, *ctx.meta), None, None, None, None, None
+
+
+def act_crop(z, m=0, act=ops.ACT_RELU, disp=(0.0, 1.0), width=None):
+    """act(z) with m in {0, 1} border pixels dropped; ACT_DISP: disp[0] + disp[1] * sigmoid(z); width: the output's width where z has
+    more than width + 2 m columns (a pitched map: the rest is dropped too)."""
+    _no_h16('act_crop', z)
+    return ActCropFn.apply(z, m, act, float(disp[0]), float(disp[1]), width)
+
+
+class AffineFn(Function):
+    @staticmethod
+    def forward(ctx, x, s, t):
+        ctx.s = s
+        return ops.affine(x.contiguous(), s, t)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        return ops.affine(dy.contiguous(), ctx.s, 0.0), None, None
+
+
+def affine(x, s, t):
+    _no_h16('affine', x)
+    return AffineFn.apply(x, float(s), float(t))
+
+
+def conv3x3_reflect(xs, weight, bias, cache, act=ops.ACT_ELU, up=1, disp=(0.0, 1.0)):
+    """The decoder's Conv3x3 (ReflectionPad2d(1) + Conv2d(3)) and the activation behind it, on `xs` (a tensor, or a tuple standing for
+    the channel concatenation), each source up-sampled by `up` first: reflect_pad1 -> the zero-pad "same" convolution on the
+    (H + 2) x (W + 2) map, whose interior is exactly the valid convolution of the padded map -> act_crop(m = 1)."""
+    if tuple(weight.shape[2:]) != (3, 3):
+        raise ValueError("conv3x3_reflect: 3x3 weights only, got %s" % (tuple(weight.shape),))
+    first = xs[0] if isinstance(xs, (tuple, list)) else xs
+    s0 = up[0] if isinstance(up, (tuple, list)) else up
+    W = s0 * first.shape[3]
+    # a padded map wider than 320 columns whose width is no multiple of 32 does not fit the convolution kernels' tiles (KITTI's 642):
+    # the pad kernel writes it at the next multiple of 32, zero columns on the right, which only reach outputs the crop drops
+    pitch = -(-(W + 2) // 32) * 32 if (W + 2) > 320 and (W + 2) % 32 else None
+    return act_crop(conv2d(reflect_pad1(xs, up, pitch), weight, bias, cache), 1, act, disp, width=W)
 
 
 class LossCombineFn(Function):

@@ -501,6 +501,154 @@ def upsample_nearest_backward(dy, s):
     return dx
 
 
+# ------------------------------------------------------------------------------------- ResNet networks
+ACT_DISP = 3                      # act_crop only: p0 + p1 * sigmoid(z)
+BN_PATH_FUSED, BN_PATH_CHUNKED, BN_PATH_EVAL = 0, 1, 2
+BN_FUSE_UNITS = 2048              # kBnFuseUnits of csrc/resnet.h: path 0 up to this many float4 (HW % 4 == 0) or floats per channel
+
+
+def batchnorm_last_path():
+    """The path the last batchnorm_act launch (either direction) took: BN_PATH_*; -1 before the first."""
+    return int(_lib.get().pnsfm_batchnorm_last_path())
+
+
+def _bn_shape(x):
+    if x.dim() < 2:
+        raise ValueError("batchnorm_act needs a [B, C, ...] tensor, got %s" % (tuple(x.shape),))
+    B, C = x.shape[0], x.shape[1]
+    return B, C, (x.numel() // (B * C) if B * C else 0)
+
+
+def batchnorm_act_forward(x, res, gamma, beta, running_mean, running_var, num_batches_tracked, eps, momentum, act, training):
+    """y = act(BN(x) + res) -> (y, stats): stats [2, C] float64 = mean | rstd (None in eval mode).  In training mode the running
+    statistics and the step counter (all nullable) are updated on the device."""
+    _chk(x, res, gamma, beta, running_mean, running_var, num_batches_tracked); _f32(x, res, gamma, beta, running_mean, running_var)
+    B, C, HW = _bn_shape(x)
+    if training and B * HW == 1:
+        raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (tuple(x.shape),))
+    if num_batches_tracked is not None and num_batches_tracked.dtype != torch.int64:
+        raise RuntimeError("batchnorm_act: num_batches_tracked must be int64")
+    y = torch.empty_like(x)
+    stats = torch.empty((2, C), dtype=torch.float64, device=x.device) if training else None
+    rc = _lib.get().pnsfm_batchnorm_act_forward(_ptr(x), _ptr(res), _ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var),
+                                                _ptr(num_batches_tracked), _ptr(y), _ptr(stats), B, C, HW, float(eps), float(momentum),
+                                                act, 1 if training else 0, _stream(x))
+    _lib.check(rc, "batchnorm_act_forward")
+    return y, stats
+
+
+def batchnorm_act_backward(dy, y, x, gamma, stats, running_mean, running_var, eps, act, want_dres):
+    """-> (dx, dres or None, dgamma, dbeta).  stats: the forward's [2, C] float64 (training) or None (eval: running statistics).  With
+    act == ACT_NONE the residual's gradient is dy itself: nothing is written for it (the caller hands dy on)."""
+    _chk(dy, y, x, gamma, stats, running_mean, running_var); _f32(dy, y, x, gamma, running_mean, running_var)
+    B, C, HW = _bn_shape(x)
+    dx = torch.empty_like(x)
+    dres = torch.empty_like(x) if (want_dres and act != ACT_NONE) else None
+    dgb = torch.empty((2, C), dtype=torch.float32, device=x.device)
+    rc = _lib.get().pnsfm_batchnorm_act_backward(_ptr(dy), _ptr(y), _ptr(x), _ptr(gamma), _ptr(stats), _ptr(running_mean), _ptr(running_var),
+                                                 _ptr(dx), _ptr(dres), _ptr(dgb[0]), _ptr(dgb[1]), B, C, HW, float(eps), act,
+                                                 0 if stats is None else 1, _stream(x))
+    _lib.check(rc, "batchnorm_act_backward")
+    return dx, dres, dgb[0], dgb[1]
+
+
+def _planes(x, what):
+    if x.dim() < 2:
+        raise ValueError("%s needs a [..., H, W] tensor, got %s" % (what, tuple(x.shape)))
+    H, W = x.shape[-2], x.shape[-1]
+    return (x.numel() // (H * W) if H * W else 0), H, W
+
+
+def maxpool3x3s2_forward(x):
+    """x [..., H, W] -> (y [..., Ho, Wo], arg uint8 of y's shape: the window slot of the maximum)."""
+    _chk(x); _f32(x)
+    N, H, W = _planes(x, "maxpool3x3s2")
+    shape = tuple(x.shape[:-2]) + ((H - 1) // 2 + 1, (W - 1) // 2 + 1)
+    y = torch.empty(shape, dtype=torch.float32, device=x.device)
+    arg = torch.empty(shape, dtype=torch.uint8, device=x.device)
+    _lib.check(_lib.get().pnsfm_maxpool3x3s2_forward(_ptr(x), _ptr(y), _ptr(arg), N, H, W, _stream(x)), "maxpool3x3s2_forward")
+    return y, arg
+
+
+def maxpool3x3s2_backward(dy, arg, in_shape):
+    _chk(dy, arg); _f32(dy)
+    dx = torch.empty(tuple(in_shape), dtype=torch.float32, device=dy.device)
+    N, H, W = _planes(dx, "maxpool3x3s2")
+    _lib.check(_lib.get().pnsfm_maxpool3x3s2_backward(_ptr(dy), _ptr(arg), _ptr(dx), N, H, W, _stream(dy)), "maxpool3x3s2_backward")
+    return dx
+
+
+def reflect_pad1_forward(xs, ups, pitch=None):
+    """pitch: the output's width (>= W + 2; default W + 2), the columns from W + 2 on zero.  xs: [B, C_i, h_i, w_i] tensors, ups: one up-sampling factor (1 | 2) each, with every s_i h_i x s_i w_i the same H x W ->
+    [B, sum C_i, H + 2, W + 2]: each source (nearest up-sampled by its factor, then) reflection-padded by 1 into its channel range."""
+    _chk(*xs); _f32(*xs)
+    B = xs[0].shape[0]
+    H, W = ups[0] * xs[0].shape[2], ups[0] * xs[0].shape[3]
+    for t, s in zip(xs, ups):
+        if t.dim() != 4 or t.shape[0] != B or (s * t.shape[2], s * t.shape[3]) != (H, W) or s not in (1, 2):
+            raise ValueError("reflect_pad1: sources %s with factors %s do not share one batch and size" % ([tuple(t.shape) for t in xs], list(ups)))
+    Ctot = sum(t.shape[1] for t in xs)
+    Wp = W + 2 if pitch is None else int(pitch)
+    if Wp < W + 2:
+        raise ValueError("reflect_pad1: pitch %d is narrower than the padded map (%d)" % (Wp, W + 2))
+    y = torch.empty((B, Ctot, H + 2, Wp), dtype=torch.float32, device=xs[0].device)
+    c0 = 0
+    for t, s in zip(xs, ups):
+        C, h, w = t.shape[1:]
+        _lib.check(_lib.get().pnsfm_reflect_pad1_forward(_ptr(t), _ptr(y), B, C, h, w, s, Ctot, c0, Wp, _stream(t)), "reflect_pad1_forward")
+        c0 += C
+    return y
+
+
+def reflect_pad1_backward(dy, shapes, ups, needs):
+    """dy [B, sum C_i, H + 2, W + 2] -> one gradient (or None where `needs` says so) per source of reflect_pad1_forward."""
+    _chk(dy); _f32(dy)
+    B, Ctot = dy.shape[0], dy.shape[1]
+    out, c0 = [], 0
+    for shape, s, need in zip(shapes, ups, needs):
+        C, h, w = shape[1:]
+        dx = None
+        if need:
+            dx = torch.empty(tuple(shape), dtype=torch.float32, device=dy.device)
+            _lib.check(_lib.get().pnsfm_reflect_pad1_backward(_ptr(dy), _ptr(dx), B, C, h, w, s, Ctot, c0, dy.shape[3], _stream(dy)), "reflect_pad1_backward")
+        out.append(dx)
+        c0 += C
+    return out
+
+
+def act_crop_forward(z, m, act, p0=0.0, p1=1.0, width=None):
+    """width: the output's width where z is wider than width + 2 m (a pitched map of reflect_pad1_forward); default: all of z."""
+    _chk(z); _f32(z)
+    N, Hz, Wz = _planes(z, "act_crop")
+    H, W = Hz - 2 * m, (Wz - 2 * m if width is None else int(width))
+    if W + 2 * m > Wz:
+        raise ValueError("act_crop: width %d + crop does not fit the %d columns" % (W, Wz))
+    if m not in (0, 1) or H < 1 or W < 1:
+        raise ValueError("act_crop: crop %d of a %d x %d map" % (m, Hz, Wz))
+    y = torch.empty(tuple(z.shape[:-2]) + (H, W), dtype=torch.float32, device=z.device)
+    _lib.check(_lib.get().pnsfm_act_crop_forward(_ptr(z), _ptr(y), N, H, W, m, Wz, act, float(p0), float(p1), _stream(z)), "act_crop_forward")
+    return y
+
+
+def act_crop_backward(dy, y, m, act, p0=0.0, p1=1.0, in_width=None):
+    _chk(dy, y); _f32(dy, y)
+    N, H, W = _planes(y, "act_crop")
+    Wz = W + 2 * m if in_width is None else int(in_width)
+    dz = torch.empty(tuple(y.shape[:-2]) + (H + 2 * m, Wz), dtype=torch.float32, device=y.device)
+    _lib.check(_lib.get().pnsfm_act_crop_backward(_ptr(dy), _ptr(y), _ptr(dz), N, H, W, m, Wz, act, float(p0), float(p1), _stream(y)),
+               "act_crop_backward")
+    return dz
+
+
+def affine(x, s, t):
+    """x * s + t."""
+    _chk(x); _f32(x)
+    y = torch.empty_like(x)
+    if x.numel():
+        _lib.check(_lib.get().pnsfm_affine(_ptr(x), _ptr(y), x.numel(), float(s), float(t), _stream(x)), "affine")
+    return y
+
+
 # ------------------------------------------------------------------------------- scalar tail of the loss
 def loss_combine_forward(photometric, smoothness, weight):
     """photometric / smoothness: lists of 0-dim device tensors -> out3 = (loss, weighted smoothness, photometric)."""
