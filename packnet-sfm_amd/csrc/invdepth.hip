@@ -294,10 +294,14 @@ int pnsfm_invdepth_conv_backward(const float* x, const float* w, const float* dz
   if (B <= 0 || C <= 0 || H <= 0 || W <= 0) { set_error("invdepth_conv_backward: bad shape"); return -1; }
   if ((size_t)H * W * 4 >= 0x7fffffffull) { set_error("invdepth_conv_backward: plane exceeds the 2 GiB buffer window"); return -1; }
   hipStream_t s = (hipStream_t)stream;
-  // pixels per thread: up to 16 (amortises the 73-value block reduction) while the grid keeps >= ~2 blocks per CU
+  // pixels per thread: up to 16 (amortises the 73-value block reduction) while the grid keeps >= ~2 blocks per CU;
+  // PNSFM_INVDEPTH_BWD_PPT = 1 / 2 / 4 / 8 / 16: always that many (tests), anything else: this rule
   const int HW = H * W, cgroups = ceil_div(C, kIdCh);
   int ppt = 16;
   while (ppt > 1 && (long)ceil_div(HW, 256 * ppt) * cgroups * B < 512) ppt >>= 1;
+  const char* e = getenv("PNSFM_INVDEPTH_BWD_PPT");
+  const int forced = e ? atoi(e) : 0;
+  if (forced == 1 || forced == 2 || forced == 4 || forced == 8 || forced == 16) ppt = forced;
   const int gx = ceil_div(HW, 256 * ppt);
   ScratchLease lease(s, (size_t)gx * B * cgroups * kIdVals * sizeof(float));
   float* const part = lease.as<float>();
