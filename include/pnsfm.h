@@ -284,6 +284,35 @@ int pnsfm_conv3d_backward_data(const float* dout, const float* w3, float* dp,
                                int B, int D, int H, int W, int NF, void* stream);
 int pnsfm_conv3d_backward_weight(const float* p, const float* dout, float* dw3, float* db3, double* ws,
                                  int B, int D, int H, int W, int NF, void* stream);
+/* The unpacking block's pair Conv3d -> depth_to_space with the shuffle folded into the stencil's stores (csrc/pack3d.hip; DESIGN.md
+ * 3b).  y: [B, NF*D/4, 2H, 2W] = depth_to_space of the Conv3d output; output channel f*D+d lands at channel (f*D+d)/4, row
+ * 2y + (d%4)/2, column 2x + d%2.  Every value is bit for bit that of the unfolded sequence of entry points above.
+ * forward_d2s: one launch when pnsfm_conv3d_d2s_folded(p, y, D, W) == 1 (the fold switch on, W % 4 == 0, D % 4 == 0, both tensors
+ *   16-byte aligned); tmp is then not touched and may be NULL.  Otherwise pnsfm_conv3d_forward into tmp [B,NF*D,H,W], then
+ *   pnsfm_depth_to_space.
+ * pnsfm_set_pack3d_fold(0) (or PNSFM_PACK3D_FOLD=0 in the environment, read once) selects the unfolded launch sequence everywhere,
+ * also inside pnsfm_pack_bias_eff_forward; 1 (the default) every fold; an even value a subset for A/B runs: 2 forward_d2s, 4
+ * pack_bias_eff_forward, 8 the *_rows entry points.  Returns the previous setting.
+ *
+ * Border strips of the collapsed packing block: p / dp [B, D, S, W] are strips of S = 2r + 1 rows, the first Bh samples
+ * top (or left, transposed) strips, the others bottom strips; only the 2r rows whose stencil lies inside the strip are kept: rows
+ * 0 .. 2r-1 of a sample b < Bh, rows 1 .. 2r of the others.  out / dout [B, NF*D, 2r, W] holds exactly those rows: forward_rows
+ * computes and stores nothing else, the two gradients read dout at its place in the S-row frame (the dropped row is zero) and
+ * backward_data_rows writes all S rows of dp.  Values are bit for bit those of the entry points above on the full frame followed by
+ * the row selection / preceded by its zero-filled gradient.  forward_rows needs W % 4 == 0 and 16-byte aligned p / out,
+ * backward_weight_rows the default weight-gradient kernel; pnsfm_conv3d_rows_folded(p, out, W) == 1 says that all three apply
+ * (and that the switch is on); elsewhere the caller runs the full frame. */
+int pnsfm_set_pack3d_fold(int on);
+int pnsfm_conv3d_d2s_folded(const float* p, const float* y, int D, int W);
+int pnsfm_conv3d_forward_d2s(const float* p, const float* w3, const float* b3, float* tmp /*nullable when folded*/, float* y,
+                             int B, int D, int H, int W, int NF, void* stream);
+int pnsfm_conv3d_rows_folded(const float* p, const float* out, int W);
+int pnsfm_conv3d_forward_rows(const float* p, const float* w3, const float* b3, float* out, int B, int D, int S, int W, int NF, int Bh,
+                              void* stream);
+int pnsfm_conv3d_backward_data_rows(const float* dout, const float* w3, float* dp, int B, int D, int S, int W, int NF, int Bh,
+                                    void* stream);
+int pnsfm_conv3d_backward_weight_rows(const float* p, const float* dout, float* dw3, float* db3, int B, int D, int S, int W, int NF,
+                                      int Bh, void* stream);
 
 /* ---- InvDepth activation: y = sigmoid(x) / min_depth  (layers01.py:119-122) --------------- */
 int pnsfm_invdepth_act_forward(const float* x, float* y, size_t n, float min_depth, void* stream);

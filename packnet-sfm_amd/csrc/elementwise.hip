@@ -327,6 +327,31 @@ __global__ void __launch_bounds__(256) pack_bias_eff_kernel(const float* __restr
   }
 }
 
+// The same sums on a (d, C) grid: the kernel above keeps C = 64 .. 256 workgroups busy with d blocks one after the other, two
+// barriers each (38 us per launch for at most 19 MB).  One workgroup per (co, f) block here; a thread adds the elements the kernel
+// above gives it, in that order, and the wave / LDS reduction is the same, so Ssum is bit-identical.  bias_eff needs a row's d sums
+// in f order: pack_bias_eff_tail_kernel, one thread per co, after it on the stream.
+__global__ void __launch_bounds__(256) pack_bias_ssum_kernel(const float* __restrict__ W2, float* __restrict__ Ssum, int d, int blk) {
+  __shared__ float part[4];
+  const int f = blockIdx.x, co = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float* p = W2 + ((size_t)co * d + f) * blk;
+  float acc = 0.f;
+  for (int e = threadIdx.x; e < blk; e += 256) acc += p[e];
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o);
+  if (lane == 0) part[wave] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) Ssum[(size_t)co * d + f] = ((part[0] + part[1]) + part[2]) + part[3];
+}
+
+__global__ void __launch_bounds__(64) pack_bias_eff_tail_kernel(const float* __restrict__ Ssum, const float* __restrict__ b2,
+                                                                const float* __restrict__ b3, float* __restrict__ bias_eff, int C, int d) {
+  const int co = blockIdx.x * 64 + threadIdx.x;
+  if (co >= C) return;
+  float acc = 0.f;
+  for (int f = 0; f < d; ++f) acc += Ssum[(size_t)co * d + f] * b3[f];
+  bias_eff[co] = (b2 ? b2[co] : 0.f) + acc;
+}
+
 // gradients of that bias: db3[f] = sum_co g[co] * Ssum[co][f] (one wave per f, ascending co per lane, fixed-order lane tree)
 __global__ void __launch_bounds__(64) pack_bias_eff_db3_kernel(const float* __restrict__ g, const float* __restrict__ Ssum,
                                                                float* __restrict__ db3, int C, int d) {
@@ -535,6 +560,12 @@ int pnsfm_loss_combine_backward(const float* g, int n, int ns, float weight, flo
 int pnsfm_pack_bias_eff_forward(const float* W2, const float* b2, const float* b3, float* Ssum, float* bias_eff, int C, int d,
                                 int blk, void* stream) {
   if (C < 1 || d < 1 || d > 8 || blk < 1) { set_error("pack_bias_eff_forward: bad sizes (C=%d d=%d blk=%d)", C, d, blk); return -1; }
+  if ((pack3d_fold_mask() & PNSFM_FOLD_BIAS) && C <= 65535) {
+    PNSFM_LAUNCH(pack_bias_ssum_kernel, dim3(d, C), dim3(256), 0, (hipStream_t)stream, W2, Ssum, d, blk);
+    if (int rc = check_launch("pack_bias_eff_forward (Ssum)")) return rc;
+    PNSFM_LAUNCH(pack_bias_eff_tail_kernel, dim3((C + 63) / 64), dim3(64), 0, (hipStream_t)stream, (const float*)Ssum, b2, b3, bias_eff, C, d);
+    return check_launch("pack_bias_eff_forward (bias)");
+  }
   PNSFM_LAUNCH(pack_bias_eff_kernel, dim3(C), dim3(256), 0, (hipStream_t)stream, W2, b2, b3, Ssum, bias_eff, d, blk);
   return check_launch("pack_bias_eff_forward");
 }

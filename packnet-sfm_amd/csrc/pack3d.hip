@@ -141,25 +141,33 @@ __global__ void __launch_bounds__(256) conv3d_fwd_kernel(const T* __restrict__ p
   }
 }
 
+// Row window of the border strips (the sense of ConvRows, pnsfm_common.h): the strips [2B, D, S, w] keep 2r of their S = 2r + 1 Conv3d
+// rows, the first 2r in the leading half of the batch and the last 2r in the trailing half.  out / dout is then [2B, NF*D, Ho, w]
+// and holds the frame rows row0 .. row0 + Ho - 1, row0 = ya for samples b < Bh, yb for the others; p / dp keep all H rows.
+struct C3dRows { int Ho, Bh, ya, yb; };
+__device__ __forceinline__ int c3d_row0(const C3dRows& rw, int b) { return b < rw.Bh ? rw.ya : rw.yb; }
+
 // Four voxels per thread along x (W % 4 == 0, 16-byte aligned tensors): the 9 rows of the stencil are read as one 16-byte load
 // plus the two edge values each (27 load instructions per 4 voxels instead of 108), the weights as [tap][feature] float4
 // broadcasts from LDS, the NF outputs leave as float4 stores.  The kernel writes NF x its input: HBM-write-bound.
+// rw: the rows of the frame that out / dout holds (C3dRows; the whole frame everywhere but on the border strips)
 template <int NF>
 __global__ void __launch_bounds__(256) conv3d_fwd_x4_kernel(const float* __restrict__ p, const float* __restrict__ w3,
                                                              const float* __restrict__ b3, float* __restrict__ out,
-                                                             int D, int H, int W) {
+                                                             int D, int H, int W, C3dRows rw) {
   __shared__ __attribute__((aligned(16))) float wt[28][NF];      // [tap][feature]; row 27 = bias
   for (int i = threadIdx.x; i < 28 * NF; i += 256) {
     const int tap = i / NF, f = i - tap * NF;
     wt[tap][f] = tap < 27 ? w3[f * 27 + tap] : (b3 ? b3[f] : 0.f);
   }
   __syncthreads();
-  const int HW = H * W, DHW = D * HW, Wq = W >> 2, HWq = H * Wq;
+  const int HW = H * W, DHW = D * HW, Wq = W >> 2, HWq = rw.Ho * Wq;
   const int idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= D * HWq) return;
   const int d = idx / HWq;
   const int pq = idx - d * HWq;
-  const int y = pq / Wq, x0 = 4 * (pq - y * Wq);
+  const int yo = pq / Wq, x0 = 4 * (pq - yo * Wq);
+  const int y = yo + c3d_row0(rw, blockIdx.z);
   const float* pb = p + (size_t)blockIdx.z * DHW;
   const float* zero = pnsfm_zero_page3;
   float acc[NF][4];
@@ -197,10 +205,90 @@ __global__ void __launch_bounds__(256) conv3d_fwd_x4_kernel(const float* __restr
           for (int i = 0; i < 4; ++i) acc[f][i] = fmaf(wv[f], v[dy][i + dx], acc[f][i]);      // p[.][y + dy - 1][x0 + i + dx - 1]
       }
   }
-  float* ob = out + (size_t)blockIdx.z * NF * DHW + (size_t)d * HW + y * W + x0;
+  const int oHW = rw.Ho * W, oDHW = D * oHW;
+  float* ob = out + (size_t)blockIdx.z * NF * oDHW + (size_t)d * oHW + yo * W + x0;
 #pragma unroll
   for (int f = 0; f < NF; ++f)
-    *reinterpret_cast<float4*>(ob + (size_t)f * DHW) = make_float4(acc[f][0], acc[f][1], acc[f][2], acc[f][3]);
+    *reinterpret_cast<float4*>(ob + (size_t)f * oDHW) = make_float4(acc[f][0], acc[f][1], acc[f][2], acc[f][3]);
+}
+
+// The same kernel with the unpacking block's depth_to_space folded into its stores (D % 4 == 0): output channel f*D + d of the
+// Conv3d is channel (f*D + d) / 4, row 2y + (d % 4) / 2, column 2x + d % 2 of y [B, NF*D/4, 2H, 2W], so the planes d and d + 1 (d
+// even) of one feature interleave along x in ONE output row.  A thread owns that pair at four x: the four p planes d - 1 .. d + 2
+// are loaded once for two outputs (36 load instructions per 8 voxels instead of 54), and a feature's eight values leave as two
+// float4 stores of 32 contiguous bytes -- the [B, NF*D, H, W] tensor and d2s_v4_kernel's pass over it (unpack1: 126 MB in, 126 MB
+// out) do not exist.  Per output the fmaf chain is conv3d_fwd_x4_kernel's: bias, then dz, dy, dx ascending -- bit-identical.
+template <int NF>
+__global__ void __launch_bounds__(256) conv3d_fwd_x4_d2s_kernel(const float* __restrict__ p, const float* __restrict__ w3,
+                                                                 const float* __restrict__ b3, float* __restrict__ y,
+                                                                 int D, int H, int W) {
+  __shared__ __attribute__((aligned(16))) float wt[28][NF];      // [tap][feature]; row 27 = bias
+  for (int i = threadIdx.x; i < 28 * NF; i += 256) {
+    const int tap = i / NF, f = i - tap * NF;
+    wt[tap][f] = tap < 27 ? w3[f * 27 + tap] : (b3 ? b3[f] : 0.f);
+  }
+  __syncthreads();
+  const int HW = H * W, DHW = D * HW, Wq = W >> 2, HWq = H * Wq;
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (D >> 1) * HWq) return;
+  const int dh = idx / HWq, d = 2 * dh;
+  const int pq = idx - dh * HWq;
+  const int yr = pq / Wq, x0 = 4 * (pq - yr * Wq);
+  const float* pb = p + (size_t)blockIdx.z * DHW;
+  const float* zero = pnsfm_zero_page3;
+  float acc[2][NF][4];                                           // [plane d / d + 1][feature][x]
+#pragma unroll
+  for (int o = 0; o < 2; ++o)
+#pragma unroll
+    for (int f = 0; f < NF; ++f)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) acc[o][f][i] = wt[27][f];
+  // (not unrolled: with the four planes in one block hipcc hoists all 216 weights and 72 values -- 256 VGPRs + 110 AGPRs, one wave
+  // per SIMD; the tap row is then a uniform run-time index into the LDS table)
+#pragma unroll 1
+  for (int pz = 0; pz < 4; ++pz) {                               // p plane d - 1 + pz: tap row dz = pz of output d, dz = pz - 1 of output d + 1
+    const int dd = d + pz - 1;
+    float v[3][6];
+#pragma unroll
+    for (int dy = 0; dy < 3; ++dy) {
+      const int yy = yr + dy - 1;
+      const bool ok = dd >= 0 && dd < D && yy >= 0 && yy < H;
+      const float* row = pb + (size_t)(ok ? dd : 0) * HW + (ok ? yy : 0) * W + x0;
+      const float4 c = *reinterpret_cast<const float4*>(ok ? row : zero);
+      v[dy][0] = *((ok && x0 > 0) ? row - 1 : zero);
+      v[dy][1] = c.x; v[dy][2] = c.y; v[dy][3] = c.z; v[dy][4] = c.w;
+      v[dy][5] = *((ok && x0 + 4 < W) ? row + 4 : zero);
+    }
+#pragma unroll
+    for (int o = 0; o < 2; ++o) {
+      const int dz = pz - o;
+      if (dz < 0 || dz > 2) continue;
+#pragma unroll
+      for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 3; ++dx) {
+          float wv[NF];
+#pragma unroll
+          for (int q = 0; q < NF / 4; ++q) {
+            const float4 t = *reinterpret_cast<const float4*>(&wt[dz * 9 + dy * 3 + dx][4 * q]);
+            wv[4 * q] = t.x; wv[4 * q + 1] = t.y; wv[4 * q + 2] = t.z; wv[4 * q + 3] = t.w;
+          }
+#pragma unroll
+          for (int f = 0; f < NF; ++f)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) acc[o][f][i] = fmaf(wv[f], v[dy][i + dx], acc[o][f][i]);
+        }
+    }
+  }
+  // channel (f*D + d) / 4 = f*D/4 + d/4 (D % 4 == 0), row 2 yr + (d % 4) / 2, columns 2 x0 .. 2 x0 + 7: d at the even ones
+  const int W2 = 2 * W;
+  float* ob = y + (size_t)blockIdx.z * NF * DHW + ((size_t)(d >> 2) * 2 * H + 2 * yr + ((d >> 1) & 1)) * W2 + 2 * x0;
+#pragma unroll
+  for (int f = 0; f < NF; ++f) {
+    float* o = ob + (size_t)f * DHW;                             // D/4 channels of 2H x 2W = D*H*W floats per feature
+    *reinterpret_cast<float4*>(o) = make_float4(acc[0][f][0], acc[1][f][0], acc[0][f][1], acc[1][f][1]);
+    *reinterpret_cast<float4*>(o + 4) = make_float4(acc[0][f][2], acc[1][f][2], acc[0][f][3], acc[1][f][3]);
+  }
 }
 
 // dp[b][d][y][x] = sum_{f,dz,dy,dx} w3[f][dz][dy][dx] * dout[b][f*D + d-dz+1][y-dy+1][x-dx+1]
@@ -223,8 +311,9 @@ __global__ void __launch_bounds__(256) conv3d_fwd_x4_kernel(const float* __restr
 // executed under divergence.
 template <int NF>
 __global__ void __launch_bounds__(256) conv3d_dgrad_kernel(const float* __restrict__ dout, const float* __restrict__ w3,
-                                                            float* __restrict__ dp, int D, int H, int W, int len, int xmap) {
-  const int HW = H * W, DHW = D * HW;
+                                                            float* __restrict__ dp, int D, int H, int W, int len, int xmap,
+                                                            C3dRows rw) {
+  const int HW = H * W, DHW = D * HW, gHW = rw.Ho * W, gDHW = D * gHW, row0 = c3d_row0(rw, blockIdx.z);
   const int nchunk = (D + len - 1) / len;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   // rows y - 1 / y + 1 of a block's pixels are the centre rows of the blocks a few places before / after it: an XCD gets a
@@ -242,14 +331,14 @@ __global__ void __launch_bounds__(256) conv3d_dgrad_kernel(const float* __restri
   // one descriptor per feature slab [D][H][W] (the range-checked window); all wave-uniform, they live in SGPRs
   pnsfm_buf gbuf[NF];
 #pragma unroll
-  for (int f = 0; f < NF; ++f) gbuf[f] = pnsfm_make_buf(dout + ((size_t)blockIdx.z * NF + f) * DHW, (unsigned)DHW * 4u);
+  for (int f = 0; f < NF; ++f) gbuf[f] = pnsfm_make_buf(dout + ((size_t)blockIdx.z * NF + f) * gDHW, (unsigned)gDHW * 4u);
   float* ob = dp + (size_t)blockIdx.z * DHW + pix;
   const unsigned kOut = 0x7fffffffu;       // out-of-range byte offset -> the load returns 0
   unsigned off[3];                         // in-plane byte offsets of the centre column in rows y + 1, y, y - 1 (kOut outside the image)
 #pragma unroll
   for (int dy = 0; dy < 3; ++dy) {
     const int yy = y - dy + 1;
-    off[dy] = (inr && yy >= 0 && yy < H) ? (unsigned)(yy * W + x) * 4u : kOut;
+    off[dy] = (inr && yy >= row0 && yy < row0 + rw.Ho) ? (unsigned)((yy - row0) * W + x) * 4u : kOut;
   }
   // a_lo -> output dd-1 (complete after this plane), a_mid -> output dd, a_hi -> output dd+1
   float a_lo = 0.f, a_mid = 0.f, a_hi = 0.f;
@@ -257,7 +346,7 @@ __global__ void __launch_bounds__(256) conv3d_dgrad_kernel(const float* __restri
   for (int t = 0; t < len + 2; ++t) {
     const int dd = d0 - 1 + t;
     const bool dok = dd >= 0 && dd < D && dd <= dend;
-    const unsigned plane = dok ? (unsigned)dd * (unsigned)HW * 4u : 0u;
+    const unsigned plane = dok ? (unsigned)dd * (unsigned)gHW * 4u : 0u;
     float g[NF][9];
 #pragma unroll
     for (int dy = 0; dy < 3; ++dy) {
@@ -298,9 +387,9 @@ __global__ void __launch_bounds__(256) conv3d_dgrad_kernel(const float* __restri
 // 320): 107 -> 64 us; the step's nine volumes 417 -> 265 us (profiles/r04_ab_conv3d_dgrad_column.txt).
 template <int NF, int LEN>
 __global__ void __launch_bounds__(256) conv3d_dgrad_col_kernel(const float* __restrict__ dout, const float* __restrict__ w3,
-                                                                float* __restrict__ dp, int D, int H, int W, int xmap) {
+                                                                float* __restrict__ dp, int D, int H, int W, int xmap, C3dRows rw) {
   constexpr int FG = 1;                    // features per pass (2: 54 weights + the plane masks overflow the SGPR file again, 76 vs 64 us)
-  const int HW = H * W, DHW = D * HW;
+  const int HW = H * W, DHW = D * HW, gHW = rw.Ho * W, gDHW = D * gHW, row0 = c3d_row0(rw, blockIdx.z);
   const int nchunk = (D + LEN - 1) / LEN;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const unsigned bx = xmap ? pnsfm_xcd_logical_block(blockIdx.x, gridDim.x) : blockIdx.x;
@@ -318,7 +407,7 @@ __global__ void __launch_bounds__(256) conv3d_dgrad_col_kernel(const float* __re
 #pragma unroll
   for (int dy = 0; dy < 3; ++dy) {
     const int yy = y - dy + 1;
-    off[dy] = (inr && yy >= 0 && yy < H) ? (unsigned)(yy * W + x) * 4u : kOut;
+    off[dy] = (inr && yy >= row0 && yy < row0 + rw.Ho) ? (unsigned)((yy - row0) * W + x) * 4u : kOut;
   }
   float acc[LEN];
 #pragma unroll
@@ -327,13 +416,13 @@ __global__ void __launch_bounds__(256) conv3d_dgrad_col_kernel(const float* __re
   for (int f0 = 0; f0 < NF; f0 += FG) {
     pnsfm_buf gbuf[FG];
 #pragma unroll
-    for (int u = 0; u < FG; ++u) gbuf[u] = pnsfm_make_buf(dout + ((size_t)blockIdx.z * NF + f0 + u) * DHW, (unsigned)DHW * 4u);
+    for (int u = 0; u < FG; ++u) gbuf[u] = pnsfm_make_buf(dout + ((size_t)blockIdx.z * NF + f0 + u) * gDHW, (unsigned)gDHW * 4u);
     const float* wf = w3 + f0 * 27;
 #pragma unroll
     for (int t = 0; t < LEN + 2; ++t) {
       const int dd = d0 - 1 + t;           // this plane feeds the outputs d0 + t - 2 (dz = 0), d0 + t - 1 (dz = 1), d0 + t (dz = 2)
       const bool dok = dd >= 0 && dd < D && dd <= dend;
-      const unsigned plane = dok ? (unsigned)dd * (unsigned)HW * 4u : 0u;
+      const unsigned plane = dok ? (unsigned)dd * (unsigned)gHW * 4u : 0u;
       float g[FG][9];
 #pragma unroll
       for (int dy = 0; dy < 3; ++dy) {
@@ -494,9 +583,9 @@ typedef float c3d_f32x2 __attribute__((ext_vector_type(2)));
 template <int PF, int FPB>      // planes / steps in flight; features per workgroup (the grid's y extent is NF / FPB)
 __global__ void __launch_bounds__(256, 2) conv3d_wgrad_ring_kernel(const float* __restrict__ p, const float* __restrict__ dout,
                                                                     float* __restrict__ part, int D, int H, int W, int len, int NF,
-                                                                    int xmap) {
+                                                                    int xmap, C3dRows rw) {
   __shared__ float red[kW3Pass * kW3Row];
-  const int HW = H * W, DHW = D * HW;
+  const int HW = H * W, DHW = D * HW, gHW = rw.Ho * W, gDHW = D * gHW, row0 = c3d_row0(rw, blockIdx.z);
   const int nchunk = (D + len - 1) / len;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const unsigned bx = xmap ? pnsfm_xcd_logical_block(blockIdx.x, gridDim.x) : blockIdx.x;
@@ -514,14 +603,14 @@ __global__ void __launch_bounds__(256, 2) conv3d_wgrad_ring_kernel(const float* 
   const pnsfm_buf pbuf = pnsfm_make_buf(p + (size_t)b * DHW, (unsigned)DHW * 4u);
   pnsfm_buf gbuf[FPB];
 #pragma unroll
-  for (int f = 0; f < FPB; ++f) gbuf[f] = pnsfm_make_buf(dout + ((size_t)b * NF + fg * FPB + f) * DHW, (unsigned)DHW * 4u);
+  for (int f = 0; f < FPB; ++f) gbuf[f] = pnsfm_make_buf(dout + ((size_t)b * NF + fg * FPB + f) * gDHW, (unsigned)gDHW * 4u);
   unsigned off[3];                         // in-plane byte offsets of the centre column in rows y - 1, y, y + 1 (kOut outside the image)
 #pragma unroll
   for (int r = 0; r < 3; ++r) {
     const int yy = y + r - 1;
     off[r] = (inr && yy >= 0 && yy < H) ? (unsigned)(yy * W + x) * 4u : kOut;
   }
-  const unsigned goff = active ? (unsigned)pix * 4u : kOut;
+  const unsigned goff = (active && y >= row0 && y < row0 + rw.Ho) ? (unsigned)((y - row0) * W + x) * 4u : kOut;      // a row dout does not hold: zero
   // plane k of this thread's run is dd = d0 - 1 + k; step s is d = d0 + s and uses the planes s, s + 1, s + 2
   auto load_centres = [&](float (&c)[3], int k) {
     const int dd = d0 - 1 + k;
@@ -547,7 +636,7 @@ __global__ void __launch_bounds__(256, 2) conv3d_wgrad_ring_kernel(const float* 
   };
   auto load_g = [&](float (&g)[FPB], int sidx) {
     const int d = d0 + sidx;
-    const unsigned vo = (goff != kOut && d < dend) ? (unsigned)d * (unsigned)HW * 4u + goff : kOut;
+    const unsigned vo = (goff != kOut && d < dend) ? (unsigned)d * (unsigned)gHW * 4u + goff : kOut;
 #pragma unroll
     for (int f = 0; f < FPB; ++f) g[f] = pnsfm_buf_load(gbuf[f], vo, 0u);
   };
@@ -629,6 +718,15 @@ static int grid_for(size_t total) {
   return (int)g;
 }
 
+// the folded launch sequences of the packing / unpacking blocks (here and pnsfm_pack_bias_eff_forward); 0 = the unfolded ones (A/B
+// switch and the reference of tests/test_gpu_pack3d_fold.py)
+static int fold_mask_of(int v) { return (v & 1) ? PNSFM_FOLD_ALL : (v & PNSFM_FOLD_ALL); }
+static int g_pack3d_fold = -1;      // -1: read PNSFM_PACK3D_FOLD on first use (default: every fold)
+int pack3d_fold_mask() {
+  if (g_pack3d_fold < 0) { const char* e = getenv("PNSFM_PACK3D_FOLD"); g_pack3d_fold = (e && e[0]) ? fold_mask_of(atoi(e)) : PNSFM_FOLD_ALL; }
+  return g_pack3d_fold;
+}
+
 }  // namespace pnsfm
 
 using namespace pnsfm;
@@ -671,14 +769,39 @@ int pnsfm_conv3d_forward(const float* p, const float* w3, const float* b3, float
   if (!nf_ok(NF, "conv3d_forward")) return -1;
   if (W % 4 == 0 && (((uintptr_t)p | (uintptr_t)out) & 15) == 0) {      // four voxels per thread
     const dim3 gq(ceil_div(D * H * (W / 4), 256), 1, B);
-    if (NF == 8) PNSFM_LAUNCH((conv3d_fwd_x4_kernel<8>), gq, dim3(256), 0, (hipStream_t)stream, p, w3, b3, out, D, H, W);
-    else PNSFM_LAUNCH((conv3d_fwd_x4_kernel<4>), gq, dim3(256), 0, (hipStream_t)stream, p, w3, b3, out, D, H, W);
+    const C3dRows rw = {H, B, 0, 0};
+    if (NF == 8) PNSFM_LAUNCH((conv3d_fwd_x4_kernel<8>), gq, dim3(256), 0, (hipStream_t)stream, p, w3, b3, out, D, H, W, rw);
+    else PNSFM_LAUNCH((conv3d_fwd_x4_kernel<4>), gq, dim3(256), 0, (hipStream_t)stream, p, w3, b3, out, D, H, W, rw);
     return check_launch("conv3d_forward");
   }
   const dim3 grid(ceil_div(D * H * W, 256), 1, B);
   if (NF == 8) PNSFM_LAUNCH((conv3d_fwd_kernel<8>), grid, dim3(256), 0, (hipStream_t)stream, p, w3, b3, out, D, H, W);
   else PNSFM_LAUNCH((conv3d_fwd_kernel<4>), grid, dim3(256), 0, (hipStream_t)stream, p, w3, b3, out, D, H, W);
   return check_launch("conv3d_forward");
+}
+
+int pnsfm_set_pack3d_fold(int on) {
+  const int prev = pack3d_fold_mask();
+  g_pack3d_fold = fold_mask_of(on);
+  return prev == PNSFM_FOLD_ALL ? 1 : prev;
+}
+
+int pnsfm_conv3d_d2s_folded(const float* p, const float* y, int D, int W) {
+  return ((pack3d_fold_mask() & PNSFM_FOLD_FWD) && W % 4 == 0 && D % 4 == 0 && (((uintptr_t)p | (uintptr_t)y) & 15) == 0) ? 1 : 0;
+}
+
+int pnsfm_conv3d_forward_d2s(const float* p, const float* w3, const float* b3, float* tmp, float* y, int B, int D, int H, int W, int NF,
+                             void* stream) {
+  if (!nf_ok(NF, "conv3d_forward_d2s")) return -1;
+  if (pnsfm_conv3d_d2s_folded(p, y, D, W)) {
+    const dim3 gq(ceil_div((D / 2) * H * (W / 4), 256), 1, B);      // a thread: planes d, d + 1 at four x
+    if (NF == 8) PNSFM_LAUNCH((conv3d_fwd_x4_d2s_kernel<8>), gq, dim3(256), 0, (hipStream_t)stream, p, w3, b3, y, D, H, W);
+    else PNSFM_LAUNCH((conv3d_fwd_x4_d2s_kernel<4>), gq, dim3(256), 0, (hipStream_t)stream, p, w3, b3, y, D, H, W);
+    return check_launch("conv3d_forward_d2s");
+  }
+  if (!tmp) { set_error("conv3d_forward_d2s: the two-kernel path needs the [B, NF*D, H, W] buffer"); return -1; }
+  if (int rc = pnsfm_conv3d_forward(p, w3, b3, tmp, B, D, H, W, NF, stream)) return rc;
+  return pnsfm_depth_to_space(tmp, y, B, NF * D / 4, H, W, stream);
 }
 
 // ---- fp16 forward (evaluation / inference): the per-element kernels above on 2-byte storage
@@ -706,63 +829,118 @@ int pnsfm_conv3d_forward_h16(const void* p, const void* w3, const void* b3, void
   return check_launch("conv3d_forward_h16");
 }
 
-int pnsfm_conv3d_backward_data(const float* dout, const float* w3, float* dp, int B, int D, int H, int W, int NF, void* stream) {
-  if (!nf_ok(NF, "conv3d_backward_data")) return -1;
-  if ((size_t)D * H * W * 4 >= 0x7fffffffull) { set_error("conv3d_backward_data: feature slab exceeds the 2 GiB buffer window"); return -1; }
-  // run length along d: 8 (25 % halo planes) when that still gives every CU a few blocks, shorter for small volumes
+// run length along d of the data gradient: 8 (25 % halo planes) when that still gives every CU a few blocks, shorter for small volumes
+static int dgrad_len(int B, int D, int H, int W) {
   int len = D < 8 ? D : 8;
   while (len > 2 && (long)B * ceil_div(D, len) * H * W < 2L * 256 * 256) len = ceil_div(len, 2);
   if (const char* e = getenv("PNSFM_CONV3D_LEN")) {          // tests: pin the run length (small volumes on the 8- / 4-plane kernels)
     const int v = atoi(e);
     if (v >= 1 && v <= 8) len = v;
   }
+  return len;
+}
+
+// rw: the rows of the H-row frame that dout holds (the whole frame, or the border strips' window)
+static int conv3d_backward_data_impl(const float* dout, const float* w3, float* dp, int B, int D, int H, int W, int NF,
+                                     void* stream, const char* what, C3dRows rw) {
+  if (!nf_ok(NF, what)) return -1;
+  if ((size_t)D * H * W * 4 >= 0x7fffffffull) { set_error("%s: feature slab exceeds the 2 GiB buffer window", what); return -1; }
+  const int len = dgrad_len(B, D, H, W);
   const dim3 grid(ceil_div(ceil_div(ceil_div(D, len) * H * W, 62), 4), 1, B);      // 62 outputs per wave (two halo lanes)
   static const int xm = [] { const char* e = getenv("PNSFM_STENCIL_XCD_MAP"); return (e && e[0] == '0') ? 0 : 1; }();      // A/B switch
   const int xmap = (block_map_mode() >= 2 && xm) ? 1 : 0;
   static const int col = [] { const char* e = getenv("PNSFM_CONV3D_DGRAD_COL"); return (e && e[0] == '0') ? 0 : 1; }();      // A/B switch
   if (col && len == 8) {
-    if (NF == 8) PNSFM_LAUNCH((conv3d_dgrad_col_kernel<8, 8>), grid, dim3(256), 0, (hipStream_t)stream, dout, w3, dp, D, H, W, xmap);
-    else PNSFM_LAUNCH((conv3d_dgrad_col_kernel<4, 8>), grid, dim3(256), 0, (hipStream_t)stream, dout, w3, dp, D, H, W, xmap);
+    if (NF == 8) PNSFM_LAUNCH((conv3d_dgrad_col_kernel<8, 8>), grid, dim3(256), 0, (hipStream_t)stream, dout, w3, dp, D, H, W, xmap, rw);
+    else PNSFM_LAUNCH((conv3d_dgrad_col_kernel<4, 8>), grid, dim3(256), 0, (hipStream_t)stream, dout, w3, dp, D, H, W, xmap, rw);
   } else if (col && len == 4) {
-    if (NF == 8) PNSFM_LAUNCH((conv3d_dgrad_col_kernel<8, 4>), grid, dim3(256), 0, (hipStream_t)stream, dout, w3, dp, D, H, W, xmap);
-    else PNSFM_LAUNCH((conv3d_dgrad_col_kernel<4, 4>), grid, dim3(256), 0, (hipStream_t)stream, dout, w3, dp, D, H, W, xmap);
+    if (NF == 8) PNSFM_LAUNCH((conv3d_dgrad_col_kernel<8, 4>), grid, dim3(256), 0, (hipStream_t)stream, dout, w3, dp, D, H, W, xmap, rw);
+    else PNSFM_LAUNCH((conv3d_dgrad_col_kernel<4, 4>), grid, dim3(256), 0, (hipStream_t)stream, dout, w3, dp, D, H, W, xmap, rw);
   } else if (col && len == 2) {
-    if (NF == 8) PNSFM_LAUNCH((conv3d_dgrad_col_kernel<8, 2>), grid, dim3(256), 0, (hipStream_t)stream, dout, w3, dp, D, H, W, xmap);
-    else PNSFM_LAUNCH((conv3d_dgrad_col_kernel<4, 2>), grid, dim3(256), 0, (hipStream_t)stream, dout, w3, dp, D, H, W, xmap);
+    if (NF == 8) PNSFM_LAUNCH((conv3d_dgrad_col_kernel<8, 2>), grid, dim3(256), 0, (hipStream_t)stream, dout, w3, dp, D, H, W, xmap, rw);
+    else PNSFM_LAUNCH((conv3d_dgrad_col_kernel<4, 2>), grid, dim3(256), 0, (hipStream_t)stream, dout, w3, dp, D, H, W, xmap, rw);
   }
-  else if (NF == 8) PNSFM_LAUNCH((conv3d_dgrad_kernel<8>), grid, dim3(256), 0, (hipStream_t)stream, dout, w3, dp, D, H, W, len, xmap);
-  else PNSFM_LAUNCH((conv3d_dgrad_kernel<4>), grid, dim3(256), 0, (hipStream_t)stream, dout, w3, dp, D, H, W, len, xmap);
-  return check_launch("conv3d_backward_data");
+  else if (NF == 8) PNSFM_LAUNCH((conv3d_dgrad_kernel<8>), grid, dim3(256), 0, (hipStream_t)stream, dout, w3, dp, D, H, W, len, xmap, rw);
+  else PNSFM_LAUNCH((conv3d_dgrad_kernel<4>), grid, dim3(256), 0, (hipStream_t)stream, dout, w3, dp, D, H, W, len, xmap, rw);
+  return check_launch(what);
 }
 
-int pnsfm_conv3d_backward_weight(const float* p, const float* dout, float* dw3, float* db3, double* ws, int B, int D, int H,
-                                 int W, int NF, void* stream) {
-  if (!nf_ok(NF, "conv3d_backward_weight")) return -1;
+int pnsfm_conv3d_backward_data(const float* dout, const float* w3, float* dp, int B, int D, int H, int W, int NF, void* stream) {
+  return conv3d_backward_data_impl(dout, w3, dp, B, D, H, W, NF, stream, "conv3d_backward_data", C3dRows{H, B, 0, 0});
+}
+
+// PNSFM_CONV3D_WGRAD_RING=0 = round 3's kernel (A/B switch).  (Measured and dropped, profiles/r04_ab_conv3d_wgrad_ring.txt: two
+// features per workgroup with rings of 3 / 6 -- 154 / 209 VGPRs -- are slower, 340 / 375 us over the step's volumes against 323:
+// the per-plane work is shared by half as many FMAs.)
+static int wgrad_ring() { const char* e = getenv("PNSFM_CONV3D_WGRAD_RING"); return (e && e[0] == '0') ? 0 : 34; }
+
+static int conv3d_backward_weight_impl(const float* p, const float* dout, float* dw3, float* db3, int B, int D, int H,
+                                       int W, int NF, void* stream, const char* what, C3dRows rw) {
+  if (!nf_ok(NF, what)) return -1;
   hipStream_t s = (hipStream_t)stream;
-  (void)ws;     // (round 3's zero-filled fp64 atomics target; the per-block partials now live in the stream's scratch buffer)
   // run length along d per thread: as long as possible (amortises the block reduction) while the grid still gives every
   // CU a few blocks
   int len = D;
   while (len > 12 && (long)B * (NF / 4) * ceil_div(D, len) * H * W < 4L * 256 * 256) len = ceil_div(len, 2);
-  // A/B switch: PNSFM_CONV3D_WGRAD_RING=0 = round 3's kernel.  (Measured and dropped, profiles/r04_ab_conv3d_wgrad_ring.txt: two
-  // features per workgroup with rings of 3 / 6 -- 154 / 209 VGPRs -- are slower, 340 / 375 us over the step's volumes against 323:
-  // the per-plane work is shared by half as many FMAs.)
-  const int ring = [] { const char* e = getenv("PNSFM_CONV3D_WGRAD_RING"); return (e && e[0] == '0') ? 0 : 34; }();
+  const int ring = wgrad_ring();
   const int pf = ring / 10, fpb = ring ? ring % 10 : 4;
-  if (ring && (size_t)D * H * W * 4 >= 0x7fffffffull) { set_error("conv3d_backward_weight: feature slab exceeds the 2 GiB buffer window"); return -1; }
+  if (rw.Ho != H && !ring) { set_error("%s: round 3's kernel reads whole frames only", what); return -1; }
+  if (ring && (size_t)D * H * W * 4 >= 0x7fffffffull) { set_error("%s: feature slab exceeds the 2 GiB buffer window", what); return -1; }
   len = ring ? ceil_div(len, pf) * pf : ceil_div(len, 3) * 3;       // whole trips of the unrolled loop
   const dim3 grid(ring ? ceil_div(ceil_div(ceil_div(D, len) * H * W, 62), 4) : ceil_div(ceil_div(D, len) * H * W, 256), NF / fpb, B);
   ScratchLease lease(s, (size_t)grid.x * grid.y * grid.z * fpb * 28 * sizeof(float));
   float* const part = lease.as<float>();
   if (!part) return -1;
   const int xmap = block_map_mode() >= 2 ? 1 : 0;
-  if (ring == 34) PNSFM_LAUNCH((conv3d_wgrad_ring_kernel<3, 4>), grid, dim3(256), 0, s, p, dout, part, D, H, W, len, NF, xmap);
+  if (ring == 34) PNSFM_LAUNCH((conv3d_wgrad_ring_kernel<3, 4>), grid, dim3(256), 0, s, p, dout, part, D, H, W, len, NF, xmap, rw);
   else PNSFM_LAUNCH(conv3d_wgrad_kernel, grid, dim3(256), 0, s, p, dout, part, D, H, W, len, NF);
-  int e = check_launch("conv3d_backward_weight");
+  int e = check_launch(what);
   if (e) return e;
   PNSFM_LAUNCH(conv3d_wgrad_finish_kernel, dim3(NF * 28), dim3(64), 0, s, (const float*)part, dw3, db3, (int)(grid.x * grid.z),
                (int)grid.y, fpb);
   return check_launch("conv3d_backward_weight_finish");
+}
+
+int pnsfm_conv3d_backward_weight(const float* p, const float* dout, float* dw3, float* db3, double* ws, int B, int D, int H,
+                                 int W, int NF, void* stream) {
+  (void)ws;     // (round 3's zero-filled fp64 atomics target; the per-block partials now live in the stream's scratch buffer)
+  return conv3d_backward_weight_impl(p, dout, dw3, db3, B, D, H, W, NF, stream, "conv3d_backward_weight", C3dRows{H, B, 0, 0});
+}
+
+// ---- border strips of the collapsed packing block: the Conv3d of [2B, D, S, w] strips for the 2r = S - 1 rows strip_select keeps
+static bool rows_ok(const char* what, int B2, int S, int Bh) {
+  if (S >= 3 && (S & 1) && Bh >= 0 && Bh <= B2) return true;
+  set_error("%s: strips of S = 2r + 1 >= 3 rows, 0 <= Bh <= B (got S=%d Bh=%d B=%d)", what, S, Bh, B2);
+  return false;
+}
+
+int pnsfm_conv3d_rows_folded(const float* p, const float* out, int W) {
+  return ((pack3d_fold_mask() & PNSFM_FOLD_ROWS) && W % 4 == 0 && (((uintptr_t)p | (uintptr_t)out) & 15) == 0 && wgrad_ring()) ? 1 : 0;
+}
+
+int pnsfm_conv3d_forward_rows(const float* p, const float* w3, const float* b3, float* out, int B, int D, int S, int W, int NF, int Bh,
+                              void* stream) {
+  if (!nf_ok(NF, "conv3d_forward_rows") || !rows_ok("conv3d_forward_rows", B, S, Bh)) return -1;
+  if (W % 4 != 0 || (((uintptr_t)p | (uintptr_t)out) & 15) != 0) {
+    set_error("conv3d_forward_rows: W %% 4 == 0 and 16-byte aligned tensors only (elsewhere: conv3d_forward, then select the rows)");
+    return -1;
+  }
+  const C3dRows rw = {S - 1, Bh, 0, 1};
+  const dim3 gq(ceil_div(D * rw.Ho * (W / 4), 256), 1, B);
+  if (NF == 8) PNSFM_LAUNCH((conv3d_fwd_x4_kernel<8>), gq, dim3(256), 0, (hipStream_t)stream, p, w3, b3, out, D, S, W, rw);
+  else PNSFM_LAUNCH((conv3d_fwd_x4_kernel<4>), gq, dim3(256), 0, (hipStream_t)stream, p, w3, b3, out, D, S, W, rw);
+  return check_launch("conv3d_forward_rows");
+}
+
+int pnsfm_conv3d_backward_data_rows(const float* dout, const float* w3, float* dp, int B, int D, int S, int W, int NF, int Bh, void* stream) {
+  if (!rows_ok("conv3d_backward_data_rows", B, S, Bh)) return -1;
+  return conv3d_backward_data_impl(dout, w3, dp, B, D, S, W, NF, stream, "conv3d_backward_data_rows", C3dRows{S - 1, Bh, 0, 1});
+}
+
+int pnsfm_conv3d_backward_weight_rows(const float* p, const float* dout, float* dw3, float* db3, int B, int D, int S, int W, int NF, int Bh,
+                                      void* stream) {
+  if (!rows_ok("conv3d_backward_weight_rows", B, S, Bh)) return -1;
+  return conv3d_backward_weight_impl(p, dout, dw3, db3, B, D, S, W, NF, stream, "conv3d_backward_weight_rows", C3dRows{S - 1, Bh, 0, 1});
 }
 
 }  // extern "C"

@@ -266,6 +266,11 @@ __device__ __forceinline__ unsigned pnsfm_xcd_logical_block(unsigned p, unsigned
 }
 int block_map_mode();      // api.hip: PNSFM_BLOCK_MAP = 0 (x fastest, round robin) | 1 (operand-sharing order) | 2 (+ XCD ranges, default)
 
+// pack3d.hip: PNSFM_PACK3D_FOLD / pnsfm_set_pack3d_fold -- which launch sequences of the packing / unpacking blocks run folded
+// (default and 1: all; 0: none; an even value is a mask of these bits, for per-kernel A/B runs)
+enum { PNSFM_FOLD_FWD = 2, PNSFM_FOLD_BIAS = 4, PNSFM_FOLD_ROWS = 8, PNSFM_FOLD_ALL = 14 };
+int pack3d_fold_mask();
+
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline int round_up(int a, int b) { return ceil_div(a, b) * b; }
 static inline size_t ceil_div_sz(size_t a, size_t b) { return (a + b - 1) / b; }

@@ -52,6 +52,13 @@ SIGNATURES = {
     "pnsfm_conv3d_forward": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "pnsfm_conv3d_backward_data": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "pnsfm_conv3d_backward_weight": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "pnsfm_set_pack3d_fold": (_i, [_i]),
+    "pnsfm_conv3d_d2s_folded": (_i, [_p, _p, _i, _i]),
+    "pnsfm_conv3d_forward_d2s": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "pnsfm_conv3d_rows_folded": (_i, [_p, _p, _i]),
+    "pnsfm_conv3d_forward_rows": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "pnsfm_conv3d_backward_data_rows": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "pnsfm_conv3d_backward_weight_rows": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "pnsfm_invdepth_act_forward": (_i, [_p, _p, _sz, _f, _p]),
     "pnsfm_invdepth_act_backward": (_i, [_p, _p, _p, _sz, _f, _p]),
     "pnsfm_pose_vec2mat_forward": (_i, [_p, _p, _i, _p]),

@@ -1039,6 +1039,42 @@ def conv3d_1to8(p, w3, b3):
     return Conv3d1to8Fn.apply(p, w3, b3, torch.is_grad_enabled())
 
 
+class Conv3dD2sFn(Function):
+    """depth_to_space(Conv3d1to8Fn(p)) of the unpacking block as one node: [B,D,H,W] -> [B,NF*D/4,2H,2W].  The stencil writes the
+    shuffled layout (csrc/pack3d.hip: conv3d_fwd_x4_d2s_kernel), so the forward shuffle and the [B,NF*D,H,W] tensor do not exist where
+    the fold applies; elsewhere (and with PNSFM_PACK3D_FOLD=0) the entry point runs the two kernels.  Backward is the two nodes':
+    space_to_depth of the gradient, then the stencil's gradients.  Bit-identical to the two nodes either way."""
+
+    @staticmethod
+    def forward(ctx, p, w3, b3, recording=True):
+        p = p.contiguous()
+        y = ops.conv3d_forward_d2s(p, w3.detach().contiguous(), b3.detach().contiguous())
+        ctx.save_for_backward(p, w3)
+        ctx.params = (w3, b3)
+        _WgradStream.note_use(recording, w3, b3)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        p, w3 = ctx.saved_tensors
+        dout = ops.space_to_depth(dy)       # dy is often a channel slice (cat backward): handled without a copy
+        want_w = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        detached = _WgradStream.side_ok(*ctx.params)
+        dp, dw3, db3 = _WgradStream.run_beside(dout, want_w, detached, lambda: ops.conv3d_backward_weight(p, dout),
+                                               (lambda: ops.conv3d_backward_data(dout, w3.detach().contiguous())) if ctx.needs_input_grad[0] else None,
+                                               (p, dout))
+        return dp, dw3, db3, None
+
+
+def conv3d_1to8_d2s(p, w3, b3):
+    """depth_to_space(conv3d_1to8(p, w3, b3))."""
+    if p.dtype == torch.float16:
+        return depth_to_space(conv3d_1to8(p, w3, b3))
+    _h16_input(p, w3)
+    return Conv3dD2sFn.apply(p, w3, b3, torch.is_grad_enabled())
+
+
 class ComposePackWeightFn(Function):
     """W_eff = Conv3d(1->8) composed with the Conv2d that follows it inside PackLayerConv3d (no non-linearity between
     them, reference layers01.py:243-246):
@@ -1243,6 +1279,44 @@ def strip_select(z, B, r, dim):
     if z.dtype == torch.float16:
         return _h16_run(lambda z: _strip_select_fwd(z, B, r, dim, ops.region_ops_h16), z)
     return StripSelectFn.apply(z, B, r, dim)
+
+
+class Conv3dStripRowsFn(Function):
+    """StripSelectFn(Conv3d1to8Fn(p), B, r, 2) as one node: the stencil computes and stores only the 2r rows the selection keeps, and
+    its gradients read the 2r-row gradient at its place in the S-row frame (csrc/pack3d.hip, C3dRows) -- the copy that dropped one
+    row of S, and the copy + zero-fill of its backward, do not exist.  Bit-identical to the two nodes."""
+
+    @staticmethod
+    def forward(ctx, p, w3, b3, B, recording=True):
+        out = ops.conv3d_forward_rows(p, w3.detach().contiguous(), b3.detach().contiguous(), B)
+        ctx.save_for_backward(p, w3)
+        ctx.params, ctx.B = (w3, b3), B
+        _WgradStream.note_use(recording, w3, b3)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        p, w3 = ctx.saved_tensors
+        B, S = ctx.B, p.shape[2]
+        dout = dout.contiguous()
+        want_w = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        detached = _WgradStream.side_ok(*ctx.params)
+        # (p: the side-stream rule goes by the pixel count of the S-row frame, as in Conv3d1to8Fn)
+        dp, dw3, db3 = _WgradStream.run_beside(p, want_w, detached, lambda: ops.conv3d_backward_weight_rows(p, dout, B),
+                                               (lambda: ops.conv3d_backward_data_rows(dout, w3.detach().contiguous(), S, B))
+                                               if ctx.needs_input_grad[0] else None, (p, dout))
+        return dp, dw3, db3, None, None
+
+
+def conv3d_1to8_rows(p, w3, b3, B, r):
+    """strip_select(conv3d_1to8(p, w3, b3), B, r, 2) of the border strips p [2B, D, 2r + 1, w]."""
+    if p.dtype != torch.float16 and p.shape[2] == 2 * r + 1:
+        p = p.contiguous()
+        if ops.conv3d_rows_folded(p):
+            _h16_input(p, w3)
+            return Conv3dStripRowsFn.apply(p, w3, b3, B, torch.is_grad_enabled())
+    return strip_select(conv3d_1to8(p, w3, b3), B, r, 2)
 
 
 class PackBorderPasteFn(Function):

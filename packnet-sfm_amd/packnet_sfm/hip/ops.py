@@ -452,6 +452,65 @@ def conv3d_backward_weight(p, dout):
     return dw3, db3
 
 
+def set_pack3d_fold(on):
+    """include/pnsfm.h, pnsfm_set_pack3d_fold: 0 = the unfolded launch sequences of the packing / unpacking blocks; returns the previous setting."""
+    return _lib.get().pnsfm_set_pack3d_fold(int(on))
+
+
+def conv3d_forward_d2s(p, w3, b3):
+    """depth_to_space(conv3d_forward(p, w3, b3)): p [B,D,H,W] -> [B,NF*D/4,2H,2W], one launch where the fold applies (pnsfm.h)."""
+    _chk(p, w3, b3); _f32(p, w3, b3)
+    B, D, H, W = p.shape
+    nf = _nf_of(w3)
+    lib = _lib.get()
+    y = torch.empty((B, nf * D // 4, 2 * H, 2 * W), dtype=torch.float32, device=p.device)
+    tmp = None if lib.pnsfm_conv3d_d2s_folded(_ptr(p), _ptr(y), D, W) else torch.empty((B, nf * D, H, W), dtype=torch.float32, device=p.device)
+    _lib.check(lib.pnsfm_conv3d_forward_d2s(_ptr(p), _ptr(w3), _ptr(b3), _ptr(tmp), _ptr(y), B, D, H, W, nf, _stream(p)), "conv3d_forward_d2s")
+    return y
+
+
+def conv3d_rows_folded(p):
+    """Does the row window of the three *_rows ops below apply to the strips p [2B,D,S,w] (contiguous)?  pnsfm.h, pnsfm_conv3d_rows_folded
+    (torch's allocations are 16-byte aligned: p stands for the output too)."""
+    S = p.shape[2]
+    return S >= 3 and S % 2 == 1 and p.dtype == torch.float32 and bool(_lib.get().pnsfm_conv3d_rows_folded(_ptr(p), _ptr(p), p.shape[3]))
+
+
+def conv3d_forward_rows(p, w3, b3, Bh):
+    """Border strips p [2B,D,S,w], S = 2r + 1: the Conv3d rows strip_select(., dim=2) keeps, [2B,NF*D,2r,w]."""
+    _chk(p, w3, b3); _f32(p, w3, b3)
+    B, D, S, W = p.shape
+    nf = _nf_of(w3)
+    out = torch.empty((B, nf * D, S - 1, W), dtype=torch.float32, device=p.device)
+    _lib.check(_lib.get().pnsfm_conv3d_forward_rows(_ptr(p), _ptr(w3), _ptr(b3), _ptr(out), B, D, S, W, nf, Bh, _stream(p)),
+               "conv3d_forward_rows")
+    return out
+
+
+def conv3d_backward_data_rows(dout, w3, S, Bh):
+    _chk(dout, w3); _f32(dout, w3)
+    B, DF, Ho, W = dout.shape
+    nf = _nf_of(w3)
+    D = DF // nf
+    assert Ho == S - 1
+    dp = torch.empty((B, D, S, W), dtype=torch.float32, device=dout.device)
+    _lib.check(_lib.get().pnsfm_conv3d_backward_data_rows(_ptr(dout), _ptr(w3), _ptr(dp), B, D, S, W, nf, Bh, _stream(dout)),
+               "conv3d_backward_data_rows")
+    return dp
+
+
+def conv3d_backward_weight_rows(p, dout, Bh):
+    _chk(p, dout); _f32(p, dout)
+    B, D, S, W = p.shape
+    nf = dout.shape[1] // D
+    assert dout.shape[2] == S - 1
+    dw3 = torch.empty((nf, 1, 3, 3, 3), dtype=torch.float32, device=p.device)
+    db3 = torch.empty((nf,), dtype=torch.float32, device=p.device)
+    _lib.check(_lib.get().pnsfm_conv3d_backward_weight_rows(_ptr(p), _ptr(dout), _ptr(dw3), _ptr(db3), B, D, S, W, nf, Bh, _stream(p)),
+               "conv3d_backward_weight_rows")
+    return dw3, db3
+
+
 # ------------------------------------------------------------------- composed packing convolution: bias
 def pack_bias_eff_forward(W2, b2, b3):
     """(bias_eff [C], Ssum [C,d]) of the composed packing convolution: include/pnsfm.h, pnsfm_pack_bias_eff_forward."""

@@ -270,13 +270,13 @@ class PackLayerConv3d(nn.Module):
         rows = bool(self.strip_frame_rows)
         P_main, tb, lr = HF.pack_border_split(P, S, lr_t)
         y = HF.conv2d(P_main, W_eff, bias_eff, self._eff_packed)
-        s_tb = HF.strip_select(HF.conv3d_1to8(tb, W3, b3), B, r, 2)              # [2B, 32C, 2r, w]
+        s_tb = HF.conv3d_1to8_rows(tb, W3, b3, B, r)                             # [2B, 32C, 2r, w]: the rows strip_select keeps
         # [2B, C, r, w] (the frame rows only) or [2B, C, 2r, w]
         o_tb = HF.conv2d_rows(s_tb, W2, b2, base._packed, r) if rows else base(s_tb)
         if lr_t:
             # transposed space: strips [2B, C, S, h], Conv3d taps (dz, dx, dy), Conv2d taps (kx, ky); the result [2B, C, 2r | r, h] is pasted
             # through a transposed view (autograd carries the weight gradients back through the two transpose views)
-            z = HF.strip_select(HF.conv3d_1to8(lr, W3.transpose(3, 4), b3), B, r, 2)
+            z = HF.conv3d_1to8_rows(lr, W3.transpose(3, 4), b3, B, r)
             o_lr = (HF.conv2d_rows(z, W2.transpose(2, 3), b2, self._lr_packed, r) if rows else
                     HF.conv2d(z, W2.transpose(2, 3), b2, self._lr_packed))
         else:
@@ -301,13 +301,12 @@ class UnpackLayerConv3d(nn.Module):
         self.conv3d = nn.Conv3d(1, d, kernel_size=(3, 3, 3), stride=(1, 1, 1), padding=(1, 1, 1))
 
     def forward(self, x):
-        feats = HF.conv3d_1to8(self.conv(x), self.conv3d.weight, self.conv3d.bias)
-        return HF.depth_to_space(feats)
+        return HF.conv3d_1to8_d2s(self.conv(x), self.conv3d.weight, self.conv3d.bias)
 
     def forward_tap(self, x):
         """(unpack(x), x_tap) -- see _HipConv2d.forward_tap (the decoder feature also feeds an InvDepth head)."""
         y, x_tap = self.conv.forward_tap(x)
-        return HF.depth_to_space(HF.conv3d_1to8(y, self.conv3d.weight, self.conv3d.bias)), x_tap
+        return HF.conv3d_1to8_d2s(y, self.conv3d.weight, self.conv3d.bias), x_tap
 
 
 # names of the reference's module of the same path that the hot path does not re-implement (packnet_sfm/_merge.py)
