@@ -5,7 +5,9 @@
 //   `activ(normalize(x_out + shortcut))` of ResidualConv (:61-62,72) and GroupNorm+ReLU of PoseNet's conv_gn
 //   (/root/reference/packnet_sfm/networks/pose/PoseNet.py:28-34).
 // HBM-bound: forward reads x (+res) twice and writes y once (12 or 20 B/element), backward reads dy, x (+res) twice and
-// writes dx once (24 B/element).  Statistics are accumulated in fp64 (sum, sum of squares) so that var = E[x^2]-E[x]^2 is safe.
+// writes dx once (24 B/element).  The variance is safe in both forms: the two-launch kernels accumulate sum and sum of squares in fp64
+// (var = E[x^2] - E[x]^2 loses mean^2 / var of 2^-53), the one-launch forward holds its slab in registers and sums the squares of the
+// CENTRED values (fp32 within a thread's 16 elements, fp64 beyond).
 //
 // Layout of the work (round 2: the round-1 kernels moved 4 bytes per lane per load and gave a workgroup 1024 elements; they
 // ran at 8-26 % of HBM bandwidth and were launch-bound on the 24x80 and smaller maps):
@@ -311,8 +313,10 @@ __global__ void __launch_bounds__(256) gn_bwd_apply_kernel(const float* __restri
 // The channels of a group are consecutive in NCHW, so a slab is ONE contiguous run of n = (C / G) * HW floats.  On the maps of
 // <= 48x160 (every layer of PackNet01 below the 96x320 level and all of PoseNet: ~40 of the step's GroupNorms) a slab is <= 240 KB and
 // the two-launch forms above are latency: 8-15 us per launch for a few MB.  Here a workgroup of 1024 (256) threads owns a slab:
-//   forward:  the slab is read ONCE into registers (NV float4 per thread), summed (fp32 over 16 elements, fp64 beyond), reduced across
-//             the workgroup (shuffles + LDS), normalised, activated and stored -- one launch instead of two;
+//   forward:  the slab is read ONCE into registers (NV float4 per thread), summed (fp32 over 16 elements, fp64 beyond) and reduced across
+//             the workgroup (shuffles + LDS) for the mean, then once more for the squares of v - mean -- raw squares summed in fp32
+//             are rounded at mean^2, which at mean 1, std 0.01 (a near-constant group) is 1e4 times the variance --, normalised,
+//             activated and stored -- one launch instead of two;
 //   backward: blocks [0, B*G*S) own a slab: pass 1 forms A = sum gamma dz and Bq = sum gamma dz xhat of their slab, pass 2 re-reads x and
 //             dy (L2-resident: the same workgroup touched them a moment ago) and writes dx; the blocks behind them own a few CHANNELS
 //             each and form dgamma / dbeta over all samples -- every per-element quantity they need (mean, rstd, gamma, beta, x, dy) is
@@ -321,9 +325,13 @@ __global__ void __launch_bounds__(256) gn_bwd_apply_kernel(const float* __restri
 // maps against 21 / 32 for the two-launch form, rocprofv3), hence (i) the cheap exponentials above, per-channel scale / shift from LDS,
 // incremental channel indices, fp32 partial sums; (ii) S workgroups per slab on the larger slabs: each forms the slab's sums itself
 // (identical order: identical bits) and normalises 1 / S of it -- the S parts of a slab land on one XCD (shared L2).
-// Results agree with the two-launch form to summation order; each form is deterministic.  pnsfm_set_gn_fused(0) / PNSFM_GN_FUSED=0
+// Results agree with the two-launch form to summation order, at any mean / std; each form is deterministic.  pnsfm_set_gn_fused(0) / PNSFM_GN_FUSED=0
 // keeps the two-launch form everywhere.
 constexpr int GNF_MAXCPG = 128;
+// |mean| <= GNF_CENTRE std: raw squares (forward) and v * rstd - mean * rstd (backward) are safe.  Raw squares leave var with about
+// 2^-24 (1 + mean^2 / var) / 3 of error (measured: rstd 1e-6 off at mean 10, std 1), so <= 17 times the error at mean 0 below the
+// threshold -- rstd within 2e-7 -- and mean * rstd is rounded at <= 4; tests/groupnorm_cases.py runs (3.5, 1) and (4.5, 1).
+constexpr float GNF_CENTRE = 4.f;
 
 __device__ __forceinline__ void gnf_block_sum2(double& a, double& b, double (*red)[16]) {
   for (int d = 32; d >= 1; d >>= 1) { a += __shfl_xor(a, d); b += __shfl_xor(b, d); }
@@ -335,6 +343,18 @@ __device__ __forceinline__ void gnf_block_sum2(double& a, double& b, double (*re
   double sa = 0.0, sb = 0.0;
   for (int k = 0; k < nw; ++k) { sa += red[0][k]; sb += red[1][k]; }
   a = sa; b = sb;
+}
+
+__device__ __forceinline__ void gnf_block_sum(double& a, double* red) {
+  for (int d = 32; d >= 1; d >>= 1) a += __shfl_xor(a, d);
+  const int nw = (int)blockDim.x >> 6, w = (int)threadIdx.x >> 6;
+  if (nw == 1) return;
+  __syncthreads();                      // (a previous use of `red` is over)
+  if ((threadIdx.x & 63) == 0) red[w] = a;
+  __syncthreads();
+  double sa = 0.0;
+  for (int k = 0; k < nw; ++k) sa += red[k];
+  a = sa;
 }
 
 // logical (slab, part) of a block: with S parts per slab and a slab count that is a multiple of 8, the parts of a slab are 8 blocks
@@ -393,9 +413,29 @@ __global__ void __launch_bounds__(1024) gn_fused_fwd_kernel(const TS* __restrict
   gnf_block_sum2(s1, s2, red);
   const double n = (double)cpg * (double)HW;
   const double m = s1 / n;
+  const float mu = (float)m;
   double var = s2 / n - m * m;
+  // The squares above are rounded in fp32 at mean^2, not at var: var carries 2^-24 (1 + mean^2 / var) of error.  Where the mean is
+  // more than GNF_CENTRE standard deviations from 0 (at mean 100, std 1 rstd was 1e-4 off; a near-constant group is mean 1, std 0.01)
+  // the slab, still in registers, is summed again as squares of the CENTRED values and reduced once more.  Every thread holds the
+  // same m and var, so the branch and its barriers are uniform; elsewhere the launch costs and computes what it did without it.
+  if ((double)(GNF_CENTRE * GNF_CENTRE) * var < m * m) {
+    double c2 = 0.0;
+    float f2 = 0.f;
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+      if (tid + k * T < n4) {                      // (a padding lane holds 0, not mu)
+        const float dx = v[k].x - mu, dy = v[k].y - mu, dz = v[k].z - mu, dw = v[k].w - mu;
+        f2 += fmaf(dx, dx, dy * dy) + fmaf(dz, dz, dw * dw);
+      }
+      if ((k & 3) == 3 || k == NV - 1) { c2 += (double)f2; f2 = 0.f; }
+    }
+    gnf_block_sum(c2, red[0]);
+    // sum (v - mu)^2 = sum (v - m)^2 + n (m - mu)^2: the rounding of the mean to fp32 is taken out again
+    var = c2 / n - (m - (double)mu) * (m - (double)mu);
+  }
   if (var < 0.0) var = 0.0;
-  const float mu = (float)m, rs = (float)(1.0 / sqrt(var + (double)eps));
+  const float rs = (float)(1.0 / sqrt(var + (double)eps));
   if (tid == 0 && part == 0) { mean_out[bg] = mu; rstd_out[bg] = rs; }
   if (tid < cpg) {
     const float sc = rs * pnsfm_ldf(gamma + gi * cpg + tid);
@@ -442,8 +482,11 @@ __global__ void __launch_bounds__(1024) gn_fused_bwd_kernel(const float* __restr
     const float4* xp = reinterpret_cast<const float4*>(x) + base4;
     const float4* rp = res ? reinterpret_cast<const float4*>(res) + base4 : nullptr;
     const float4* dp = reinterpret_cast<const float4*>(dy) + base4;
+    // xhat = (v - sub) * rs + nmr: v * rs - mu * rs (sub = 0) where the mean is within GNF_CENTRE standard deviations of 0, and
+    // (v - mu) * rs (nmr = 0), as in the two-launch form, beyond: there mu * rs is rounded at |mean| / std and the difference cancels
     const float mu = mean[bg], rs = rstd[bg];
-    const float nmr = -mu * rs;                    // xhat = v * rs + nmr
+    const bool centre = fabsf(mu) * rs > GNF_CENTRE;
+    const float sub = centre ? mu : 0.f, nmr = centre ? 0.f : -mu * rs;
     if (tid < cpg) { lga[tid] = gamma[gi * cpg + tid]; lbe[tid] = beta[gi * cpg + tid]; }
     __syncthreads();
     double A = 0.0, Bq = 0.0;
@@ -473,7 +516,7 @@ __global__ void __launch_bounds__(1024) gn_fused_bwd_kernel(const float* __restr
             float a1 = 0.f, a2 = 0.f;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-              const float xh = fmaf(vv[k], rs, nmr);
+              const float xh = fmaf(vv[k] - sub, rs, nmr);
               const float dz = dd[k] * act_grad(fmaf(xh, ga, be), act);
               a1 += dz;
               a2 = fmaf(dz, xh, a2);
@@ -521,7 +564,7 @@ __global__ void __launch_bounds__(1024) gn_fused_bwd_kernel(const float* __restr
           float oo[4];
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
-            const float xh = fmaf(vv[k], rs, nmr);
+            const float xh = fmaf(vv[k] - sub, rs, nmr);
             const float dz = dd[k] * act_grad(fmaf(xh, ga, be), act);
             oo[k] = rs * (dz * ga - mA - xh * mB);
           }
@@ -543,7 +586,7 @@ __global__ void __launch_bounds__(1024) gn_fused_bwd_kernel(const float* __restr
   const int per = B * HW4;
   for (int e0 = l; e0 < per; e0 += 4 * TPC) {
     float4 v[4], d[4];
-    float rs[4], nmr[4];
+    float rs[4], sub[4], nmr[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int e = e0 + u * TPC;
@@ -554,7 +597,10 @@ __global__ void __launch_bounds__(1024) gn_fused_bwd_kernel(const float* __restr
         d[u] = reinterpret_cast<const float4*>(dy)[o4];
         if (res) { const float4 q = reinterpret_cast<const float4*>(res)[o4]; v[u].x += q.x; v[u].y += q.y; v[u].z += q.z; v[u].w += q.w; }
         rs[u] = rstd[b * G + gi];
-        nmr[u] = -mean[b * G + gi] * rs[u];
+        const float mu = mean[b * G + gi];
+        const bool centre = fabsf(mu) * rs[u] > GNF_CENTRE;           // (as in the slab blocks)
+        sub[u] = centre ? mu : 0.f;
+        nmr[u] = centre ? 0.f : -mu * rs[u];
       }
     }
     float f1 = 0.f, f2 = 0.f;
@@ -565,7 +611,7 @@ __global__ void __launch_bounds__(1024) gn_fused_bwd_kernel(const float* __restr
         const float vv[4] = {v[u].x, v[u].y, v[u].z, v[u].w}, dd[4] = {d[u].x, d[u].y, d[u].z, d[u].w};
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-          const float xh = fmaf(vv[k], rs[u], nmr[u]);
+          const float xh = fmaf(vv[k] - sub[u], rs[u], nmr[u]);
           const float dz = dd[k] * act_grad(fmaf(xh, ga, be), act);
           f1 += dz;
           f2 = fmaf(dz, xh, f2);

@@ -1086,9 +1086,10 @@ def test_conv2d_bx3_edge_inputs_emulated(emulated_kernels):
 @pytest.mark.parametrize('act,use_res', [(1, False), (2, True), (0, True)])
 def test_groupnorm_two_launch_form(emulated_kernels, shape, act, use_res):
     """GroupNorm(16) + activation (+ residual) forward AND backward vs torch on shapes that exercise every work split of
-    csrc/groupnorm.hip: one lane per row with surplus rows in the workgroup (2x4 maps), scalar loads (5x7), rows cut into chunks
-    (64x80), rows of 128/256 lanes (barrier-based row sums), many channels per group -- since round 3 the apply kernels add the
-    partial slots themselves (no gn_finish / gn_bwd_group launches)."""
+    csrc/groupnorm.hip: one lane per row with surplus rows in the workgroup (2x4 maps), scalar loads (5x7), rows of 128/256 lanes
+    (barrier-based row sums), many channels per group -- since round 3 the apply kernels add the partial slots themselves (no
+    gn_finish / gn_bwd_group launches).  No shape here cuts a row into chunks (gn_geom keeps a row whole below 8192 elements with
+    vector loads, 2048 with scalar ones; 64x80 is 5120): tests/groupnorm_cases.py has those, (1,16,45,47) and (1,16,3,2732)."""
     from packnet_sfm.hip import _lib
     _lib.get().pnsfm_set_gn_fused(0)          # the two-launch kernels (the large maps' path), also on the slabs the one-launch form takes
     P.case_groupnorm('cpu', shape, act, use_res)
