@@ -314,6 +314,50 @@ int pnsfm_conv3d_backward_data_rows(const float* dout, const float* w3, float* d
 int pnsfm_conv3d_backward_weight_rows(const float* p, const float* dout, float* dw3, float* db3, int B, int D, int S, int W, int NF,
                                       int Bh, void* stream);
 
+/* Kernel composition of the collapsed packing block on the Conv2d weight itself: dout [B, NF*D, Hd, Wd] stands in the
+ * middle of an (Hd + 2) x (Wd + 2) frame whose one-tap outer ring is zero and is not stored; dp / p are [B, D, Hd + 2, Wd + 2].
+ * backward_data_ring = pnsfm_conv3d_backward_data on the zero-padded dout, backward_weight_ring = pnsfm_conv3d_backward_weight on it
+ * (the default weight-gradient kernel only), bit for bit: the ring is read as zero by the kernels' window check. */
+int pnsfm_conv3d_backward_data_ring(const float* dout, const float* w3, float* dp, int B, int D, int Hd, int Wd, int NF, void* stream);
+int pnsfm_conv3d_backward_weight_ring(const float* p, const float* dout, float* dw3, float* db3, int B, int D, int Hd, int Wd, int NF,
+                                      int epi /* PNSFM_WGRAD_EPI_* */, void* stream);
+
+/* Transposed taps read in place, and gradients that meet inside the kernels (the weight path of the collapsed packing block, DESIGN.md
+ * 3b).  tapT != 0: tap (dz, dy, dx) of the stencil is w3[f][dz][dx][dy] -- the entry point computes what its plain form computes on
+ * w3.transpose(3, 4).contiguous(), bit for bit, without that copy.  epi (weight gradients) is a mask:
+ *   PNSFM_WGRAD_EPI_ADD  (1)  the finished sums are added to what dw / db hold, last (dst = dst + sum: the bits of an elementwise add
+ *                             of the plain result), instead of being stored;
+ *   PNSFM_WGRAD_EPI_TAPT (2)  dw leaves with the tap swap undone: the gradient of a layer that convolved with transposed taps, in the
+ *                             weight's own layout (the bias gradient has no taps).
+ * forward_t / forward_rows_t need W % 4 == 0 and 16-byte aligned p / out.  db3 of the three *_epi / _ring weight gradients may be
+ * NULL: the bias gradient is then not stored (the kernel composition has no use for it). */
+#ifndef PNSFM_WGRAD_EPI_ADD
+#define PNSFM_WGRAD_EPI_ADD 1
+#define PNSFM_WGRAD_EPI_TAPT 2
+#endif
+int pnsfm_conv3d_forward_t(const float* p, const float* w3, const float* b3, float* out, int B, int D, int H, int W, int NF, int tapT,
+                           void* stream);
+int pnsfm_conv3d_backward_data_t(const float* dout, const float* w3, float* dp, int B, int D, int H, int W, int NF, int tapT, void* stream);
+int pnsfm_conv3d_backward_weight_epi(const float* p, const float* dout, float* dw3, float* db3, int B, int D, int H, int W, int NF, int epi,
+                                     void* stream);
+int pnsfm_conv3d_forward_rows_t(const float* p, const float* w3, const float* b3, float* out, int B, int D, int S, int W, int NF, int Bh,
+                                int tapT, void* stream);
+int pnsfm_conv3d_backward_data_rows_t(const float* dout, const float* w3, float* dp, int B, int D, int S, int W, int NF, int Bh, int tapT,
+                                      void* stream);
+int pnsfm_conv3d_backward_weight_rows_epi(const float* p, const float* dout, float* dw3, float* db3, int B, int D, int S, int W, int NF,
+                                          int Bh, int epi, void* stream);
+/* The Conv2d side.  pack_weights_t / pack_item_fill_t: the packed images of w with its (ky, kx) taps transposed, read in place
+ * (tap (ky, kx) of the images is w[co][ci][kx][ky]); split-bf16 layers only (pnsfm_conv2d_pack_tapt_supported == 1).
+ * backward_weight_epi: pnsfm_conv2d_backward_weight (Hi == H, yshift == shift_from_b == 0) or pnsfm_conv2d_backward_weight_rows with
+ * an epilogue; PNSFM_WGRAD_EPI_TAPT stores dw[co][ci][kx][ky] for tap (ky, kx).  The epilogue runs in the second stage of the
+ * split-bf16 kernels (a single pixel split then writes one partial tensor); other kernels take a pass of its own after them. */
+int pnsfm_conv2d_pack_tapt_supported(int Cin, int Cout, int ks);
+int pnsfm_conv2d_pack_weights_t(const float* w, float* wp_fwd, float* wp_bwd, int Cin, int Cout, int ks, int tapT, void* stream);
+int pnsfm_conv2d_pack_item_fill_t(void* item_host, const float* w, float* wp_fwd, float* wp_bwd, int Cin, int Cout, int ks,
+                                  int first_block, int tapT);
+int pnsfm_conv2d_backward_weight_epi(const float* x, const float* dy, float* dw, float* dbias, int B, int Cin, int Cout, int H, int Hi,
+                                     int W, int ks, int yshift, int shift_from_b, int epi, void* stream);
+
 /* ---- InvDepth activation: y = sigmoid(x) / min_depth  (layers01.py:119-122) --------------- */
 int pnsfm_invdepth_act_forward(const float* x, float* y, size_t n, float min_depth, void* stream);
 int pnsfm_invdepth_act_backward(const float* dy, const float* y, float* dx, size_t n, float min_depth,
@@ -459,6 +503,10 @@ int pnsfm_pack_bias_eff_forward(const float* W2, const float* b2, const float* b
                                 int blk, void* stream);
 int pnsfm_pack_bias_eff_backward(const float* g, const float* Ssum, const float* b3, const float* dWeff_full, float* db3, float* dW2,
                                  int C, int d, int D, int k, void* stream);
+/* ... adding into its destinations: db3 = db3 + sum, dW2 = dW2 + (crop + g*b3), and db2[co] = db2[co] + g[co] (db2 nullable; needs
+ * db3) -- the composition's gradients joining those the border strips left there. */
+int pnsfm_pack_bias_eff_backward_add(const float* g, const float* Ssum, const float* b3, const float* dWeff_full, float* db3, float* dW2,
+                                     float* db2, int C, int d, int D, int k, void* stream);
 
 /* ---- Adam over a flat fp32 parameter buffer (torch.optim.Adam semantics, no amsgrad) -------
  * replaces the optimizer.step() of models/model_wrapper.py:128-149 / trainers/horovod_trainer.py:93

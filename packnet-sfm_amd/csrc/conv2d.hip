@@ -1981,7 +1981,7 @@ size_t pnsfm_conv2d_packed_elems_bwd(int Cin, int Cout, int ks) {
   return conv_bx3_supported(Cout, ks) ? n + n / 2 : n;
 }
 
-int pnsfm_conv2d_pack_weights(const float* w, float* wp_fwd, float* wp_bwd, int Cin, int Cout, int ks, void* stream) {
+static int pack_weights_impl(const float* w, float* wp_fwd, float* wp_bwd, int Cin, int Cout, int ks, int tapT, void* stream) {
   if (ks != 1 && ks != 3 && ks != 5 && ks != 7) { set_error("pack_weights: unsupported kernel size %d", ks); return -1; }
   hipStream_t s = (hipStream_t)stream;
   const int KK = ks * ks;
@@ -1989,6 +1989,10 @@ int pnsfm_conv2d_pack_weights(const float* w, float* wp_fwd, float* wp_bwd, int 
   const int KPf = conv_pack_KP(Cin), MPf = conv_pack_MP(Cout), KPb = conv_pack_KP(Cout), MPb = conv_pack_MP(Cin);
   // the layout of each direction follows the kernel that will read it (launch_conv takes the same decision)
   const bool bxf = wp_fwd && conv_use_bx3(Cin, ks), bxb = wp_bwd && conv_use_bx3(Cout, ks);
+  if (tapT && ((wp_fwd && !bxf) || (wp_bwd && !bxb))) {
+    set_error("pack_weights: transposed taps are read in place by the split-bf16 packer only (pnsfm_conv2d_pack_tapt_supported)");
+    return -1;
+  }
   float* const f32f = bxf ? nullptr : wp_fwd;
   float* const f32b = bxb ? nullptr : wp_bwd;
   if (f32f || f32b) {
@@ -2002,18 +2006,45 @@ int pnsfm_conv2d_pack_weights(const float* w, float* wp_fwd, float* wp_bwd, int 
     const int nf = bxf ? (MPf / 32) * nchF : 0, nb = bxb ? (MPb / 32) * nchB : 0;
     unsigned char* const pf = reinterpret_cast<unsigned char*>(bxf ? wp_fwd : nullptr);
     unsigned char* const pb = reinterpret_cast<unsigned char*>(bxb ? wp_bwd : nullptr);
-    if (ks == 1) PNSFM_LAUNCH((pack_bx3_kernel<1>), dim3(nf + nb), dim3(256), 0, s, w, pf, pb, Cin, Cout, nchF, nchB, nf);
-    else if (ks == 3) PNSFM_LAUNCH((pack_bx3_kernel<3>), dim3(nf + nb), dim3(256), 0, s, w, pf, pb, Cin, Cout, nchF, nchB, nf);
-    else if (ks == 5) PNSFM_LAUNCH((pack_bx3_kernel<5>), dim3(nf + nb), dim3(256), 0, s, w, pf, pb, Cin, Cout, nchF, nchB, nf);
-    else PNSFM_LAUNCH((pack_bx3_kernel<7>), dim3(nf + nb), dim3(256), 0, s, w, pf, pb, Cin, Cout, nchF, nchB, nf);
+    if (ks == 1) PNSFM_LAUNCH((pack_bx3_kernel<1>), dim3(nf + nb), dim3(256), 0, s, w, pf, pb, Cin, Cout, nchF, nchB, nf, tapT);
+    else if (ks == 3) PNSFM_LAUNCH((pack_bx3_kernel<3>), dim3(nf + nb), dim3(256), 0, s, w, pf, pb, Cin, Cout, nchF, nchB, nf, tapT);
+    else if (ks == 5) PNSFM_LAUNCH((pack_bx3_kernel<5>), dim3(nf + nb), dim3(256), 0, s, w, pf, pb, Cin, Cout, nchF, nchB, nf, tapT);
+    else PNSFM_LAUNCH((pack_bx3_kernel<7>), dim3(nf + nb), dim3(256), 0, s, w, pf, pb, Cin, Cout, nchF, nchB, nf, tapT);
   }
   return check_launch("pack_weights");
 }
 
+int pnsfm_conv2d_pack_weights(const float* w, float* wp_fwd, float* wp_bwd, int Cin, int Cout, int ks, void* stream) {
+  return pack_weights_impl(w, wp_fwd, wp_bwd, Cin, Cout, ks, 0, stream);
+}
+
+// 1 when both packed images of this layer take the split-bf16 layout under the arithmetic mode in force: the layers whose transposed
+// taps the packers read in place (pnsfm_conv2d_pack_weights_t, pnsfm_conv2d_pack_item_fill_t)
+int pnsfm_conv2d_pack_tapt_supported(int Cin, int Cout, int ks) {
+  return ((ks == 1 || ks == 3 || ks == 5 || ks == 7) && conv_use_bx3(Cin, ks) && conv_use_bx3(Cout, ks)) ? 1 : 0;
+}
+
+int pnsfm_conv2d_pack_weights_t(const float* w, float* wp_fwd, float* wp_bwd, int Cin, int Cout, int ks, int tapT, void* stream) {
+  return pack_weights_impl(w, wp_fwd, wp_bwd, Cin, Cout, ks, tapT ? 1 : 0, stream);
+}
+
 size_t pnsfm_conv2d_pack_item_bytes(void) { return sizeof(PackItem); }
+
+static int pack_item_fill_impl(void* item_host, const float* w, float* wp_fwd, float* wp_bwd, int Cin, int Cout, int ks, int first_block,
+                               int tapT);
 
 int pnsfm_conv2d_pack_item_fill(void* item_host, const float* w, float* wp_fwd, float* wp_bwd, int Cin, int Cout, int ks,
                                 int first_block) {
+  return pack_item_fill_impl(item_host, w, wp_fwd, wp_bwd, Cin, Cout, ks, first_block, 0);
+}
+
+int pnsfm_conv2d_pack_item_fill_t(void* item_host, const float* w, float* wp_fwd, float* wp_bwd, int Cin, int Cout, int ks,
+                                  int first_block, int tapT) {
+  return pack_item_fill_impl(item_host, w, wp_fwd, wp_bwd, Cin, Cout, ks, first_block, tapT ? 1 : 0);
+}
+
+static int pack_item_fill_impl(void* item_host, const float* w, float* wp_fwd, float* wp_bwd, int Cin, int Cout, int ks, int first_block,
+                               int tapT) {
   if (ks != 1 && ks != 3 && ks != 5 && ks != 7) { set_error("pack_item_fill: unsupported kernel size %d", ks); return -1; }
   if (!item_host || !w || !wp_fwd || !wp_bwd) { set_error("pack_item_fill: null pointer"); return -1; }
   // only weights whose BOTH directions run the split-bf16 kernels go through the table (the others keep the per-layer call)
@@ -2028,6 +2059,7 @@ int pnsfm_conv2d_pack_item_fill(void* item_host, const float* w, float* wp_fwd, 
   it.nf = (MPf / 32) * it.nchF;
   it.blk0 = first_block;
   it.nblk = it.nf + (MPb / 32) * it.nchB;
+  it.tapT = tapT;
   memcpy(item_host, &it, sizeof(it));
   return it.nblk;
 }
@@ -2132,7 +2164,25 @@ struct WgradPlan {
   size_t smem;
   int MT, n_tiles, m_tiles;
   WgradDecision run;
+  int epi;                         // PNSFM_WGRAD_EPI_*: the second stage of the split-bf16 / nine-taps kernels; other kernels: wgrad_merge_kernel
 };
+
+// dst[co][ci][tap'] = (add ? dst : 0) + src[co][ci][tap] -- the epilogue (pnsfm_common.h: PNSFM_WGRAD_EPI_*) of a launch whose kernel
+// has no second stage that could take it (the generic and the tap-major kernel: shapes off the split-bf16 path): the gradient is
+// written to a temporary first.  n = Cout * Cin * KK weight elements, then Cout bias elements (nb = 0: none).
+__global__ void __launch_bounds__(256) wgrad_merge_kernel(const float* __restrict__ src, float* __restrict__ dst, const float* __restrict__ bsrc,
+                                                          float* __restrict__ bdst, size_t n, int nb, int KS, int epi) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const int KK = KS * KS;
+  if (i < n) {
+    const int tap = (int)(i % KK);
+    const size_t j = (epi & PNSFM_WGRAD_EPI_TAPT) ? i - tap + (tap % KS) * KS + tap / KS : i;
+    dst[j] = (epi & PNSFM_WGRAD_EPI_ADD) ? dst[j] + src[i] : src[i];
+  } else if (i - n < (size_t)nb) {
+    const size_t c = i - n;
+    bdst[c] = (epi & PNSFM_WGRAD_EPI_ADD) ? bdst[c] + bsrc[c] : bsrc[c];
+  }
+}
 
 // (a) shape facts and the generic kernel's geometry.  H, W: size of dY (the conv OUTPUT); x is [B, Cin, Hi, Wi] with Hi = H, Wi = W
 // when S == 1
@@ -2306,8 +2356,30 @@ static int enqueue_wgrad_generic(const WgradPlan& p, int split) {
 static int wgrad_enqueue(const WgradPlan& p) {
   const WgradDecision& d = p.run;
   switch (d.kernel) {
-    case 3: return enqueue_wgrad4(p.x, p.dy, p.dw, p.dbias, p.B, p.Cin, p.Cout, p.H0, p.W0, d.split, d.cfg4(), p.s, p.ms, p.rows);
-    case 2: return enqueue_wgrad3(p.x, p.dy, p.dw, p.dbias, p.B, p.Cin, p.Cout, p.H3, p.W3, p.ks, d.split, d.NT, d.wm, p.s, p.ms, p.rows);
+    case 3: return enqueue_wgrad4(p.x, p.dy, p.dw, p.dbias, p.B, p.Cin, p.Cout, p.H0, p.W0, d.split, d.cfg4(), p.s, p.ms, p.rows, p.epi);
+    case 2: return enqueue_wgrad3(p.x, p.dy, p.dw, p.dbias, p.B, p.Cin, p.Cout, p.H3, p.W3, p.ks, d.split, d.NT, d.wm, p.s, p.ms, p.rows, p.epi);
+    default: break;
+  }
+  if (p.epi) {      // a kernel without a second stage: plain gradient into a temporary, then the epilogue as a pass of its own
+    const size_t n = (size_t)p.Cout * p.Cin * p.ks * p.ks;
+    const int nb = p.dbias ? p.Cout : 0;
+    void* tmp = nullptr;
+    if (hipMallocAsync(&tmp, (n + nb) * sizeof(float), p.s) != hipSuccess || !tmp) { set_error("conv2d_backward_weight: no memory for the epilogue's temporary"); return -1; }
+    WgradPlan q = p;
+    q.epi = 0;
+    q.dw = static_cast<float*>(tmp);
+    q.dbias = nb ? q.dw + n : nullptr;
+    q.a.dw = q.dw; q.a.dbias = q.dbias;      // (the generic kernel's argument block carries the destination too)
+    int rc = wgrad_enqueue(q);
+    if (!rc) {
+      PNSFM_LAUNCH(wgrad_merge_kernel, dim3((unsigned)ceil_div_sz(n + nb, 256)), dim3(256), 0, p.s, (const float*)q.dw, p.dw, (const float*)q.dbias,
+                   p.dbias, n, nb, p.ks, p.epi);
+      rc = check_launch("conv2d_backward_weight (epilogue)");
+    }
+    (void)hipFreeAsync(tmp, p.s);
+    return rc;
+  }
+  switch (d.kernel) {
     case 1: return enqueue_wgrad2(p.x, p.dy, p.dw, p.dbias, p.B, p.Cin, p.Cout, p.H0, p.W0, p.ks, d.split, p.s);
     default: return enqueue_wgrad_generic(p, d.split);
   }
@@ -2396,10 +2468,11 @@ static std::array<int, 7> wgrad_tune_key(const WgradPlan& p) {
 }
 
 static int wgrad_impl(const float* x, const float* dy, float* dw, float* dbias, int B, int Cin, int Cout, int H, int W,
-                      int ks, int S, int Hi, int Wi, void* stream, const ConvSrc* ms = nullptr, const ConvRows* rows = nullptr) {
+                      int ks, int S, int Hi, int Wi, void* stream, const ConvSrc* ms = nullptr, const ConvRows* rows = nullptr, int epi = 0) {
+  if (epi & ~(PNSFM_WGRAD_EPI_ADD | PNSFM_WGRAD_EPI_TAPT)) { set_error("backward_weight: unknown epilogue flags %d", epi); return -1; }
   WgradPlan p;
   p.x = x; p.dy = dy; p.dw = dw; p.dbias = dbias; p.ms = ms; p.rows = rows; p.s = (hipStream_t)stream;
-  p.B = B; p.Cin = Cin; p.Cout = Cout; p.ks = ks; p.S = S;
+  p.B = B; p.Cin = Cin; p.Cout = Cout; p.ks = ks; p.S = S; p.epi = epi;
   if (wgrad_plan_init(p, H, W, Hi, Wi)) return -1;
   p.run = wgrad_default(p);
   {
@@ -2426,7 +2499,19 @@ static int wgrad_impl(const float* x, const float* dy, float* dw, float* dbias, 
 #ifndef PNSFM_EMU
     // (first seen inside a hipGraph capture: keep the analytic split -- timing would synchronise)
     if (!dec && tune && !stream_capturing(p.s)) {
-      dec = &g_tuned.emplace(key, wgrad_tune(p, key).encode()).first->second;
+      // (the candidates are plain launches: under an epilogue they write a temporary, never the destination that is being added to)
+      WgradPlan t = p;
+      void* tmp = nullptr;
+      if (p.epi) {
+        const size_t n = (size_t)Cout * Cin * ks * ks;
+        if (hipMalloc(&tmp, (n + Cout) * sizeof(float)) != hipSuccess || !tmp) { set_error("backward_weight: no memory to tune under an epilogue"); return -1; }
+        t.epi = 0;
+        t.dw = static_cast<float*>(tmp);
+        t.dbias = dbias ? t.dw + n : nullptr;
+        t.a.dw = t.dw; t.a.dbias = t.dbias;
+      }
+      dec = &g_tuned.emplace(key, wgrad_tune(t, key).encode()).first->second;
+      if (tmp) (void)hipFree(tmp);
       tune_db_append(key, *dec);
     }
 #endif
@@ -2499,6 +2584,16 @@ int pnsfm_conv2d_backward_weight_rows(const float* x, const float* dy, float* dw
   if (!conv_rows_ok("conv2d_backward_weight_rows", B, H, Hi, shift_from_b)) return -1;
   const ConvRows rows = {Hi, yshift, shift_from_b};
   return wgrad_impl(x, dy, dw, dbias, B, Cin, Cout, H, W, ks, 1, Hi, W, stream, nullptr, &rows);
+}
+
+// The two entry points above with an epilogue (PNSFM_WGRAD_EPI_*): the gradient is added to what dw / dbias hold, and / or dw leaves
+// with its taps swapped back.  Hi == H and yshift == shift_from_b == 0: no row window.
+int pnsfm_conv2d_backward_weight_epi(const float* x, const float* dy, float* dw, float* dbias, int B, int Cin, int Cout, int H, int Hi, int W,
+                                     int ks, int yshift, int shift_from_b, int epi, void* stream) {
+  if (Hi == H && yshift == 0 && shift_from_b == 0) return wgrad_impl(x, dy, dw, dbias, B, Cin, Cout, H, W, ks, 1, H, W, stream, nullptr, nullptr, epi);
+  if (!conv_rows_ok("conv2d_backward_weight_epi", B, H, Hi, shift_from_b)) return -1;
+  const ConvRows rows = {Hi, yshift, shift_from_b};
+  return wgrad_impl(x, dy, dw, dbias, B, Cin, Cout, H, W, ks, 1, Hi, W, stream, nullptr, &rows, epi);
 }
 
 int pnsfm_set_autotune(int on) {

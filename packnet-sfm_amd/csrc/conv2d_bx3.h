@@ -387,10 +387,15 @@ __global__ void __launch_bounds__(256, OCC) conv2d_bx3_kernel(ConvArgs a) {
 // One block per (32-row m-block, 16-channel chunk); taps go through LDS -- all 9 of a 3x3 at once, one kernel row at a time for
 // 5x5 / 7x7 -- so that global reads are runs of (channel, tap) and every output tap is written as one contiguous 3072-byte
 // slab.  KS is a template parameter: the index arithmetic of the copy loops divides by compile-time constants only.
+// tapT: the images are those of w with its (ky, kx) taps transposed -- tap (ky, kx) of the images is w[.][.][kx][ky] -- read in place
+// (the column strips of the collapsed packing block convolve in transposed space; no transposed copy of the weight is made).
+template <int KS>
+__device__ __forceinline__ int pack_src_tap(int t, bool tapT) { return tapT ? (t % KS) * KS + t / KS : t; }
+
 template <int KS>
 __device__ __forceinline__ void pack_bx3_block(float (*tile)[16][33], const float* __restrict__ w, unsigned char* __restrict__ wp_fwd,
                                                unsigned char* __restrict__ wp_bwd, int Cin, int Cout, int nchF, int nchB, int nf,
-                                               int blk) {
+                                               int blk, bool tapT = false) {
   constexpr int KK = KS * KS, TSEG = (KS == 3) ? 9 : KS;
   const bool fwd = blk < nf;
   if (!fwd) blk -= nf;
@@ -405,7 +410,7 @@ __device__ __forceinline__ void pack_bx3_block(float (*tile)[16][33], const floa
       for (int e = threadIdx.x; e < 32 * 16 * TSEG; e += 256) {
         const int m = e / (16 * TSEG), r = e - m * (16 * TSEG), k = r / TSEG, tt = r - k * TSEG;
         float v = 0.f;
-        if (m0 + m < Mn && k0 + k < Kn) v = w[((size_t)(m0 + m) * Cin + k0 + k) * KK + t0 + tt];
+        if (m0 + m < Mn && k0 + k < Kn) v = w[((size_t)(m0 + m) * Cin + k0 + k) * KK + pack_src_tap<KS>(t0 + tt, tapT)];
         tile[tt][k][m] = v;
       }
     } else {
@@ -413,7 +418,7 @@ __device__ __forceinline__ void pack_bx3_block(float (*tile)[16][33], const floa
       for (int e = threadIdx.x; e < 16 * 32 * TSEG; e += 256) {
         const int k = e / (32 * TSEG), r = e - k * (32 * TSEG), m = r / TSEG, tt = r - m * TSEG;
         float v = 0.f;
-        if (m0 + m < Mn && k0 + k < Kn) v = w[((size_t)(k0 + k) * Cin + m0 + m) * KK + (KK - 1 - (t0 + tt))];
+        if (m0 + m < Mn && k0 + k < Kn) v = w[((size_t)(k0 + k) * Cin + m0 + m) * KK + pack_src_tap<KS>(KK - 1 - (t0 + tt), tapT)];
         tile[tt][k][m] = v;
       }
     }
@@ -437,9 +442,9 @@ __device__ __forceinline__ void pack_bx3_block(float (*tile)[16][33], const floa
 template <int KS>
 __global__ void __launch_bounds__(256) pack_bx3_kernel(const float* __restrict__ w, unsigned char* __restrict__ wp_fwd,
                                                        unsigned char* __restrict__ wp_bwd, int Cin, int Cout, int nchF,
-                                                       int nchB, int nf) {
+                                                       int nchB, int nf, int tapT) {
   __shared__ float tile[(KS == 3) ? 9 : KS][16][33];
-  pack_bx3_block<KS>(tile, w, wp_fwd, wp_bwd, Cin, Cout, nchF, nchB, nf, (int)blockIdx.x);
+  pack_bx3_block<KS>(tile, w, wp_fwd, wp_bwd, Cin, Cout, nchF, nchB, nf, (int)blockIdx.x, tapT != 0);
 }
 
 // One launch for MANY weights (every conv layer of a model right after the optimizer step): a device-resident table of
@@ -450,6 +455,7 @@ struct PackItem {
   unsigned char* pf;
   unsigned char* pb;
   int Cin, Cout, ks, nchF, nchB, nf, blk0, nblk;
+  int tapT;            // pack_bx3_block: the images of the tap-transposed weight
 };
 __global__ void __launch_bounds__(256) pack_bx3_table_kernel(const PackItem* __restrict__ tab, int n) {
   __shared__ float tile[9][16][33];
@@ -461,10 +467,10 @@ __global__ void __launch_bounds__(256) pack_bx3_table_kernel(const PackItem* __r
   const PackItem it = tab[lo];
   const int blk = (int)blockIdx.x - it.blk0;
   if (blk >= it.nblk) return;
-  if (it.ks == 3) pack_bx3_block<3>(tile, it.w, it.pf, it.pb, it.Cin, it.Cout, it.nchF, it.nchB, it.nf, blk);
-  else if (it.ks == 1) pack_bx3_block<1>(tile, it.w, it.pf, it.pb, it.Cin, it.Cout, it.nchF, it.nchB, it.nf, blk);
-  else if (it.ks == 5) pack_bx3_block<5>(tile, it.w, it.pf, it.pb, it.Cin, it.Cout, it.nchF, it.nchB, it.nf, blk);
-  else pack_bx3_block<7>(tile, it.w, it.pf, it.pb, it.Cin, it.Cout, it.nchF, it.nchB, it.nf, blk);
+  if (it.ks == 3) pack_bx3_block<3>(tile, it.w, it.pf, it.pb, it.Cin, it.Cout, it.nchF, it.nchB, it.nf, blk, it.tapT != 0);
+  else if (it.ks == 1) pack_bx3_block<1>(tile, it.w, it.pf, it.pb, it.Cin, it.Cout, it.nchF, it.nchB, it.nf, blk, it.tapT != 0);
+  else if (it.ks == 5) pack_bx3_block<5>(tile, it.w, it.pf, it.pb, it.Cin, it.Cout, it.nchF, it.nchB, it.nf, blk, it.tapT != 0);
+  else pack_bx3_block<7>(tile, it.w, it.pf, it.pb, it.Cin, it.Cout, it.nchF, it.nchB, it.nf, blk, it.tapT != 0);
 }
 
 // ---- Adam update + re-pack of the split-bf16 conv weights in ONE pass (round 5).  adam_flat_kernel moved 28 B

@@ -401,7 +401,7 @@ __global__ void __launch_bounds__(256, OCC) conv2d_wgrad3_kernel(Wgrad3Args a) {
 // layers (Z = 69), 77 us for 129 -> 64 @ 192x640 (Z = 237), 0.61 ms per step (profiles/r05_step_breakdown.txt).
 __global__ void __launch_bounds__(256) wgrad3_reduce_kernel(const float* __restrict__ ws, const float* __restrict__ ws_bias,
                                                             float* __restrict__ dw, float* __restrict__ dbias, int Z, int KS,
-                                                            int COP, int CIP, int Cin, int Cout, int ncol, int ZG) {
+                                                            int COP, int CIP, int Cin, int Cout, int ncol, int ZG, int epi) {
   __shared__ float4 part[256];
   __shared__ float tile[4 * 256 + 4];
   const int KK = KS * KS, items = KK * ncol, CIB = 4 * ncol;
@@ -434,25 +434,31 @@ __global__ void __launch_bounds__(256) wgrad3_reduce_kernel(const float* __restr
   if (zg == 0 && ci < CIP) {
     float4 s = part[item];
     for (int g = 1; g < ZG; ++g) { const float4 q = part[g * items + item]; s.x += q.x; s.y += q.y; s.z += q.z; s.w += q.w; }
-    float* tl = tile + (4 * j) * KK + tap;
+    // epi: the gradient of a layer that convolved with transposed taps leaves in the weight's own layout, tap (ky, kx) at [kx][ky]
+    const int tapd = (epi & PNSFM_WGRAD_EPI_TAPT) ? (tap - (tap / KS) * KS) * KS + tap / KS : tap;
+    float* tl = tile + (4 * j) * KK + tapd;
     tl[0] = s.x; tl[KK] = s.y; tl[2 * KK] = s.z; tl[3 * KK] = s.w;
   }
   __syncthreads();
   int nci = Cin - ci0;
   if (nci > CIB) nci = CIB;
   float* out = dw + ((size_t)co * Cin + ci0) * KK;
-  for (int e = t; e < nci * KK; e += 256) out[e] = tile[e];
+  if (epi & PNSFM_WGRAD_EPI_ADD) {                // the finished sum is added last: dst = dst + sum
+    for (int e = t; e < nci * KK; e += 256) out[e] = out[e] + tile[e];
+  } else {
+    for (int e = t; e < nci * KK; e += 256) out[e] = tile[e];
+  }
   if (dbias && blockIdx.y == 0 && t < 64) {       // the bias partials: 64 lanes share the z range, a fixed shuffle tree
     float sum = 0.f;
     for (int z = t; z < Z; z += 64) sum += ws_bias[(size_t)z * COP + co];
     for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d);
-    if (t == 0) dbias[co] = sum;
+    if (t == 0) dbias[co] = (epi & PNSFM_WGRAD_EPI_ADD) ? dbias[co] + sum : sum;
   }
 }
 
 // the second stage on its own (conv2d_wgrad4.hip writes the same partial-tensor layout)
 int launch_wgrad3_reduce(const float* ws, const float* ws_bias, float* dw, float* dbias, int Z, int KS, int COP, int CIP, int Cin,
-                         int Cout, hipStream_t s) {
+                         int Cout, hipStream_t s, int epi) {
   // z groups so that a thread adds <= ~8 partials; columns per block from what is left of the 256 threads (1x1 layers: <= 32 columns)
   const int KK = KS * KS;
   int zg_want = ceil_div(Z, 8);
@@ -465,7 +471,7 @@ int launch_wgrad3_reduce(const float* ws, const float* ws_bias, float* dw, float
   int ZG = 256 / (KK * ncol);
   if (ZG > Z) ZG = Z;
   PNSFM_LAUNCH(wgrad3_reduce_kernel, dim3(Cout, ceil_div(Cin, 4 * ncol)), dim3(256), 0, s, ws, ws_bias, dw, dbias, Z, KS, COP, CIP,
-               Cin, Cout, ncol, ZG);
+               Cin, Cout, ncol, ZG, epi);
   return check_launch("conv2d_backward_weight (split-bf16, reduction)");
 }
 
@@ -505,7 +511,7 @@ static int launch_wgrad3(const Wgrad3Args& a, dim3 grid, hipStream_t s) {
 }
 
 int enqueue_wgrad3(const float* x, const float* dy, float* dw, float* dbias, int B, int Cin, int Cout, int H, int W, int ks,
-                   int split, int NT, int WMwant, hipStream_t s, const ConvSrc* ms, const ConvRows* rows) {
+                   int split, int NT, int WMwant, hipStream_t s, const ConvSrc* ms, const ConvRows* rows, int epi) {
   if (!wgrad3_supported(Cin, Cout, H, W, ks)) { set_error("conv2d_backward_weight (split-bf16): unsupported shape"); return -1; }
   if (NT != 2 || !wgrad3_nt2_ok(Cin, ks)) NT = 1;
   if (ms && NT == 2 && !conv_src_aligned(*ms, Cin, 64)) NT = 1;     // a 64-channel tile would straddle two tensors
@@ -522,7 +528,7 @@ int enqueue_wgrad3(const float* x, const float* dy, float* dw, float* dbias, int
   const int co_groups = ceil_div(ceil_div(Cout, 32), WM);
   Wgrad3Args a;
   const int splitP = wgrad_bx3_begin(a, "split-bf16", x, dy, dw, dbias, B, Cin, Cout, H, W, ks, 4, tc, co_groups * WM * 32,
-                                     ci_tiles * 32 * NT, split, s, ms, rows);
+                                     ci_tiles * 32 * NT, split, s, ms, rows, epi);
   if (splitP < 0) return -1;
   a.g = {ci_tiles, ci_tiles * ks, co_groups, block_map_mode()};
   dim3 grid(ci_tiles * ks * co_groups * splitP);
@@ -554,7 +560,7 @@ int enqueue_wgrad3(const float* x, const float* dy, float* dw, float* dbias, int
   else PNSFM_W3(7, 1);
 #undef PNSFM_W3T
 #undef PNSFM_W3
-  return wgrad_bx3_finish(a, splitP, rc, ks, s);
+  return wgrad_bx3_finish(a, splitP, rc, ks, s, epi);
 }
 
 }  // namespace pnsfm

@@ -339,7 +339,7 @@ static int launch_wgrad4(const Wgrad4Args& a, dim3 grid, hipStream_t s) {
 
 // cfg: WCI (1 | 2) | TG << 4 | TR << 8 (0: library choice)
 int enqueue_wgrad4(const float* x, const float* dy, float* dw, float* dbias, int B, int Cin, int Cout, int H, int W, int split,
-                   int cfg, hipStream_t s, const ConvSrc* ms, const ConvRows* rows) {
+                   int cfg, hipStream_t s, const ConvSrc* ms, const ConvRows* rows, int epi) {
   if (!wgrad4_supported(Cin, Cout, H, W, 3)) { set_error("conv2d_backward_weight (nine taps): unsupported shape"); return -1; }
   const int WCI = (cfg & 15) == 1 ? 1 : 2;
   const int TG = wgrad4_TG(W, (cfg >> 4) & 15);
@@ -350,7 +350,7 @@ int enqueue_wgrad4(const float* x, const float* dy, float* dw, float* dbias, int
   const int ci_tiles = ceil_div(Cin, 16 * WCI), co_groups = ceil_div(Cout, 32 * (4 / WCI));
   Wgrad4Args a;
   const int splitP = wgrad_bx3_begin(a, "nine taps", x, dy, dw, dbias, B, Cin, Cout, H, W, 3, TR, 8 * TG, co_groups * 32 * (4 / WCI),
-                                     ci_tiles * 16 * WCI, split, s, ms, rows);
+                                     ci_tiles * 16 * WCI, split, s, ms, rows, epi);
   if (splitP < 0) return -1;
   a.Hx = Hd;      // (this kernel's reading of the field: the rows of dY)
   a.g = {ci_tiles, co_groups, block_map_mode()};
@@ -371,7 +371,7 @@ int enqueue_wgrad4(const float* x, const float* dy, float* dw, float* dbias, int
   if (WCI == 1) PNSFM_W4G(1); else PNSFM_W4G(2);
 #undef PNSFM_W4G
 #undef PNSFM_W4
-  return wgrad_bx3_finish(a, splitP, rc, 3, s);
+  return wgrad_bx3_finish(a, splitP, rc, 3, s, epi);
 }
 
 }  // namespace pnsfm

@@ -47,8 +47,12 @@ struct WgradBx3Args {
 #endif
 
 // ---- host side of a launch.  conv2d_wgrad3.hip: sums the partial tensors of a pixel-split launch in a fixed order
+// epi (PNSFM_WGRAD_EPI_*, include/pnsfm.h): what the second stage does with the finished sums -- add them to what dw / dbias hold
+// (dst = dst + sum, the sum complete first: the bits of a separate elementwise add), store dw with its (ky, kx) taps swapped back (the
+// gradient of a layer that convolved with transposed taps, in the weight's own layout).  A launch with epi != 0 always goes through
+// the second stage, a single pixel split included (one partial tensor): the kernels' own direct store knows neither.
 int launch_wgrad3_reduce(const float* ws, const float* ws_bias, float* dw, float* dbias, int Z, int KS, int COP, int CIP, int Cin,
-                         int Cout, hipStream_t s);
+                         int Cout, hipStream_t s, int epi = 0);
 
 // Everything of `a` but the launch shape, for pixel tiles of tr x tc pixels and a workspace padded to COP x CIP channels: the size and
 // source checks, the tensors, the tile counts, `split` clamped to whole tiles and the scratch of a pixel-split launch.
@@ -56,7 +60,7 @@ int launch_wgrad3_reduce(const float* ws, const float* ws_bias, float* dw, float
 template <class Args>
 static inline int wgrad_bx3_begin(Args& a, const char* what, const float* x, const float* dy, float* dw, float* dbias, int B, int Cin,
                                   int Cout, int H, int W, int ks, int tr, int tc, int COP, int CIP, int split, hipStream_t s,
-                                  const ConvSrc* ms, const ConvRows* rows) {
+                                  const ConvSrc* ms, const ConvRows* rows, int epi = 0) {
   if (rows && (ms || ks < 3 || rows->Hi <= 0)) {
     set_error("conv2d_backward_weight (%s): a row window needs a 3x3 / 5x5 / 7x7 layer with one input tensor", what);
     return -1;
@@ -83,7 +87,7 @@ static inline int wgrad_bx3_begin(Args& a, const char* what, const float* x, con
   a.tiles_per_split = ceil_div(a.total_tiles, split);
   const int splitP = ceil_div(a.total_tiles, a.tiles_per_split);
   a.ws = nullptr; a.ws_bias = nullptr;
-  if (splitP > 1) {
+  if (splitP > 1 || epi) {
     // pixel-split launch: partial tensors in the stream's scratch buffer (api.hip: valid until the stream's next request, i.e. through
     // the reduction that wgrad_bx3_finish enqueues), summed by wgrad3_reduce_kernel
     // (scratch_get itself, not a ScratchLease: a lease object could not outlive this function, and the pointer has to)
@@ -96,8 +100,8 @@ static inline int wgrad_bx3_begin(Args& a, const char* what, const float* x, con
 }
 // after the kernel's launch (rc): the second stage of a pixel-split launch
 template <class Args>
-static inline int wgrad_bx3_finish(const Args& a, int splitP, int rc, int ks, hipStream_t s) {
-  if (a.ws && !rc) rc = launch_wgrad3_reduce(a.ws, a.ws_bias, a.dw, a.dbias, splitP, ks, a.COP, a.CIP, a.Cin, a.Cout, s);
+static inline int wgrad_bx3_finish(const Args& a, int splitP, int rc, int ks, hipStream_t s, int epi = 0) {
+  if (a.ws && !rc) rc = launch_wgrad3_reduce(a.ws, a.ws_bias, a.dw, a.dbias, splitP, ks, a.COP, a.CIP, a.Cin, a.Cout, s, epi);
   return rc;
 }
 

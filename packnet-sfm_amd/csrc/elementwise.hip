@@ -353,27 +353,35 @@ __global__ void __launch_bounds__(64) pack_bias_eff_tail_kernel(const float* __r
 }
 
 // gradients of that bias: db3[f] = sum_co g[co] * Ssum[co][f] (one wave per f, ascending co per lane, fixed-order lane tree)
+// add: the finished sum is added to what db3 holds (dst = dst + sum).  Blocks past d (add mode, db2 given): db2[co] = db2[co] + g[co],
+// the Conv2d bias's share of the composed bias -- g itself -- joining the gradients the strips left there.
 __global__ void __launch_bounds__(64) pack_bias_eff_db3_kernel(const float* __restrict__ g, const float* __restrict__ Ssum,
-                                                               float* __restrict__ db3, int C, int d) {
+                                                               float* __restrict__ db3, float* __restrict__ db2, int C, int d, int add) {
+  if ((int)blockIdx.x >= d) {
+    const int co = ((int)blockIdx.x - d) * 64 + threadIdx.x;
+    if (co < C) db2[co] = db2[co] + g[co];
+    return;
+  }
   const int f = blockIdx.x;
   float acc = 0.f;
   for (int co = threadIdx.x; co < C; co += 64) acc += g[co] * Ssum[(size_t)co * d + f];
   for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o);
-  if (threadIdx.x == 0) db3[f] = acc;
+  if (threadIdx.x == 0) db3[f] = add ? db3[f] + acc : acc;
 }
 
 // ... and the Conv2d weight's: dW2[co][f-block][ky][kx] = full[co][f-block][ky + 1][kx + 1] (the composition's gradient, computed on
 // the zero-ring-padded (k+2)^2 taps) + g[co] * b3[f] (the bias path).  rows = C * d * D tap planes of k x k.
 __global__ void __launch_bounds__(256) pack_dw2_finish_kernel(const float* __restrict__ full, const float* __restrict__ g,
                                                               const float* __restrict__ b3, float* __restrict__ dW2, int d, int D,
-                                                              int k, unsigned total) {
+                                                              int k, unsigned total, int add) {
   const unsigned i = blockIdx.x * 256u + threadIdx.x;
   if (i >= total) return;
   const unsigned kk = (unsigned)(k * k), plane = i / kk, tap = i - plane * kk;
   const unsigned ky = tap / (unsigned)k, kx = tap - ky * (unsigned)k;
   const unsigned co = plane / (unsigned)(d * D), f = (plane / (unsigned)D) % (unsigned)d;
   const unsigned k2 = (unsigned)(k + 2);
-  dW2[i] = full[((size_t)plane * k2 + ky + 1) * k2 + kx + 1] + g[co] * b3[f];
+  const float v = full[((size_t)plane * k2 + ky + 1) * k2 + kx + 1] + g[co] * b3[f];
+  dW2[i] = add ? dW2[i] + v : v;      // add: this node's finished gradient joins what the strips left in dW2 (dst = dst + v)
 }
 
 }  // namespace pnsfm
@@ -570,21 +578,32 @@ int pnsfm_pack_bias_eff_forward(const float* W2, const float* b2, const float* b
   return check_launch("pack_bias_eff_forward");
 }
 
-int pnsfm_pack_bias_eff_backward(const float* g, const float* Ssum, const float* b3, const float* dWeff_full, float* db3, float* dW2,
-                                 int C, int d, int D, int k, void* stream) {
+static int pack_bias_eff_backward_impl(const float* g, const float* Ssum, const float* b3, const float* dWeff_full, float* db3, float* dW2,
+                                       float* db2, int C, int d, int D, int k, int add, void* stream) {
   if (C < 1 || d < 1 || d > 8 || D < 1 || k < 1) { set_error("pack_bias_eff_backward: bad sizes (C=%d d=%d D=%d k=%d)", C, d, D, k); return -1; }
+  if (db2 && !(add && db3)) { set_error("pack_bias_eff_backward: db2 is an add-into destination and rides on the db3 launch"); return -1; }
   if (db3) {
-    PNSFM_LAUNCH(pack_bias_eff_db3_kernel, dim3(d), dim3(64), 0, (hipStream_t)stream, g, Ssum, db3, C, d);
+    PNSFM_LAUNCH(pack_bias_eff_db3_kernel, dim3(d + (db2 ? (C + 63) / 64 : 0)), dim3(64), 0, (hipStream_t)stream, g, Ssum, db3, db2, C, d, add);
     if (int rc = check_launch("pack_bias_eff_backward (db3)")) return rc;
   }
   if (dW2) {
     const size_t total = (size_t)C * d * D * k * k;
     if (total >= (1ull << 32)) { set_error("pack_bias_eff_backward: >= 2^32 weight elements"); return -1; }
     PNSFM_LAUNCH(pack_dw2_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dWeff_full, g, b3,
-                 dW2, d, D, k, (unsigned)total);
+                 dW2, d, D, k, (unsigned)total, add);
     if (int rc = check_launch("pack_bias_eff_backward (dW2)")) return rc;
   }
   return 0;
+}
+
+int pnsfm_pack_bias_eff_backward(const float* g, const float* Ssum, const float* b3, const float* dWeff_full, float* db3, float* dW2,
+                                 int C, int d, int D, int k, void* stream) {
+  return pack_bias_eff_backward_impl(g, Ssum, b3, dWeff_full, db3, dW2, nullptr, C, d, D, k, 0, stream);
+}
+
+int pnsfm_pack_bias_eff_backward_add(const float* g, const float* Ssum, const float* b3, const float* dWeff_full, float* db3, float* dW2,
+                                     float* db2, int C, int d, int D, int k, void* stream) {
+  return pack_bias_eff_backward_impl(g, Ssum, b3, dWeff_full, db3, dW2, db2, C, d, D, k, 1, stream);
 }
 
 }  // extern "C"

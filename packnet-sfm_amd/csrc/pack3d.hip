@@ -144,8 +144,14 @@ __global__ void __launch_bounds__(256) conv3d_fwd_kernel(const T* __restrict__ p
 // Row window of the border strips (the sense of ConvRows, pnsfm_common.h): the strips [2B, D, S, w] keep 2r of their S = 2r + 1 Conv3d
 // rows, the first 2r in the leading half of the batch and the last 2r in the trailing half.  out / dout is then [2B, NF*D, Ho, w]
 // and holds the frame rows row0 .. row0 + Ho - 1, row0 = ya for samples b < Bh, yb for the others; p / dp keep all H rows.
-struct C3dRows { int Ho, Bh, ya, yb; };
+// Column window (the gradient kernels only): out / dout holds the Wo frame columns xa .. xa + Wo - 1 of each of its rows, [.., Ho, Wo];
+// Wo = W, xa = 0 everywhere but in the kernel composition of the collapsed packing block, whose dout is the Conv2d weight standing
+// inside a one-tap ring of zeros that is never stored (pnsfm_conv3d_backward_data_ring / _weight_ring).
+struct C3dRows { int Ho, Bh, ya, yb, Wo, xa; };
 __device__ __forceinline__ int c3d_row0(const C3dRows& rw, int b) { return b < rw.Bh ? rw.ya : rw.yb; }
+// Transposed taps, read in place (the column strips of the collapsed packing block convolve in transposed space): tap (dz, dy, dx)
+// of the stencil is w3[f][dz][dx][dy].  A weight gradient computed that way is stored through the same map: in w3's own layout.
+__host__ __device__ constexpr int c3d_tap_t(int t) { return (t / 9) * 9 + (t % 3) * 3 + (t % 9) / 3; }
 
 // Four voxels per thread along x (W % 4 == 0, 16-byte aligned tensors): the 9 rows of the stencil are read as one 16-byte load
 // plus the two edge values each (27 load instructions per 4 voxels instead of 108), the weights as [tap][feature] float4
@@ -154,11 +160,11 @@ __device__ __forceinline__ int c3d_row0(const C3dRows& rw, int b) { return b < r
 template <int NF>
 __global__ void __launch_bounds__(256) conv3d_fwd_x4_kernel(const float* __restrict__ p, const float* __restrict__ w3,
                                                              const float* __restrict__ b3, float* __restrict__ out,
-                                                             int D, int H, int W, C3dRows rw) {
+                                                             int D, int H, int W, C3dRows rw, int tapT) {
   __shared__ __attribute__((aligned(16))) float wt[28][NF];      // [tap][feature]; row 27 = bias
   for (int i = threadIdx.x; i < 28 * NF; i += 256) {
     const int tap = i / NF, f = i - tap * NF;
-    wt[tap][f] = tap < 27 ? w3[f * 27 + tap] : (b3 ? b3[f] : 0.f);
+    wt[tap][f] = tap < 27 ? w3[f * 27 + (tapT ? c3d_tap_t(tap) : tap)] : (b3 ? b3[f] : 0.f);
   }
   __syncthreads();
   const int HW = H * W, DHW = D * HW, Wq = W >> 2, HWq = rw.Ho * Wq;
@@ -309,11 +315,11 @@ __global__ void __launch_bounds__(256) conv3d_fwd_x4_d2s_kernel(const float* __r
 // (97 % lane efficiency); row / image ends are masked (x == 0 has no left neighbour whatever lane holds pixel - 1).  The d loop
 // has the SAME trip count (len + 2) on every lane -- lanes of a wave may sit in different d chunks -- so the shifts are never
 // executed under divergence.
-template <int NF>
+template <int NF, bool TAPT = false>
 __global__ void __launch_bounds__(256) conv3d_dgrad_kernel(const float* __restrict__ dout, const float* __restrict__ w3,
                                                             float* __restrict__ dp, int D, int H, int W, int len, int xmap,
                                                             C3dRows rw) {
-  const int HW = H * W, DHW = D * HW, gHW = rw.Ho * W, gDHW = D * gHW, row0 = c3d_row0(rw, blockIdx.z);
+  const int HW = H * W, DHW = D * HW, gHW = rw.Ho * rw.Wo, gDHW = D * gHW, row0 = c3d_row0(rw, blockIdx.z);
   const int nchunk = (D + len - 1) / len;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   // rows y - 1 / y + 1 of a block's pixels are the centre rows of the blocks a few places before / after it: an XCD gets a
@@ -338,7 +344,7 @@ __global__ void __launch_bounds__(256) conv3d_dgrad_kernel(const float* __restri
 #pragma unroll
   for (int dy = 0; dy < 3; ++dy) {
     const int yy = y - dy + 1;
-    off[dy] = (inr && yy >= row0 && yy < row0 + rw.Ho) ? (unsigned)((yy - row0) * W + x) * 4u : kOut;
+    off[dy] = (inr && yy >= row0 && yy < row0 + rw.Ho && x >= rw.xa && x < rw.xa + rw.Wo) ? (unsigned)((yy - row0) * rw.Wo + x - rw.xa) * 4u : kOut;
   }
   // a_lo -> output dd-1 (complete after this plane), a_mid -> output dd, a_hi -> output dd+1
   float a_lo = 0.f, a_mid = 0.f, a_hi = 0.f;
@@ -367,9 +373,10 @@ __global__ void __launch_bounds__(256) conv3d_dgrad_kernel(const float* __restri
     for (int f = 0; f < NF; ++f)
 #pragma unroll
       for (int tp = 0; tp < 9; ++tp) {
-        a_lo = fmaf(w3[f * 27 + tp], g[f][tp], a_lo);             // dz = 0: d = dd - 1
-        a_mid = fmaf(w3[f * 27 + 9 + tp], g[f][tp], a_mid);       // dz = 1: d = dd
-        a_hi = fmaf(w3[f * 27 + 18 + tp], g[f][tp], a_hi);        // dz = 2: d = dd + 1
+        const int ts = TAPT ? c3d_tap_t(tp) : tp;                 // (compile-time: tp is an unrolled index)
+        a_lo = fmaf(w3[f * 27 + ts], g[f][tp], a_lo);             // dz = 0: d = dd - 1
+        a_mid = fmaf(w3[f * 27 + 9 + ts], g[f][tp], a_mid);       // dz = 1: d = dd
+        a_hi = fmaf(w3[f * 27 + 18 + ts], g[f][tp], a_hi);        // dz = 2: d = dd + 1
       }
     if (active && dd - 1 >= d0 && dd - 1 < dend) ob[(size_t)(dd - 1) * HW] = a_lo;
     a_lo = a_mid;
@@ -385,11 +392,11 @@ __global__ void __launch_bounds__(256) conv3d_dgrad_kernel(const float* __restri
 // accumulator a plane feeds is a compile-time index, every FMA is half of a v_pk_fma_f32), nothing is parked or re-loaded, one
 // buffer descriptor instead of eight, 94 VGPRs.  Loads and wave shifts per output are unchanged.  unpack1's volume (4 x 32 x 96 x
 // 320): 107 -> 64 us; the step's nine volumes 417 -> 265 us (profiles/r04_ab_conv3d_dgrad_column.txt).
-template <int NF, int LEN>
+template <int NF, int LEN, bool TAPT = false>
 __global__ void __launch_bounds__(256) conv3d_dgrad_col_kernel(const float* __restrict__ dout, const float* __restrict__ w3,
                                                                 float* __restrict__ dp, int D, int H, int W, int xmap, C3dRows rw) {
   constexpr int FG = 1;                    // features per pass (2: 54 weights + the plane masks overflow the SGPR file again, 76 vs 64 us)
-  const int HW = H * W, DHW = D * HW, gHW = rw.Ho * W, gDHW = D * gHW, row0 = c3d_row0(rw, blockIdx.z);
+  const int HW = H * W, DHW = D * HW, gHW = rw.Ho * rw.Wo, gDHW = D * gHW, row0 = c3d_row0(rw, blockIdx.z);
   const int nchunk = (D + LEN - 1) / LEN;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const unsigned bx = xmap ? pnsfm_xcd_logical_block(blockIdx.x, gridDim.x) : blockIdx.x;
@@ -407,7 +414,7 @@ __global__ void __launch_bounds__(256) conv3d_dgrad_col_kernel(const float* __re
 #pragma unroll
   for (int dy = 0; dy < 3; ++dy) {
     const int yy = y - dy + 1;
-    off[dy] = (inr && yy >= row0 && yy < row0 + rw.Ho) ? (unsigned)((yy - row0) * W + x) * 4u : kOut;
+    off[dy] = (inr && yy >= row0 && yy < row0 + rw.Ho && x >= rw.xa && x < rw.xa + rw.Wo) ? (unsigned)((yy - row0) * rw.Wo + x - rw.xa) * 4u : kOut;
   }
   float acc[LEN];
 #pragma unroll
@@ -443,9 +450,10 @@ __global__ void __launch_bounds__(256) conv3d_dgrad_col_kernel(const float* __re
       for (int u = 0; u < FG; ++u)
 #pragma unroll
         for (int tp = 0; tp < 9; ++tp) {
-          if (t >= 2) acc[t >= 2 ? t - 2 : 0] = fmaf(wf[u * 27 + tp], g[u][tp], acc[t >= 2 ? t - 2 : 0]);
-          if (t >= 1 && t <= LEN) acc[(t >= 1 && t <= LEN) ? t - 1 : 0] = fmaf(wf[u * 27 + 9 + tp], g[u][tp], acc[(t >= 1 && t <= LEN) ? t - 1 : 0]);
-          if (t < LEN) acc[t < LEN ? t : 0] = fmaf(wf[u * 27 + 18 + tp], g[u][tp], acc[t < LEN ? t : 0]);
+          const int ts = TAPT ? c3d_tap_t(tp) : tp;                 // (compile-time: tp is an unrolled index)
+          if (t >= 2) acc[t >= 2 ? t - 2 : 0] = fmaf(wf[u * 27 + ts], g[u][tp], acc[t >= 2 ? t - 2 : 0]);
+          if (t >= 1 && t <= LEN) acc[(t >= 1 && t <= LEN) ? t - 1 : 0] = fmaf(wf[u * 27 + 9 + ts], g[u][tp], acc[(t >= 1 && t <= LEN) ? t - 1 : 0]);
+          if (t < LEN) acc[t < LEN ? t : 0] = fmaf(wf[u * 27 + 18 + ts], g[u][tp], acc[t < LEN ? t : 0]);
         }
     }
   }
@@ -585,7 +593,7 @@ __global__ void __launch_bounds__(256, 2) conv3d_wgrad_ring_kernel(const float* 
                                                                     float* __restrict__ part, int D, int H, int W, int len, int NF,
                                                                     int xmap, C3dRows rw) {
   __shared__ float red[kW3Pass * kW3Row];
-  const int HW = H * W, DHW = D * HW, gHW = rw.Ho * W, gDHW = D * gHW, row0 = c3d_row0(rw, blockIdx.z);
+  const int HW = H * W, DHW = D * HW, gHW = rw.Ho * rw.Wo, gDHW = D * gHW, row0 = c3d_row0(rw, blockIdx.z);
   const int nchunk = (D + len - 1) / len;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const unsigned bx = xmap ? pnsfm_xcd_logical_block(blockIdx.x, gridDim.x) : blockIdx.x;
@@ -610,7 +618,8 @@ __global__ void __launch_bounds__(256, 2) conv3d_wgrad_ring_kernel(const float* 
     const int yy = y + r - 1;
     off[r] = (inr && yy >= 0 && yy < H) ? (unsigned)(yy * W + x) * 4u : kOut;
   }
-  const unsigned goff = (active && y >= row0 && y < row0 + rw.Ho) ? (unsigned)((y - row0) * W + x) * 4u : kOut;      // a row dout does not hold: zero
+  const unsigned goff = (active && y >= row0 && y < row0 + rw.Ho && x >= rw.xa && x < rw.xa + rw.Wo)
+                            ? (unsigned)((y - row0) * rw.Wo + x - rw.xa) * 4u : kOut;      // a row / column dout does not hold: zero
   // plane k of this thread's run is dd = d0 - 1 + k; step s is d = d0 + s and uses the planes s, s + 1, s + 2
   auto load_centres = [&](float (&c)[3], int k) {
     const int dd = d0 - 1 + k;
@@ -702,13 +711,17 @@ __global__ void __launch_bounds__(256, 2) conv3d_wgrad_ring_kernel(const float* 
 // dw3 / db3 entry (f, t) = sum over the blocks' partials (fp64), one wave per entry: lane l adds blocks l, l + 64, ... in order, the
 // lane sums meet in a fixed shuffle tree -- bit-reproducible
 __global__ void __launch_bounds__(64) conv3d_wgrad_finish_kernel(const float* __restrict__ part, float* __restrict__ dw3,
-                                                                 float* __restrict__ db3, int nblk, int ngroups, int fpb) {
+                                                                 float* __restrict__ db3, int nblk, int ngroups, int fpb, int epi) {
   const int i = blockIdx.x, lane = threadIdx.x;             // i = f * 28 + t over all NF features; fpb features per group
   const int f = i / 28, t = i - f * 28, fg = f / fpb, v = (f - fg * fpb) * 28 + t;
   double s = 0.0;
   for (int p = lane; p < nblk; p += 64) s += (double)part[((size_t)p * ngroups + fg) * (fpb * 28) + v];
   for (int d = 32; d >= 1; d >>= 1) s += __shfl_down(s, d);
-  if (lane == 0) { if (t < 27) dw3[f * 27 + t] = (float)s; else db3[f] = (float)s; }
+  if (lane == 0 && (t < 27 || db3)) {      // epi (PNSFM_WGRAD_EPI_*): taps stored swapped back; the finished sum added to what the destination holds, last
+    float* dst = t < 27 ? dw3 + f * 27 + ((epi & PNSFM_WGRAD_EPI_TAPT) ? c3d_tap_t(t) : t) : db3 + f;
+    const float v = (float)s;
+    *dst = (epi & PNSFM_WGRAD_EPI_ADD) ? *dst + v : v;
+  }
 }
 
 static int grid_for(size_t total) {
@@ -764,20 +777,31 @@ static bool nf_ok(int NF, const char* what) {
   return false;
 }
 
-int pnsfm_conv3d_forward(const float* p, const float* w3, const float* b3, float* out, int B, int D, int H, int W, int NF,
-                         void* stream) {
+static int conv3d_forward_impl(const float* p, const float* w3, const float* b3, float* out, int B, int D, int H, int W, int NF,
+                               int tapT, void* stream) {
   if (!nf_ok(NF, "conv3d_forward")) return -1;
   if (W % 4 == 0 && (((uintptr_t)p | (uintptr_t)out) & 15) == 0) {      // four voxels per thread
     const dim3 gq(ceil_div(D * H * (W / 4), 256), 1, B);
-    const C3dRows rw = {H, B, 0, 0};
-    if (NF == 8) PNSFM_LAUNCH((conv3d_fwd_x4_kernel<8>), gq, dim3(256), 0, (hipStream_t)stream, p, w3, b3, out, D, H, W, rw);
-    else PNSFM_LAUNCH((conv3d_fwd_x4_kernel<4>), gq, dim3(256), 0, (hipStream_t)stream, p, w3, b3, out, D, H, W, rw);
+    const C3dRows rw = {H, B, 0, 0, W, 0};
+    if (NF == 8) PNSFM_LAUNCH((conv3d_fwd_x4_kernel<8>), gq, dim3(256), 0, (hipStream_t)stream, p, w3, b3, out, D, H, W, rw, tapT);
+    else PNSFM_LAUNCH((conv3d_fwd_x4_kernel<4>), gq, dim3(256), 0, (hipStream_t)stream, p, w3, b3, out, D, H, W, rw, tapT);
     return check_launch("conv3d_forward");
   }
+  if (tapT) { set_error("conv3d_forward_t: transposed taps need W %% 4 == 0 and 16-byte aligned tensors"); return -1; }
   const dim3 grid(ceil_div(D * H * W, 256), 1, B);
   if (NF == 8) PNSFM_LAUNCH((conv3d_fwd_kernel<8>), grid, dim3(256), 0, (hipStream_t)stream, p, w3, b3, out, D, H, W);
   else PNSFM_LAUNCH((conv3d_fwd_kernel<4>), grid, dim3(256), 0, (hipStream_t)stream, p, w3, b3, out, D, H, W);
   return check_launch("conv3d_forward");
+}
+
+int pnsfm_conv3d_forward(const float* p, const float* w3, const float* b3, float* out, int B, int D, int H, int W, int NF,
+                         void* stream) {
+  return conv3d_forward_impl(p, w3, b3, out, B, D, H, W, NF, 0, stream);
+}
+
+int pnsfm_conv3d_forward_t(const float* p, const float* w3, const float* b3, float* out, int B, int D, int H, int W, int NF, int tapT,
+                           void* stream) {
+  return conv3d_forward_impl(p, w3, b3, out, B, D, H, W, NF, tapT ? 1 : 0, stream);
 }
 
 int pnsfm_set_pack3d_fold(int on) {
@@ -842,7 +866,7 @@ static int dgrad_len(int B, int D, int H, int W) {
 
 // rw: the rows of the H-row frame that dout holds (the whole frame, or the border strips' window)
 static int conv3d_backward_data_impl(const float* dout, const float* w3, float* dp, int B, int D, int H, int W, int NF,
-                                     void* stream, const char* what, C3dRows rw) {
+                                     void* stream, const char* what, C3dRows rw, int tapT = 0) {
   if (!nf_ok(NF, what)) return -1;
   if ((size_t)D * H * W * 4 >= 0x7fffffffull) { set_error("%s: feature slab exceeds the 2 GiB buffer window", what); return -1; }
   const int len = dgrad_len(B, D, H, W);
@@ -850,23 +874,21 @@ static int conv3d_backward_data_impl(const float* dout, const float* w3, float* 
   static const int xm = [] { const char* e = getenv("PNSFM_STENCIL_XCD_MAP"); return (e && e[0] == '0') ? 0 : 1; }();      // A/B switch
   const int xmap = (block_map_mode() >= 2 && xm) ? 1 : 0;
   static const int col = [] { const char* e = getenv("PNSFM_CONV3D_DGRAD_COL"); return (e && e[0] == '0') ? 0 : 1; }();      // A/B switch
-  if (col && len == 8) {
-    if (NF == 8) PNSFM_LAUNCH((conv3d_dgrad_col_kernel<8, 8>), grid, dim3(256), 0, (hipStream_t)stream, dout, w3, dp, D, H, W, xmap, rw);
-    else PNSFM_LAUNCH((conv3d_dgrad_col_kernel<4, 8>), grid, dim3(256), 0, (hipStream_t)stream, dout, w3, dp, D, H, W, xmap, rw);
-  } else if (col && len == 4) {
-    if (NF == 8) PNSFM_LAUNCH((conv3d_dgrad_col_kernel<8, 4>), grid, dim3(256), 0, (hipStream_t)stream, dout, w3, dp, D, H, W, xmap, rw);
-    else PNSFM_LAUNCH((conv3d_dgrad_col_kernel<4, 4>), grid, dim3(256), 0, (hipStream_t)stream, dout, w3, dp, D, H, W, xmap, rw);
-  } else if (col && len == 2) {
-    if (NF == 8) PNSFM_LAUNCH((conv3d_dgrad_col_kernel<8, 2>), grid, dim3(256), 0, (hipStream_t)stream, dout, w3, dp, D, H, W, xmap, rw);
-    else PNSFM_LAUNCH((conv3d_dgrad_col_kernel<4, 2>), grid, dim3(256), 0, (hipStream_t)stream, dout, w3, dp, D, H, W, xmap, rw);
-  }
-  else if (NF == 8) PNSFM_LAUNCH((conv3d_dgrad_kernel<8>), grid, dim3(256), 0, (hipStream_t)stream, dout, w3, dp, D, H, W, len, xmap, rw);
-  else PNSFM_LAUNCH((conv3d_dgrad_kernel<4>), grid, dim3(256), 0, (hipStream_t)stream, dout, w3, dp, D, H, W, len, xmap, rw);
+#define PNSFM_C3D_DGRAD(NFv, T)                                                                                                        \
+  do {                                                                                                                                 \
+    if (col && len == 8) PNSFM_LAUNCH((conv3d_dgrad_col_kernel<NFv, 8, T>), grid, dim3(256), 0, (hipStream_t)stream, dout, w3, dp, D, H, W, xmap, rw);      \
+    else if (col && len == 4) PNSFM_LAUNCH((conv3d_dgrad_col_kernel<NFv, 4, T>), grid, dim3(256), 0, (hipStream_t)stream, dout, w3, dp, D, H, W, xmap, rw); \
+    else if (col && len == 2) PNSFM_LAUNCH((conv3d_dgrad_col_kernel<NFv, 2, T>), grid, dim3(256), 0, (hipStream_t)stream, dout, w3, dp, D, H, W, xmap, rw); \
+    else PNSFM_LAUNCH((conv3d_dgrad_kernel<NFv, T>), grid, dim3(256), 0, (hipStream_t)stream, dout, w3, dp, D, H, W, len, xmap, rw);                       \
+  } while (0)
+  if (tapT) { if (NF == 8) PNSFM_C3D_DGRAD(8, true); else PNSFM_C3D_DGRAD(4, true); }
+  else { if (NF == 8) PNSFM_C3D_DGRAD(8, false); else PNSFM_C3D_DGRAD(4, false); }
+#undef PNSFM_C3D_DGRAD
   return check_launch(what);
 }
 
 int pnsfm_conv3d_backward_data(const float* dout, const float* w3, float* dp, int B, int D, int H, int W, int NF, void* stream) {
-  return conv3d_backward_data_impl(dout, w3, dp, B, D, H, W, NF, stream, "conv3d_backward_data", C3dRows{H, B, 0, 0});
+  return conv3d_backward_data_impl(dout, w3, dp, B, D, H, W, NF, stream, "conv3d_backward_data", C3dRows{H, B, 0, 0, W, 0});
 }
 
 // PNSFM_CONV3D_WGRAD_RING=0 = round 3's kernel (A/B switch).  (Measured and dropped, profiles/r04_ab_conv3d_wgrad_ring.txt: two
@@ -875,8 +897,9 @@ int pnsfm_conv3d_backward_data(const float* dout, const float* w3, float* dp, in
 static int wgrad_ring() { const char* e = getenv("PNSFM_CONV3D_WGRAD_RING"); return (e && e[0] == '0') ? 0 : 34; }
 
 static int conv3d_backward_weight_impl(const float* p, const float* dout, float* dw3, float* db3, int B, int D, int H,
-                                       int W, int NF, void* stream, const char* what, C3dRows rw) {
+                                       int W, int NF, void* stream, const char* what, C3dRows rw, int epi = 0) {
   if (!nf_ok(NF, what)) return -1;
+  if (epi & ~(PNSFM_WGRAD_EPI_ADD | PNSFM_WGRAD_EPI_TAPT)) { set_error("%s: unknown epilogue flags %d", what, epi); return -1; }
   hipStream_t s = (hipStream_t)stream;
   // run length along d per thread: as long as possible (amortises the block reduction) while the grid still gives every
   // CU a few blocks
@@ -884,7 +907,7 @@ static int conv3d_backward_weight_impl(const float* p, const float* dout, float*
   while (len > 12 && (long)B * (NF / 4) * ceil_div(D, len) * H * W < 4L * 256 * 256) len = ceil_div(len, 2);
   const int ring = wgrad_ring();
   const int pf = ring / 10, fpb = ring ? ring % 10 : 4;
-  if (rw.Ho != H && !ring) { set_error("%s: round 3's kernel reads whole frames only", what); return -1; }
+  if ((rw.Ho != H || rw.Wo != W) && !ring) { set_error("%s: round 3's kernel reads whole frames only", what); return -1; }
   if (ring && (size_t)D * H * W * 4 >= 0x7fffffffull) { set_error("%s: feature slab exceeds the 2 GiB buffer window", what); return -1; }
   len = ring ? ceil_div(len, pf) * pf : ceil_div(len, 3) * 3;       // whole trips of the unrolled loop
   const dim3 grid(ring ? ceil_div(ceil_div(ceil_div(D, len) * H * W, 62), 4) : ceil_div(ceil_div(D, len) * H * W, 256), NF / fpb, B);
@@ -897,14 +920,40 @@ static int conv3d_backward_weight_impl(const float* p, const float* dout, float*
   int e = check_launch(what);
   if (e) return e;
   PNSFM_LAUNCH(conv3d_wgrad_finish_kernel, dim3(NF * 28), dim3(64), 0, s, (const float*)part, dw3, db3, (int)(grid.x * grid.z),
-               (int)grid.y, fpb);
+               (int)grid.y, fpb, epi);
   return check_launch("conv3d_backward_weight_finish");
 }
 
 int pnsfm_conv3d_backward_weight(const float* p, const float* dout, float* dw3, float* db3, double* ws, int B, int D, int H,
                                  int W, int NF, void* stream) {
   (void)ws;     // (round 3's zero-filled fp64 atomics target; the per-block partials now live in the stream's scratch buffer)
-  return conv3d_backward_weight_impl(p, dout, dw3, db3, B, D, H, W, NF, stream, "conv3d_backward_weight", C3dRows{H, B, 0, 0});
+  return conv3d_backward_weight_impl(p, dout, dw3, db3, B, D, H, W, NF, stream, "conv3d_backward_weight", C3dRows{H, B, 0, 0, W, 0});
+}
+
+// ---- kernel composition of the collapsed packing block on the Conv2d weight itself: dout [B, NF*D, Hd, Wd] stands in the middle of an
+// (Hd + 2) x (Wd + 2) frame whose outer ring is zero and is never stored -- the window reads it as zero the way the frame's own edge
+// is read.  Same kernels, same operations per output as on the zero-padded tensor: bit-identical to it.
+int pnsfm_conv3d_backward_data_ring(const float* dout, const float* w3, float* dp, int B, int D, int Hd, int Wd, int NF, void* stream) {
+  if (Hd < 1 || Wd < 1) { set_error("conv3d_backward_data_ring: empty window %d x %d", Hd, Wd); return -1; }
+  return conv3d_backward_data_impl(dout, w3, dp, B, D, Hd + 2, Wd + 2, NF, stream, "conv3d_backward_data_ring", C3dRows{Hd, B, 1, 1, Wd, 1});
+}
+
+int pnsfm_conv3d_backward_weight_ring(const float* p, const float* dout, float* dw3, float* db3, int B, int D, int Hd, int Wd, int NF,
+                                      int epi, void* stream) {
+  if (Hd < 1 || Wd < 1) { set_error("conv3d_backward_weight_ring: empty window %d x %d", Hd, Wd); return -1; }
+  return conv3d_backward_weight_impl(p, dout, dw3, db3, B, D, Hd + 2, Wd + 2, NF, stream, "conv3d_backward_weight_ring",
+                                     C3dRows{Hd, B, 1, 1, Wd, 1}, epi);
+}
+
+// ---- transposed taps read in place (tapT: tap (dz, dy, dx) is w3[f][dz][dx][dy]) and the weight gradient's epilogue (epi:
+// PNSFM_WGRAD_EPI_ADD the finished sums are added to what dw3 / db3 hold, PNSFM_WGRAD_EPI_TAPT dw3 leaves in w3's own layout)
+int pnsfm_conv3d_backward_data_t(const float* dout, const float* w3, float* dp, int B, int D, int H, int W, int NF, int tapT, void* stream) {
+  return conv3d_backward_data_impl(dout, w3, dp, B, D, H, W, NF, stream, "conv3d_backward_data_t", C3dRows{H, B, 0, 0, W, 0}, tapT ? 1 : 0);
+}
+
+int pnsfm_conv3d_backward_weight_epi(const float* p, const float* dout, float* dw3, float* db3, int B, int D, int H, int W, int NF, int epi,
+                                     void* stream) {
+  return conv3d_backward_weight_impl(p, dout, dw3, db3, B, D, H, W, NF, stream, "conv3d_backward_weight_epi", C3dRows{H, B, 0, 0, W, 0}, epi);
 }
 
 // ---- border strips of the collapsed packing block: the Conv3d of [2B, D, S, w] strips for the 2r = S - 1 rows strip_select keeps
@@ -918,29 +967,51 @@ int pnsfm_conv3d_rows_folded(const float* p, const float* out, int W) {
   return ((pack3d_fold_mask() & PNSFM_FOLD_ROWS) && W % 4 == 0 && (((uintptr_t)p | (uintptr_t)out) & 15) == 0 && wgrad_ring()) ? 1 : 0;
 }
 
-int pnsfm_conv3d_forward_rows(const float* p, const float* w3, const float* b3, float* out, int B, int D, int S, int W, int NF, int Bh,
-                              void* stream) {
+static int conv3d_forward_rows_impl(const float* p, const float* w3, const float* b3, float* out, int B, int D, int S, int W, int NF, int Bh,
+                                    int tapT, void* stream) {
   if (!nf_ok(NF, "conv3d_forward_rows") || !rows_ok("conv3d_forward_rows", B, S, Bh)) return -1;
   if (W % 4 != 0 || (((uintptr_t)p | (uintptr_t)out) & 15) != 0) {
     set_error("conv3d_forward_rows: W %% 4 == 0 and 16-byte aligned tensors only (elsewhere: conv3d_forward, then select the rows)");
     return -1;
   }
-  const C3dRows rw = {S - 1, Bh, 0, 1};
+  const C3dRows rw = {S - 1, Bh, 0, 1, W, 0};
   const dim3 gq(ceil_div(D * rw.Ho * (W / 4), 256), 1, B);
-  if (NF == 8) PNSFM_LAUNCH((conv3d_fwd_x4_kernel<8>), gq, dim3(256), 0, (hipStream_t)stream, p, w3, b3, out, D, S, W, rw);
-  else PNSFM_LAUNCH((conv3d_fwd_x4_kernel<4>), gq, dim3(256), 0, (hipStream_t)stream, p, w3, b3, out, D, S, W, rw);
+  if (NF == 8) PNSFM_LAUNCH((conv3d_fwd_x4_kernel<8>), gq, dim3(256), 0, (hipStream_t)stream, p, w3, b3, out, D, S, W, rw, tapT);
+  else PNSFM_LAUNCH((conv3d_fwd_x4_kernel<4>), gq, dim3(256), 0, (hipStream_t)stream, p, w3, b3, out, D, S, W, rw, tapT);
   return check_launch("conv3d_forward_rows");
+}
+
+int pnsfm_conv3d_forward_rows(const float* p, const float* w3, const float* b3, float* out, int B, int D, int S, int W, int NF, int Bh,
+                              void* stream) {
+  return conv3d_forward_rows_impl(p, w3, b3, out, B, D, S, W, NF, Bh, 0, stream);
+}
+
+int pnsfm_conv3d_forward_rows_t(const float* p, const float* w3, const float* b3, float* out, int B, int D, int S, int W, int NF, int Bh,
+                                int tapT, void* stream) {
+  return conv3d_forward_rows_impl(p, w3, b3, out, B, D, S, W, NF, Bh, tapT ? 1 : 0, stream);
+}
+
+int pnsfm_conv3d_backward_data_rows_t(const float* dout, const float* w3, float* dp, int B, int D, int S, int W, int NF, int Bh, int tapT,
+                                      void* stream) {
+  if (!rows_ok("conv3d_backward_data_rows_t", B, S, Bh)) return -1;
+  return conv3d_backward_data_impl(dout, w3, dp, B, D, S, W, NF, stream, "conv3d_backward_data_rows_t", C3dRows{S - 1, Bh, 0, 1, W, 0}, tapT ? 1 : 0);
+}
+
+int pnsfm_conv3d_backward_weight_rows_epi(const float* p, const float* dout, float* dw3, float* db3, int B, int D, int S, int W, int NF, int Bh,
+                                          int epi, void* stream) {
+  if (!rows_ok("conv3d_backward_weight_rows_epi", B, S, Bh)) return -1;
+  return conv3d_backward_weight_impl(p, dout, dw3, db3, B, D, S, W, NF, stream, "conv3d_backward_weight_rows_epi", C3dRows{S - 1, Bh, 0, 1, W, 0}, epi);
 }
 
 int pnsfm_conv3d_backward_data_rows(const float* dout, const float* w3, float* dp, int B, int D, int S, int W, int NF, int Bh, void* stream) {
   if (!rows_ok("conv3d_backward_data_rows", B, S, Bh)) return -1;
-  return conv3d_backward_data_impl(dout, w3, dp, B, D, S, W, NF, stream, "conv3d_backward_data_rows", C3dRows{S - 1, Bh, 0, 1});
+  return conv3d_backward_data_impl(dout, w3, dp, B, D, S, W, NF, stream, "conv3d_backward_data_rows", C3dRows{S - 1, Bh, 0, 1, W, 0});
 }
 
 int pnsfm_conv3d_backward_weight_rows(const float* p, const float* dout, float* dw3, float* db3, int B, int D, int S, int W, int NF, int Bh,
                                       void* stream) {
   if (!rows_ok("conv3d_backward_weight_rows", B, S, Bh)) return -1;
-  return conv3d_backward_weight_impl(p, dout, dw3, db3, B, D, S, W, NF, stream, "conv3d_backward_weight_rows", C3dRows{S - 1, Bh, 0, 1});
+  return conv3d_backward_weight_impl(p, dout, dw3, db3, B, D, S, W, NF, stream, "conv3d_backward_weight_rows", C3dRows{S - 1, Bh, 0, 1, W, 0});
 }
 
 }  // extern "C"

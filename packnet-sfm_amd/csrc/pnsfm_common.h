@@ -269,6 +269,12 @@ int block_map_mode();      // api.hip: PNSFM_BLOCK_MAP = 0 (x fastest, round rob
 // pack3d.hip: PNSFM_PACK3D_FOLD / pnsfm_set_pack3d_fold -- which launch sequences of the packing / unpacking blocks run folded
 // (default and 1: all; 0: none; an even value is a mask of these bits, for per-kernel A/B runs)
 enum { PNSFM_FOLD_FWD = 2, PNSFM_FOLD_BIAS = 4, PNSFM_FOLD_ROWS = 8, PNSFM_FOLD_ALL = 14 };
+// epilogue of a weight-gradient launch (the masks of include/pnsfm.h, for files that do not include it): ADD = dst + finished sum
+// instead of a plain store; TAPT = the taps are stored swapped back, tap (ky, kx) at [kx][ky] (Conv3d: (dz, dy, dx) at [dz][dx][dy])
+#ifndef PNSFM_WGRAD_EPI_ADD
+#define PNSFM_WGRAD_EPI_ADD 1
+#define PNSFM_WGRAD_EPI_TAPT 2
+#endif
 int pack3d_fold_mask();
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
@@ -347,7 +353,7 @@ int wgrad3_total_tiles(int B, int H, int W);
 int wgrad3_WM(int Cout, int want);          // co tiles per workgroup (want: 0 = the most the layer fills, or 1 / 2 / 4)
 int wgrad3_base_blocks(int Cin, int Cout, int ks, int NT, int WM);
 int enqueue_wgrad3(const float* x, const float* dy, float* dw, float* dbias, int B, int Cin, int Cout, int H, int W, int ks,
-                   int split, int NT, int WM, hipStream_t stream, const ConvSrc* ms = nullptr, const ConvRows* rows = nullptr);
+                   int split, int NT, int WM, hipStream_t stream, const ConvSrc* ms = nullptr, const ConvRows* rows = nullptr, int epi = 0);
 
 // nine-taps-per-workgroup 3x3 weight gradient on the 16x16x32 MFMA (conv2d_wgrad4.hip).  cfg = WCI (ci tiles of 16 channels per
 // workgroup: 1 | 2) | TG << 4 (tile width in 8-pixel groups, 0 = library choice) | TR << 8 (tile rows, 0 = library choice)
@@ -357,7 +363,7 @@ int wgrad4_TR(int H, int want);
 int wgrad4_total_tiles(int B, int H, int W, int TG, int TR);
 int wgrad4_base_blocks(int Cin, int Cout, int WCI);
 int enqueue_wgrad4(const float* x, const float* dy, float* dw, float* dbias, int B, int Cin, int Cout, int H, int W, int split,
-                   int cfg, hipStream_t stream, const ConvSrc* ms = nullptr, const ConvRows* rows = nullptr);
+                   int cfg, hipStream_t stream, const ConvSrc* ms = nullptr, const ConvRows* rows = nullptr, int epi = 0);
 
 // more than 64 KB of dynamic LDS needs hipFuncSetAttribute once per kernel AND device: `mask` (one static per kernel
 // instantiation) remembers the devices already done (api.hip).  0 on success.

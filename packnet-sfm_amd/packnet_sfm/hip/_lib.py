@@ -59,6 +59,19 @@ SIGNATURES = {
     "pnsfm_conv3d_forward_rows": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "pnsfm_conv3d_backward_data_rows": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "pnsfm_conv3d_backward_weight_rows": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "pnsfm_conv3d_backward_data_ring": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "pnsfm_conv3d_backward_weight_ring": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "pnsfm_conv3d_forward_t": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "pnsfm_conv3d_backward_data_t": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "pnsfm_conv3d_backward_weight_epi": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "pnsfm_conv3d_forward_rows_t": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "pnsfm_conv3d_backward_data_rows_t": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "pnsfm_conv3d_backward_weight_rows_epi": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "pnsfm_conv2d_pack_tapt_supported": (_i, [_i, _i, _i]),
+    "pnsfm_conv2d_pack_weights_t": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
+    "pnsfm_conv2d_pack_item_fill_t": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i]),
+    "pnsfm_conv2d_backward_weight_epi": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "pnsfm_pack_bias_eff_backward_add": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "pnsfm_invdepth_act_forward": (_i, [_p, _p, _sz, _f, _p]),
     "pnsfm_invdepth_act_backward": (_i, [_p, _p, _p, _sz, _f, _p]),
     "pnsfm_pose_vec2mat_forward": (_i, [_p, _p, _i, _p]),

@@ -82,7 +82,10 @@ class PackedConvWeight:
         self.key_h16 = None
         self.shape_h16 = None
 
-    def get(self, weight, need_bwd):
+    def get(self, weight, need_bwd, tapT=False):
+        """tapT: the packed images of weight.transpose(2, 3), read from `weight` in place (the same bytes as packing a materialised
+        transpose: the key does not tell them apart).  Such a cache is never registered for the optimizer's batched re-pack, whose
+        tables hold one image pair per parameter."""
         if self.volatile:
             self._serial += 1
             key = ('volatile', self._serial)
@@ -98,13 +101,13 @@ class PackedConvWeight:
             if do_b and self.wp_bwd is not None and (self.wp_bwd.device != w.device):
                 self.wp_bwd = None
             f, b = ops.conv2d_pack(w.contiguous(), self.wp_fwd if do_f else None, self.wp_bwd if do_b else None,
-                                   want_fwd=do_f, want_bwd=do_b)
+                                   want_fwd=do_f, want_bwd=do_b, tapT=tapT)
             held = None if self.volatile else w
             if do_f:
                 self.wp_fwd, self.key_fwd, self._src_f = f, key, held
             if do_b:
                 self.wp_bwd, self.key_bwd, self._src_b = b, key, held
-            if not self.volatile and weight.is_leaf and weight.requires_grad:
+            if not self.volatile and not tapT and weight.is_leaf and weight.requires_grad:
                 _register_packed(self, weight)
         return self.wp_fwd, (self.wp_bwd if need_bwd else None)
 
@@ -225,7 +228,8 @@ class _WgradStream:
     engine's AccumulateGrad (a pointer hand-over, no kernel).  A non-leaf weight (the composed kernel of the collapsed
     packing block) or a parameter used by several nodes (that block's Conv2d / Conv3d weights) has its gradient read or
     accumulated by compute-stream kernels during the same backward pass: for those the weight gradient still runs on the
-    side stream next to the node's own data gradient, but the compute stream waits for it before the node returns.
+    side stream next to the node's own data gradient, but the compute stream waits for it before the node returns.  (The collapsed
+    packing block's parameters have an owner of their own where it applies -- _PackGrads -- and then stay in flight like the others.)
     """
     _env = os.environ.get('PNSFM_WGRAD_STREAM', '1')
     enabled = _env not in ('0', '')
@@ -375,6 +379,7 @@ class _WgradStream:
         cls._cb_task = None
         cls._join_pending()
         cls._uses.clear()
+        _PackGrads.end_of_backward()
 
     @classmethod
     def _join_pending(cls):
@@ -442,6 +447,122 @@ def _slots_for(weight, bias, usable):
     if tuple(sw.shape) != tuple(weight.shape) or (bias is not None and sb.numel() != bias.numel()):
         return None, None           # the parameter was re-shaped behind the optimizer's back: plain gradient path
     return sw, sb
+
+
+class _PackGrads:
+    """One owner for the gradients of the four parameters (W2, b2, W3, b3) of a collapsed packing block (PNSFM_PACK_WPATH, below).
+
+    Each of them is read by three nodes of the block -- the kernel composition, the row strips and the column strips -- so autograd
+    used to add three gradients per parameter with elementwise kernels (one of them through a transposed view), FlatAdam gathered
+    the sums into its arena with a copy, and the compute stream waited inside every node for a weight gradient on the side stream.
+    With an owner the FIRST contribution of a backward pass is written into the parameter's gradient slot (_slot_of; a fresh tensor
+    when no optimizer registered one), LATER ones are added there by the kernels' own epilogues (dst = dst + finished sum: the bits
+    of the elementwise add) and only the LAST node hands the tensor to autograd; the others return None.  The order of the
+    contributions is the order the engine runs the nodes in -- column strips, row strips, composition -- so (g1 + g2) + g3 is unchanged.
+
+    Two groups, each returned by its own last node: 'c2' = (W2, b2), 'c3' = (W3, b3).  Streams: a contribution on the side stream is
+    ordered behind everything on the compute stream by the fork (_WgradStream.run); one on the compute stream that follows one on
+    the side stream waits for it explicitly (before()).  The owner is made per forward call (layers01.py) and decides ONCE per
+    backward pass, at its first node, whether it is in charge: every parameter a leaf without .grad and without hooks (what
+    side_ok asks), and no other owner of the same parameters alive in the graph.  Otherwise every node returns its own gradient,
+    in the parameter's own layout, and autograd adds them as before."""
+    _live = {}          # id(parameter) -> owners made for it since the last end of a backward pass
+    _active = []        # owners in charge in the running backward pass (checked complete at its end)
+    passes = 0          # backward passes an owner was in charge of (tests)
+
+    def __init__(self, W2, b2, W3, b3):
+        self.params = (W2, b2, W3, b3)
+        self.expect = {'c2': 0, 'c3': 0}
+        self.left = None
+        self.task = None
+        self.on = False
+        self.dst = {'c2': None, 'c3': None}
+        self.side_dirty = False
+        for q in self.params:
+            if q is not None:
+                _PackGrads._live[id(q)] = _PackGrads._live.get(id(q), 0) + 1
+
+    def expect_node(self, *groups):
+        for g in groups:
+            self.expect[g] += 1
+
+    def begin(self):
+        """Called by every node's backward: is the owner in charge in this backward pass?"""
+        task = torch._C._current_graph_task_id()
+        if self.task != task:
+            self.task = task
+            self.left = dict(self.expect)
+            self.dst = {'c2': None, 'c3': None}
+            self.side_dirty = False
+            self.on = all(q is None or (q.is_leaf and q.grad is None and not q._backward_hooks and _PackGrads._live.get(id(q), 0) == 1)
+                          for q in self.params)
+            if self.on:
+                _PackGrads._active.append(self)
+                _PackGrads.passes += 1
+        return self.on
+
+    def dest(self, group):
+        """(weight destination, bias destination or None, first contribution?) of `group`."""
+        d = self.dst[group]
+        if d is not None:
+            return d[0], d[1], False
+        w, b = self.params[:2] if group == 'c2' else self.params[2:]
+        sw, sb = _slot_of(w), _slot_of(b)
+        if sw is not None and tuple(sw.shape) != tuple(w.shape):
+            sw = None
+        if sb is not None and sb.numel() != b.numel():
+            sb = None
+        dw = sw if sw is not None else torch.empty_like(w, memory_format=torch.contiguous_format)
+        db = None if b is None else (sb if sb is not None else torch.empty_like(b))
+        self.dst[group] = (dw, db)
+        return dw, db, True
+
+    def before(self, ref, on_side):
+        """Stream order of the contribution about to be enqueued for a tensor on ref's device: on the compute stream behind
+        contributions still running on the side stream."""
+        if on_side:
+            self.side_dirty = True
+        elif self.side_dirty and ref.is_cuda:
+            ops.stream_wait_stream(ops.launch_stream_raw(ref.device), _WgradStream.get(ref.device).cuda_stream)
+            self.side_dirty = False
+
+    def done(self, group):
+        """A node has enqueued its contribution to `group`: (dw, db) for autograd when it was the last one, else (None, None)."""
+        self.left[group] -= 1
+        if self.left[group] > 0:
+            return None, None
+        dw, db = self.dst[group]
+        self.dst[group] = None
+        # fresh view objects: AccumulateGrad adopts a gradient only if nobody else holds the tensor object
+        return dw.view(dw.shape), (None if db is None else db.view(db.shape))
+
+    @classmethod
+    def end_of_backward(cls):
+        act, cls._active = cls._active, []
+        cls._live.clear()
+        for o in act:
+            if o.left is not None and any(v > 0 for v in o.left.values()):
+                o.task = None
+                raise RuntimeError("collapsed packing block: a backward pass ended before every node had contributed its parameter "
+                                   "gradients (PNSFM_PACK_WPATH=0 runs the path without a gradient owner)")
+
+
+def pack_grad_owner(W2, b2, W3, b3, h, w):
+    """The gradient owner of a collapsed packing block's forward call on a packed map of h x w pixels, or None: the former path.
+    Needs autograd recording, four trainable leaf parameters, the packers' in-place tap transpose for the Conv2d (split-bf16 layers)
+    and the row-window Conv3d kernels for both strip directions."""
+    if not (_PACK_WPATH and torch.is_grad_enabled() and ops.conv3d_ring_ok()):
+        return None
+    for q in (W2, W3, b3):
+        if not (q.is_leaf and q.requires_grad and q.dtype == torch.float32):
+            return None
+    if b2 is not None and not (b2.is_leaf and b2.requires_grad):
+        return None
+    if get_conv_math() != 'bx3' or not ops.conv2d_pack_tapT_supported(W2.shape[1], W2.shape[0], W2.shape[2]):
+        return None
+    if not (ops.conv3d_rows_window_ok(w) and ops.conv3d_rows_window_ok(h)):
+        return None
+    return _PackGrads(W2, b2, W3, b3)
 
 
 def side_streams(device):
@@ -684,10 +805,13 @@ class Conv2dRowsFn(Function):
     every other convolution's."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, cache, r, recording=True):
+    def forward(ctx, x, weight, bias, cache, r, recording=True, tapT=False, owner=None):
         x = x.contiguous()
         need_dx = ctx.needs_input_grad[0]
-        wp_fwd, wp_bwd = cache.get(weight, need_dx)
+        wp_fwd, wp_bwd = cache.get(weight, need_dx, tapT=tapT)
+        ctx.tapT, ctx.owner = tapT, (owner if recording else None)
+        if ctx.owner is not None:
+            ctx.owner.expect_node('c2')
         Cout, Cin, ks, _ = weight.shape
         if ks // 2 != r or x.shape[1] != Cin:
             raise RuntimeError("conv2d_rows: weight %s does not fit r = %d, input %s" % (tuple(weight.shape), r, tuple(x.shape)))
@@ -706,19 +830,35 @@ class Conv2dRowsFn(Function):
         dy = dy.contiguous()
         want_w = bool(ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]))
         detached = _WgradStream.side_ok(*ctx.params)
+        epi = ops.WGRAD_EPI_TAPT if ctx.tapT else 0      # (the gradient leaves in the weight's own layout either way)
+        dgrad = (lambda: ops.conv2d_backward_data_rows(dy, wp_bwd, Cin, ks, r)) if ctx.needs_input_grad[0] else None
+        own = ctx.owner
+        if own is not None and own.begin():
+            # the block's gradient owner: written / added into the parameter's one gradient tensor, left in flight on the side stream
+            dwd, dbd, first = own.dest('c2')
+            if not first:
+                epi |= ops.WGRAD_EPI_ADD
+            own.before(dy, _WgradStream.use_for(dy))
+            dx, _, _ = _WgradStream.run_beside(
+                dy, True, True, lambda: ops.conv2d_backward_weight_rows(x, dy, ks, r, want_bias=has_bias, dw_out=dwd, db_out=dbd, epi=epi),
+                dgrad, (x, dy))
+            dw, db = own.done('c2')
+            return dx, dw, db, None, None, None, None, None
         sw, sb = _slots_for(ctx.params[0], ctx.params[1], detached and ctx.needs_input_grad[1])
         dx, dw, db = _WgradStream.run_beside(
-            dy, want_w, detached, lambda: ops.conv2d_backward_weight_rows(x, dy, ks, r, want_bias=has_bias, dw_out=sw, db_out=sb),
-            (lambda: ops.conv2d_backward_data_rows(dy, wp_bwd, Cin, ks, r)) if ctx.needs_input_grad[0] else None, (x, dy))
-        return dx, dw, db, None, None, None
+            dy, want_w, detached, lambda: ops.conv2d_backward_weight_rows(x, dy, ks, r, want_bias=has_bias, dw_out=sw, db_out=sb, epi=epi),
+            dgrad, (x, dy))
+        return dx, dw, db, None, None, None, None, None
 
 
-def conv2d_rows(x, weight, bias, cache, r):
-    """Frame rows of conv2d over the batched border strips (Conv2dRowsFn): x [2B, Cin, 2r, w] -> [2B, Cout, r, w]."""
+def conv2d_rows(x, weight, bias, cache, r, tapT=False, owner=None):
+    """Frame rows of conv2d over the batched border strips (Conv2dRowsFn): x [2B, Cin, 2r, w] -> [2B, Cout, r, w].
+    tapT: convolve with weight.transpose(2, 3), read in place (packer flag; the weight gradient comes back in weight's own layout).
+    owner: the block's gradient owner (_PackGrads) or None."""
     if x.dtype == torch.float16:
         raise NotImplementedError("conv2d_rows: the fp16 forward keeps the full-strip form (conv2d + strip rows dropped at the paste)")
     _h16_input(x, weight)
-    return Conv2dRowsFn.apply(x, weight, bias, cache, r, torch.is_grad_enabled())
+    return Conv2dRowsFn.apply(x, weight, bias, cache, r, torch.is_grad_enabled(), tapT, owner)
 
 
 # Round 5: gradient taps.  A tensor read by a convolution AND by something else (the encoder feature that is also a decoder skip input;
@@ -1086,9 +1226,14 @@ class ComposePackWeightFn(Function):
 
     @staticmethod
     def forward(ctx, W2, W3, recording=True):
-        W2pad = torch.nn.functional.pad(W2.detach(), (1, 1, 1, 1)).contiguous()      # [C, 8D, k+2, k+2]
         w3 = W3.detach().contiguous()
-        Weff = ops.conv3d_backward_data(W2pad, w3)                                    # [C, D, k+2, k+2]
+        ctx.ring = _ring_on()
+        if ctx.ring:                                                                  # the ring of zeros is implicit (ComposePackParamsFn)
+            W2pad = W2.detach().contiguous()                                          # [C, 8D, k, k]
+            Weff = ops.conv3d_backward_data_ring(W2pad, w3)                           # [C, D, k+2, k+2]
+        else:
+            W2pad = torch.nn.functional.pad(W2.detach(), (1, 1, 1, 1)).contiguous()  # [C, 8D, k+2, k+2]
+            Weff = ops.conv3d_backward_data(W2pad, w3)
         ctx.save_for_backward(W2pad, w3)
         ctx.params = (W2, W3)
         _WgradStream.note_use(recording, W2, W3)
@@ -1104,12 +1249,32 @@ class ComposePackWeightFn(Function):
         if ctx.needs_input_grad[0]:
             dW2 = ops.conv3d_forward(g, w3, torch.zeros(w3.shape[0], device=g.device, dtype=g.dtype))[:, :, 1:-1, 1:-1].contiguous()
         if ctx.needs_input_grad[1]:
-            dW3, _ = ops.conv3d_backward_weight(g, W2pad)
+            dW3, _ = ops.conv3d_backward_weight_ring(g, W2pad) if ctx.ring else ops.conv3d_backward_weight(g, W2pad)
         return dW2, dW3, None
 
 
 def compose_pack_weight(W2, W3):
     return ComposePackWeightFn.apply(W2, W3, torch.is_grad_enabled())
+
+
+# The weight path of the collapsed packing block without ATen passes (PNSFM_PACK_WPATH=0 / set_pack_wpath(False): the former path, the
+# A/B switch and the reference of tests/pack_wpath_cases.py).  The kernel composition and its Conv3d weight gradient read
+# the Conv2d weight itself -- the zero ring around its taps is the stencil kernels' window check, not a padded copy (a fill and a copy
+# of [C, d*D, k+2, k+2] per block and step, and twice the bytes under both stencils); the column strips read the transposed taps of W2 /
+# W3 in place (packer and stencil flags) instead of materialised transposes; and the block's four parameters have one gradient owner
+# (_PackGrads) whose contributions meet inside the weight-gradient kernels' epilogues instead of in autograd's adds.  Bit-identical.
+_PACK_WPATH = os.environ.get('PNSFM_PACK_WPATH', '1') != '0'
+
+
+def set_pack_wpath(on):
+    """Returns the previous setting."""
+    global _PACK_WPATH
+    prev, _PACK_WPATH = _PACK_WPATH, bool(on)
+    return prev
+
+
+def _ring_on():
+    return _PACK_WPATH and ops.conv3d_ring_ok()
 
 
 class ComposePackParamsFn(Function):
@@ -1118,16 +1283,25 @@ class ComposePackParamsFn(Function):
         bias_eff[co] = b2[co] + sum_f b3[f] * sum_{ci,taps} W2[co, f*D + ci, taps]
 
     (a Conv3d bias is a constant plane, which the Conv2d turns into a per-channel constant away from the border).  One node instead
-    of two plus a chain of reshape / sum / mul / add: forward = pad, composition stencil, one bias kernel; backward = the two
-    stencils and two small kernels that also fold the bias path's rank-one term into dW2 (no second gradient to accumulate)."""
+    of two plus a chain of reshape / sum / mul / add: forward = composition stencil (on W2 inside an implicit ring of zeros; under
+    PNSFM_PACK_WPATH=0 on a padded copy), one bias kernel; backward = the two stencils and two small kernels that also fold the bias
+    path's rank-one term into dW2 (no second gradient to accumulate)."""
 
     @staticmethod
-    def forward(ctx, W2, b2, W3, b3, recording=True):
+    def forward(ctx, W2, b2, W3, b3, recording=True, owner=None):
         W2d, w3, b3d = W2.detach().contiguous(), W3.detach().contiguous(), b3.detach().contiguous()
-        W2pad = torch.nn.functional.pad(W2d, (1, 1, 1, 1))                            # [C, d*D, k+2, k+2]
-        Weff = ops.conv3d_backward_data(W2pad, w3)                                    # [C, D, k+2, k+2]
+        ctx.ring = _ring_on()
+        ctx.owner = owner if (recording and ctx.ring) else None
+        if ctx.owner is not None:
+            ctx.owner.expect_node('c2', 'c3')
+        if ctx.ring:
+            W2src = W2d                                                               # [C, d*D, k, k]: the ring is never stored
+            Weff = ops.conv3d_backward_data_ring(W2d, w3)                             # [C, D, k+2, k+2]
+        else:
+            W2src = torch.nn.functional.pad(W2d, (1, 1, 1, 1))                        # [C, d*D, k+2, k+2]
+            Weff = ops.conv3d_backward_data(W2src, w3)
         bias_eff, Ssum = ops.pack_bias_eff_forward(W2d, None if b2 is None else b2.detach().contiguous(), b3d)
-        ctx.save_for_backward(W2pad, w3, b3d, Ssum)
+        ctx.save_for_backward(W2src, w3, b3d, Ssum)
         ctx.params = (W2, W3)
         ctx.k = W2.shape[-1]
         _WgradStream.note_use(recording, W2, W3)
@@ -1136,27 +1310,44 @@ class ComposePackParamsFn(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, gW, gb):
-        W2pad, w3, b3, Ssum = ctx.saved_tensors
+        W2src, w3, b3, Ssum = ctx.saved_tensors
         _WgradStream.side_ok(*ctx.params)            # bookkeeping only: this node always runs on the compute stream
         need_W2, need_b2, need_W3, need_b3 = ctx.needs_input_grad[:4]
-        C = W2pad.shape[0]
+        C, k = W2src.shape[0], ctx.k
         if gW is None:
-            gW = W2pad.new_zeros((C, W2pad.shape[1] // w3.shape[0], ctx.k + 2, ctx.k + 2))
+            gW = W2src.new_zeros((C, W2src.shape[1] // w3.shape[0], k + 2, k + 2))
         if gb is None:
-            gb = W2pad.new_zeros((C,))
+            gb = W2src.new_zeros((C,))
         gW, gb = gW.contiguous(), gb.contiguous()
         dW2 = dW3 = db3 = None
+        own = ctx.owner
+        if own is not None and own.begin():
+            # the block's gradient owner (_PackGrads): this node's gradients join the strips' inside its kernels; it runs on the compute
+            # stream, behind the strips' contributions on the side stream
+            dW2d, db2d, first2 = own.dest('c2')
+            dW3d, db3d, first3 = own.dest('c3')
+            own.before(gW, False)
+            if first2 or first3:
+                # (the composition is the block's first node and therefore the last of its backward pass: both strips have contributed)
+                raise RuntimeError("collapsed packing block: the composition's backward ran before the border strips'")
+            full = ops.conv3d_forward(gW, w3, None)
+            ops.pack_bias_eff_backward_add(gb, Ssum, b3, full, k, db3d, dW2d, db2d)
+            ops.conv3d_backward_weight_ring(gW, W2src, dw3_out=dW3d, db3_out=None, epi=ops.WGRAD_EPI_ADD)
+            dW2, db2 = own.done('c2')
+            dW3, db3 = own.done('c3')
+            return dW2, db2, dW3, db3, None, None
         if need_W2 or need_b3:
             # the composition's gradient on the padded taps; cropped and completed by the bias path's term in the same kernel
-            full = ops.conv3d_forward(gW, w3, None) if need_W2 else W2pad       # (W2pad: right shape, not read when dW2 is not wanted)
-            db3, dW2 = ops.pack_bias_eff_backward(gb, Ssum, b3, full, ctx.k, want_db3=need_b3, want_dW2=need_W2)
+            # (not wanted: a tensor of the right shape that the kernel does not read)
+            full = ops.conv3d_forward(gW, w3, None) if need_W2 else W2src.new_empty((C, W2src.shape[1], k + 2, k + 2))
+            db3, dW2 = ops.pack_bias_eff_backward(gb, Ssum, b3, full, k, want_db3=need_b3, want_dW2=need_W2)
         if need_W3:
-            dW3, _ = ops.conv3d_backward_weight(gW, W2pad)
-        return dW2, (gb if need_b2 else None), dW3, db3, None
+            dW3, _ = ops.conv3d_backward_weight_ring(gW, W2src) if ctx.ring else ops.conv3d_backward_weight(gW, W2src)
+        return dW2, (gb if need_b2 else None), dW3, db3, None, None
 
 
-def compose_pack_params(W2, b2, W3, b3):
-    return ComposePackParamsFn.apply(W2, b2, W3, b3, torch.is_grad_enabled())
+def compose_pack_params(W2, b2, W3, b3, owner=None):
+    return ComposePackParamsFn.apply(W2, b2, W3, b3, torch.is_grad_enabled(), owner)
 
 
 def _R(op, dst, src=None):
@@ -1287,10 +1478,13 @@ class Conv3dStripRowsFn(Function):
     row of S, and the copy + zero-fill of its backward, do not exist.  Bit-identical to the two nodes."""
 
     @staticmethod
-    def forward(ctx, p, w3, b3, B, recording=True):
-        out = ops.conv3d_forward_rows(p, w3.detach().contiguous(), b3.detach().contiguous(), B)
+    def forward(ctx, p, w3, b3, B, recording=True, tapT=False, owner=None):
+        out = ops.conv3d_forward_rows(p, w3.detach().contiguous(), b3.detach().contiguous(), B, tapT=tapT)
         ctx.save_for_backward(p, w3)
         ctx.params, ctx.B = (w3, b3), B
+        ctx.tapT, ctx.owner = tapT, (owner if recording else None)
+        if ctx.owner is not None:
+            ctx.owner.expect_node('c3')
         _WgradStream.note_use(recording, w3, b3)
         return out
 
@@ -1302,20 +1496,34 @@ class Conv3dStripRowsFn(Function):
         dout = dout.contiguous()
         want_w = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
         detached = _WgradStream.side_ok(*ctx.params)
+        tapT = ctx.tapT
+        epi = ops.WGRAD_EPI_TAPT if tapT else 0      # (the gradient leaves in w3's own layout either way)
+        dgrad = (lambda: ops.conv3d_backward_data_rows(dout, w3.detach().contiguous(), S, B, tapT=tapT)) if ctx.needs_input_grad[0] else None
+        own = ctx.owner
+        if own is not None and own.begin():      # the block's gradient owner: see Conv2dRowsFn.backward
+            dwd, dbd, first = own.dest('c3')
+            if not first:
+                epi |= ops.WGRAD_EPI_ADD
+            own.before(p, _WgradStream.use_for(p))
+            dp, _, _ = _WgradStream.run_beside(p, True, True, lambda: ops.conv3d_backward_weight_rows(p, dout, B, dw3_out=dwd, db3_out=dbd, epi=epi),
+                                               dgrad, (p, dout))
+            dw3, db3 = own.done('c3')
+            return dp, dw3, db3, None, None, None, None
         # (p: the side-stream rule goes by the pixel count of the S-row frame, as in Conv3d1to8Fn)
-        dp, dw3, db3 = _WgradStream.run_beside(p, want_w, detached, lambda: ops.conv3d_backward_weight_rows(p, dout, B),
-                                               (lambda: ops.conv3d_backward_data_rows(dout, w3.detach().contiguous(), S, B))
-                                               if ctx.needs_input_grad[0] else None, (p, dout))
-        return dp, dw3, db3, None, None
+        dp, dw3, db3 = _WgradStream.run_beside(p, want_w, detached, lambda: ops.conv3d_backward_weight_rows(p, dout, B, epi=epi), dgrad, (p, dout))
+        return dp, dw3, db3, None, None, None, None
 
 
-def conv3d_1to8_rows(p, w3, b3, B, r):
-    """strip_select(conv3d_1to8(p, w3, b3), B, r, 2) of the border strips p [2B, D, 2r + 1, w]."""
+def conv3d_1to8_rows(p, w3, b3, B, r, tapT=False, owner=None):
+    """strip_select(conv3d_1to8(p, w3, b3), B, r, 2) of the border strips p [2B, D, 2r + 1, w].
+    tapT: with w3.transpose(3, 4), read in place (row-window kernels only); owner: the block's gradient owner (_PackGrads) or None."""
     if p.dtype != torch.float16 and p.shape[2] == 2 * r + 1:
         p = p.contiguous()
         if ops.conv3d_rows_folded(p):
             _h16_input(p, w3)
-            return Conv3dStripRowsFn.apply(p, w3, b3, B, torch.is_grad_enabled())
+            return Conv3dStripRowsFn.apply(p, w3, b3, B, torch.is_grad_enabled(), tapT, owner)
+    if tapT or owner is not None:
+        raise RuntimeError("conv3d_1to8_rows: transposed taps and gradient owners run on the row-window kernels only")
     return strip_select(conv3d_1to8(p, w3, b3), B, r, 2)
 
 

@@ -4,6 +4,7 @@ Every wrapper validates dtype / contiguity / device, allocates outputs with torc
 allocator and stream owner -- plumbing, not compute) and enqueues the HIP kernels on torch's current stream.
 """
 import ctypes
+import os
 import threading
 
 import torch
@@ -114,8 +115,17 @@ def conv2d_packed_sizes(Cin, Cout, ks):
     return (int(lib.pnsfm_conv2d_packed_elems_fwd(Cin, Cout, ks)), int(lib.pnsfm_conv2d_packed_elems_bwd(Cin, Cout, ks)))
 
 
-def conv2d_pack(w, wp_fwd=None, wp_bwd=None, want_fwd=True, want_bwd=True):
-    """w: [Cout, Cin, k, k] (reference layout) -> packed forward / backward-data weights."""
+WGRAD_EPI_ADD, WGRAD_EPI_TAPT = 1, 2      # PNSFM_WGRAD_EPI_* of include/pnsfm.h
+
+
+def conv2d_pack_tapT_supported(Cin, Cout, ks):
+    """Do the packers read this layer's transposed taps in place (conv2d_pack(tapT=True), a (w, pf, pb, True) table entry)?"""
+    return bool(_lib.get().pnsfm_conv2d_pack_tapt_supported(Cin, Cout, ks))
+
+
+def conv2d_pack(w, wp_fwd=None, wp_bwd=None, want_fwd=True, want_bwd=True, tapT=False):
+    """w: [Cout, Cin, k, k] (reference layout) -> packed forward / backward-data weights.  tapT: the images of w.transpose(2, 3),
+    read in place."""
     _chk(w, wp_fwd, wp_bwd); _f32(w)
     Cout, Cin, ks, ks2 = w.shape
     assert ks == ks2
@@ -124,14 +134,19 @@ def conv2d_pack(w, wp_fwd=None, wp_bwd=None, want_fwd=True, want_bwd=True):
         wp_fwd = torch.empty(nf, dtype=torch.float32, device=w.device)
     if want_bwd and wp_bwd is None:
         wp_bwd = torch.empty(nb, dtype=torch.float32, device=w.device)
-    rc = _lib.get().pnsfm_conv2d_pack_weights(_ptr(w), _ptr(wp_fwd if want_fwd else None),
-                                              _ptr(wp_bwd if want_bwd else None), Cin, Cout, ks, _stream(w))
+    if tapT:
+        rc = _lib.get().pnsfm_conv2d_pack_weights_t(_ptr(w), _ptr(wp_fwd if want_fwd else None),
+                                                    _ptr(wp_bwd if want_bwd else None), Cin, Cout, ks, 1, _stream(w))
+    else:
+        rc = _lib.get().pnsfm_conv2d_pack_weights(_ptr(w), _ptr(wp_fwd if want_fwd else None),
+                                                  _ptr(wp_bwd if want_bwd else None), Cin, Cout, ks, _stream(w))
     _lib.check(rc, "conv2d_pack_weights")
     return wp_fwd, wp_bwd
 
 
 def conv2d_pack_table_build(entries, device):
-    """entries: [(w, wp_fwd, wp_bwd)] with w [Cout, Cin, k, k] and packed buffers of conv2d_packed_sizes().  Returns
+    """entries: [(w, wp_fwd, wp_bwd)] (or (w, wp_fwd, wp_bwd, tapT): the images of w.transpose(2, 3), read in place) with w
+    [Cout, Cin, k, k] and packed buffers of conv2d_packed_sizes().  Returns
     (table tensor on `device`, number of items, total blocks, indices of the entries the table covers) -- entries whose shape
     does not take the split-bf16 layout in both directions are left out (pack them with conv2d_pack)."""
     import ctypes
@@ -139,10 +154,14 @@ def conv2d_pack_table_build(entries, device):
     isz = int(lib.pnsfm_conv2d_pack_item_bytes())
     host = (ctypes.c_ubyte * (isz * max(1, len(entries))))()
     n, blocks, covered = 0, 0, []
-    for i, (w, pf, pb) in enumerate(entries):
+    for i, ent in enumerate(entries):
+        w, pf, pb = ent[:3]
         _chk(w, pf, pb); _f32(w, pf, pb)
         Cout, Cin, ks, _ = w.shape
-        rc = lib.pnsfm_conv2d_pack_item_fill(ctypes.addressof(host) + n * isz, _ptr(w), _ptr(pf), _ptr(pb), Cin, Cout, ks, blocks)
+        if len(ent) > 3 and ent[3]:
+            rc = lib.pnsfm_conv2d_pack_item_fill_t(ctypes.addressof(host) + n * isz, _ptr(w), _ptr(pf), _ptr(pb), Cin, Cout, ks, blocks, 1)
+        else:
+            rc = lib.pnsfm_conv2d_pack_item_fill(ctypes.addressof(host) + n * isz, _ptr(w), _ptr(pf), _ptr(pb), Cin, Cout, ks, blocks)
         if rc < 0:
             _lib.check(rc, "conv2d_pack_item_fill")
         if rc > 0:
@@ -316,8 +335,11 @@ def conv2d_backward_data_rows(dy, wp_bwd, Cin, ks, r):
     return dx
 
 
-def conv2d_backward_weight_rows(x, dy, ks, r, want_bias=True, dw_out=None, db_out=None):
-    """Weight (and bias) gradient of conv2d_forward_rows; dw_out / db_out: gradient slots, as conv2d_backward_weight."""
+def conv2d_backward_weight_rows(x, dy, ks, r, want_bias=True, dw_out=None, db_out=None, epi=0):
+    """Weight (and bias) gradient of conv2d_forward_rows; dw_out / db_out: gradient slots, as conv2d_backward_weight.
+    epi (WGRAD_EPI_*): ADD -- the gradient is added to what dw_out / db_out hold (needs them); TAPT -- dw with its taps swapped back."""
+    if (epi & WGRAD_EPI_ADD) and dw_out is None:
+        raise RuntimeError("conv2d_backward_weight_rows: adding into a gradient needs the destination")
     _chk(x, dy); _f32(x, dy)
     B2, Cin, W = _rows_shape(x, r, 2 * r, "conv2d_backward_weight_rows")
     if _rows_shape(dy, r, r, "conv2d_backward_weight_rows")[::2] != (B2, W):
@@ -330,8 +352,12 @@ def conv2d_backward_weight_rows(x, dy, ks, r, want_bias=True, dw_out=None, db_ou
         dw, db = dw_out.view(dw_out.shape), (db_out.view(db_out.shape) if want_bias else None)
     else:
         dw, db = _alloc_dw_db(Cout, Cin, ks, want_bias, x.device)
-    rc = _lib.get().pnsfm_conv2d_backward_weight_rows(_ptr(x), _ptr(dy), _ptr(dw), _ptr(db), B2, Cin, Cout, r, 2 * r, W, ks, r, B2 // 2,
-                                                      _stream(x))
+    if epi:
+        rc = _lib.get().pnsfm_conv2d_backward_weight_epi(_ptr(x), _ptr(dy), _ptr(dw), _ptr(db), B2, Cin, Cout, r, 2 * r, W, ks, r, B2 // 2,
+                                                         int(epi), _stream(x))
+    else:
+        rc = _lib.get().pnsfm_conv2d_backward_weight_rows(_ptr(x), _ptr(dy), _ptr(dw), _ptr(db), B2, Cin, Cout, r, 2 * r, W, ks, r, B2 // 2,
+                                                          _stream(x))
     _lib.check(rc, "conv2d_backward_weight_rows")
     return dw, db
 
@@ -476,39 +502,97 @@ def conv3d_rows_folded(p):
     return S >= 3 and S % 2 == 1 and p.dtype == torch.float32 and bool(_lib.get().pnsfm_conv3d_rows_folded(_ptr(p), _ptr(p), p.shape[3]))
 
 
-def conv3d_forward_rows(p, w3, b3, Bh):
-    """Border strips p [2B,D,S,w], S = 2r + 1: the Conv3d rows strip_select(., dim=2) keeps, [2B,NF*D,2r,w]."""
+def conv3d_rows_window_ok(W):
+    """conv3d_rows_folded for 16-byte aligned strips of width W that do not exist yet."""
+    return bool(_lib.get().pnsfm_conv3d_rows_folded(None, None, int(W)))
+
+
+def conv3d_forward_rows(p, w3, b3, Bh, tapT=False):
+    """Border strips p [2B,D,S,w], S = 2r + 1: the Conv3d rows strip_select(., dim=2) keeps, [2B,NF*D,2r,w].
+    tapT: with the taps of w3.transpose(3, 4), read in place."""
     _chk(p, w3, b3); _f32(p, w3, b3)
     B, D, S, W = p.shape
     nf = _nf_of(w3)
     out = torch.empty((B, nf * D, S - 1, W), dtype=torch.float32, device=p.device)
-    _lib.check(_lib.get().pnsfm_conv3d_forward_rows(_ptr(p), _ptr(w3), _ptr(b3), _ptr(out), B, D, S, W, nf, Bh, _stream(p)),
-               "conv3d_forward_rows")
+    if tapT:
+        rc = _lib.get().pnsfm_conv3d_forward_rows_t(_ptr(p), _ptr(w3), _ptr(b3), _ptr(out), B, D, S, W, nf, Bh, 1, _stream(p))
+    else:
+        rc = _lib.get().pnsfm_conv3d_forward_rows(_ptr(p), _ptr(w3), _ptr(b3), _ptr(out), B, D, S, W, nf, Bh, _stream(p))
+    _lib.check(rc, "conv3d_forward_rows")
     return out
 
 
-def conv3d_backward_data_rows(dout, w3, S, Bh):
+def conv3d_backward_data_rows(dout, w3, S, Bh, tapT=False):
     _chk(dout, w3); _f32(dout, w3)
     B, DF, Ho, W = dout.shape
     nf = _nf_of(w3)
     D = DF // nf
     assert Ho == S - 1
     dp = torch.empty((B, D, S, W), dtype=torch.float32, device=dout.device)
-    _lib.check(_lib.get().pnsfm_conv3d_backward_data_rows(_ptr(dout), _ptr(w3), _ptr(dp), B, D, S, W, nf, Bh, _stream(dout)),
-               "conv3d_backward_data_rows")
+    if tapT:
+        rc = _lib.get().pnsfm_conv3d_backward_data_rows_t(_ptr(dout), _ptr(w3), _ptr(dp), B, D, S, W, nf, Bh, 1, _stream(dout))
+    else:
+        rc = _lib.get().pnsfm_conv3d_backward_data_rows(_ptr(dout), _ptr(w3), _ptr(dp), B, D, S, W, nf, Bh, _stream(dout))
+    _lib.check(rc, "conv3d_backward_data_rows")
     return dp
 
 
-def conv3d_backward_weight_rows(p, dout, Bh):
+def _dw3_dst(p, nf, dw3_out, db3_out, epi, what):
+    if dw3_out is None:
+        if epi & WGRAD_EPI_ADD:
+            raise RuntimeError("%s: adding into a gradient needs the destination" % what)
+        return (torch.empty((nf, 1, 3, 3, 3), dtype=torch.float32, device=p.device), torch.empty((nf,), dtype=torch.float32, device=p.device))
+    _chk(dw3_out, db3_out); _f32(dw3_out, db3_out)
+    if dw3_out.numel() != nf * 27 or (db3_out is not None and db3_out.numel() != nf):
+        raise RuntimeError("%s: gradient slot has the wrong shape" % what)
+    # (fresh view objects: see conv2d_backward_weight; db3_out None: the bias gradient is not stored)
+    return dw3_out.view(nf, 1, 3, 3, 3), (None if db3_out is None else db3_out.view(nf))
+
+
+def conv3d_backward_weight_rows(p, dout, Bh, dw3_out=None, db3_out=None, epi=0):
+    """epi (WGRAD_EPI_*): ADD -- the gradients are added to what dw3_out / db3_out hold; TAPT -- dw3 with its (y, x) taps swapped back."""
     _chk(p, dout); _f32(p, dout)
     B, D, S, W = p.shape
     nf = dout.shape[1] // D
     assert dout.shape[2] == S - 1
-    dw3 = torch.empty((nf, 1, 3, 3, 3), dtype=torch.float32, device=p.device)
-    db3 = torch.empty((nf,), dtype=torch.float32, device=p.device)
-    _lib.check(_lib.get().pnsfm_conv3d_backward_weight_rows(_ptr(p), _ptr(dout), _ptr(dw3), _ptr(db3), B, D, S, W, nf, Bh, _stream(p)),
-               "conv3d_backward_weight_rows")
+    dw3, db3 = _dw3_dst(p, nf, dw3_out, db3_out, epi, "conv3d_backward_weight_rows")
+    if epi:
+        rc = _lib.get().pnsfm_conv3d_backward_weight_rows_epi(_ptr(p), _ptr(dout), _ptr(dw3), _ptr(db3), B, D, S, W, nf, Bh, int(epi), _stream(p))
+    else:
+        rc = _lib.get().pnsfm_conv3d_backward_weight_rows(_ptr(p), _ptr(dout), _ptr(dw3), _ptr(db3), B, D, S, W, nf, Bh, _stream(p))
+    _lib.check(rc, "conv3d_backward_weight_rows")
     return dw3, db3
+
+
+def conv3d_backward_data_ring(dout, w3):
+    """conv3d_backward_data(F.pad(dout, (1, 1, 1, 1)), w3) without the padded tensor: dout [B,NF*D,Hd,Wd] -> [B,D,Hd+2,Wd+2]."""
+    _chk(dout, w3); _f32(dout, w3)
+    B, DF, Hd, Wd = dout.shape
+    nf = _nf_of(w3)
+    D = DF // nf
+    dp = torch.empty((B, D, Hd + 2, Wd + 2), dtype=torch.float32, device=dout.device)
+    _lib.check(_lib.get().pnsfm_conv3d_backward_data_ring(_ptr(dout), _ptr(w3), _ptr(dp), B, D, Hd, Wd, nf, _stream(dout)),
+               "conv3d_backward_data_ring")
+    return dp
+
+
+def conv3d_backward_weight_ring(p, dout, dw3_out=None, db3_out=None, epi=0):
+    """conv3d_backward_weight(p, F.pad(dout, (1, 1, 1, 1))) without the padded tensor: p [B,D,Hd+2,Wd+2], dout [B,NF*D,Hd,Wd].
+    dw3_out / db3_out / epi: as conv3d_backward_weight_rows."""
+    _chk(p, dout); _f32(p, dout)
+    B, D, H, W = p.shape
+    nf = dout.shape[1] // D
+    assert tuple(dout.shape) == (B, nf * D, H - 2, W - 2)
+    dw3, db3 = _dw3_dst(p, nf, dw3_out, db3_out, epi, "conv3d_backward_weight_ring")
+    _lib.check(_lib.get().pnsfm_conv3d_backward_weight_ring(_ptr(p), _ptr(dout), _ptr(dw3), _ptr(db3), B, D, H - 2, W - 2, nf, int(epi),
+                                                            _stream(p)), "conv3d_backward_weight_ring")
+    return dw3, db3
+
+
+def conv3d_ring_ok():
+    """Do the two *_ring ops apply?  The window is read through the buffer descriptors of the default weight-gradient kernel;
+    PNSFM_CONV3D_WGRAD_RING=0 (round 3's kernel, an A/B switch) reads whole frames only."""
+    return os.environ.get('PNSFM_CONV3D_WGRAD_RING', '1')[:1] != '0'
 
 
 # ------------------------------------------------------------------- composed packing convolution: bias
@@ -522,6 +606,18 @@ def pack_bias_eff_forward(W2, b2, b3):
     _lib.check(_lib.get().pnsfm_pack_bias_eff_forward(_ptr(W2), _ptr(b2), _ptr(b3), _ptr(Ssum), _ptr(bias), C, d, blk, _stream(W2)),
                "pack_bias_eff_forward")
     return bias, Ssum
+
+
+def pack_bias_eff_backward_add(g, Ssum, b3, dWeff_full, k, db3, dW2, db2=None):
+    """pack_bias_eff_backward adding into its destinations: db3 [d] and dW2 [C, d*D, k, k] receive dst + (the plain result), db2 [C]
+    (optional) db2 + g."""
+    _chk(g, Ssum, b3, dWeff_full, db3, dW2, db2); _f32(g, Ssum, b3, dWeff_full, db3, dW2, db2)
+    C, d = Ssum.shape
+    D = dWeff_full.shape[1] // d
+    assert tuple(dWeff_full.shape) == (C, d * D, k + 2, k + 2) and g.numel() == C
+    assert db3.numel() == d and dW2.numel() == C * d * D * k * k and (db2 is None or db2.numel() == C)
+    _lib.check(_lib.get().pnsfm_pack_bias_eff_backward_add(_ptr(g), _ptr(Ssum), _ptr(b3), _ptr(dWeff_full), _ptr(db3), _ptr(dW2), _ptr(db2), C, d,
+                                                           D, k, _stream(g)), "pack_bias_eff_backward_add")
 
 
 def pack_bias_eff_backward(g, Ssum, b3, dWeff_full, k, want_db3=True, want_dW2=True):

@@ -261,21 +261,28 @@ class PackLayerConv3d(nn.Module):
         k = self.conv.kernel_size
         r, S = k // 2, 2 * (k // 2) + 1
         B, _, h, w = P.shape
+        lr_t = bool(self.lr_transposed)
+        rows = bool(self.strip_frame_rows)
+        # one owner for the gradients of the four parameters, each read by the composition, the row strips and the column strips
+        # (HF._PackGrads: the contributions meet inside the kernels instead of in ATen adds and a gather copy); None: the former path
+        own = HF.pack_grad_owner(W2, b2, W3, b3, h, w) if (lr_t and rows) else None
         # interior: one (k+2)x(k+2) conv with the composed kernel; its bias is b2 + sum over ALL taps of W2 * b3
-        W_eff, bias_eff = HF.compose_pack_params(W2, b2, W3, b3)
+        W_eff, bias_eff = HF.compose_pack_params(W2, b2, W3, b3, owner=own)
         # border frame (r pixels): original formula on strips of 2r+1 packed rows / columns (top+bottom and left+right
         # are batched together); only rows/cols whose Conv3d neighbourhood lies inside the strip are kept.  The three
         # helper Functions do the strip gather / select / paste without full-size zero-fills and adds in backward.
-        lr_t = bool(self.lr_transposed)
-        rows = bool(self.strip_frame_rows)
         P_main, tb, lr = HF.pack_border_split(P, S, lr_t)
         y = HF.conv2d(P_main, W_eff, bias_eff, self._eff_packed)
-        s_tb = HF.conv3d_1to8_rows(tb, W3, b3, B, r)                             # [2B, 32C, 2r, w]: the rows strip_select keeps
+        s_tb = HF.conv3d_1to8_rows(tb, W3, b3, B, r, owner=own)                  # [2B, 32C, 2r, w]: the rows strip_select keeps
         # [2B, C, r, w] (the frame rows only) or [2B, C, 2r, w]
-        o_tb = HF.conv2d_rows(s_tb, W2, b2, base._packed, r) if rows else base(s_tb)
-        if lr_t:
-            # transposed space: strips [2B, C, S, h], Conv3d taps (dz, dx, dy), Conv2d taps (kx, ky); the result [2B, C, 2r | r, h] is pasted
-            # through a transposed view (autograd carries the weight gradients back through the two transpose views)
+        o_tb = HF.conv2d_rows(s_tb, W2, b2, base._packed, r, owner=own) if rows else base(s_tb)
+        if lr_t and own is not None:
+            # transposed space: strips [2B, C, S, h], Conv3d taps (dz, dx, dy), Conv2d taps (kx, ky), both read in place from W3 / W2 (the
+            # kernels' and the packer's tap-transpose flag); the weight gradients come back in the parameters' own layout
+            z = HF.conv3d_1to8_rows(lr, W3, b3, B, r, tapT=True, owner=own)
+            o_lr = HF.conv2d_rows(z, W2, b2, self._lr_packed, r, tapT=True, owner=own)
+        elif lr_t:
+            # ... through materialised transposes (autograd carries the weight gradients back through the two transpose views)
             z = HF.conv3d_1to8_rows(lr, W3.transpose(3, 4), b3, B, r)
             o_lr = (HF.conv2d_rows(z, W2.transpose(2, 3), b2, self._lr_packed, r) if rows else
                     HF.conv2d(z, W2.transpose(2, 3), b2, self._lr_packed))
