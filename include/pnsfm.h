@@ -741,6 +741,45 @@ int pnsfm_act_crop_backward(const float* dy, const float* y, float* dz, int N, i
                             void* stream);
 int pnsfm_affine(const float* x, float* y, size_t n, float s, float t, void* stream);
 
+/* ---- fp16 forward: ResNet networks (csrc/conv2d_h16g.h, csrc/resnet.h), since ABI version 9 -------------------------------------------
+ * The evaluation / inference forward of DepthResNet in fp16, under the numerics contract of "fp16 forward" above.  In eval mode a
+ * BatchNorm is a per-channel affine, and reflection padding, nearest up-sampling and the channel concatenation are index maps: all of
+ * them live INSIDE the convolution, so there is no fp16 batchnorm_act / reflect_pad1 / act_crop / affine and no padded intermediate map.
+ * pnsfm_conv2d_forward_h16g: y = act(scale[m] conv(G(x), w)[m] + shift[m] + res), rounded once to fp16.  The descriptor is a HOST struct:
+ *   x[i] [B][C[i]][H >> up[i]][W >> up[i]] fp16 (x[1], x[2] nullable when their C is 0): their channel concatenation on the H x W grid,
+ *   source i read at (gy >> up[i], gx >> up[i]) (up in {0, 1}: nearest 2x; H and W even when a source is up-sampled); wp from
+ *   pnsfm_conv2d_pack_weights_h16; padding ks / 2, zero (pad_reflect == 0) or reflect (-1 -> 1, H -> H - 2, on the up-sampled coordinate;
+ *   H, W >= 2 and > ks / 2, else an error); pre != 0: every in-bounds input value is replaced by x pre_a + pre_b rounded once to fp16, padding stays 0;
+ *   stride in {1, 2}, ks in {1, 3, 5, 7}; y [B][Cout][Ho][Wo], Ho = (H + 2 (ks / 2) - ks) / stride + 1; scale, shift fp32 [Cout], nullable
+ *   (1 and 0); res fp16 of y's shape, nullable; act 0 none, 1 ELU, 2 ReLU, 3 DISP p0 + p1 sigmoid.  With stride 1, zero padding and no
+ *   scale / res / act / pre / up it gives pnsfm_conv2d_forward_h16's bits.  K splits as in pnsfm_conv2d_forward_h16
+ *   (pnsfm_set_h16_max_split), the second stage applying the same epilogue function.  pnsfm_conv2d_last_config: {10, NT, MT, WM,
+ *   K splits, tile width, workgroups, LDS bytes}.
+ * pnsfm_bn_fold_h16: fp16 gamma, beta, running_mean, running_var [C] -> out fp32 [2][C] = scale | shift, scale = gamma / sqrt(var + eps),
+ *   shift = beta - mean scale, computed in fp64, rounded once each.
+ * pnsfm_maxpool3x3s2_forward_h16: pnsfm_maxpool3x3s2_forward on fp16 x / y, without the arg-max plane (same tie and NaN rule). */
+typedef struct {
+  const void* x[3];
+  int C[3];
+  int up[3];
+  const void* wp;
+  const float* scale;
+  const float* shift;
+  const void* res;
+  void* y;
+  int B, Cout, H, W, ks, stride, pad_reflect, act;
+  float p0, p1;
+  int pre;
+  float pre_a, pre_b;
+} pnsfm_conv_h16g;
+int pnsfm_conv2d_forward_h16g(const pnsfm_conv_h16g* desc, void* stream);
+/* Stride-2 patches of pnsfm_conv2d_forward_h16g in LDS: != 0 (default) even columns first, odd columns behind them (a one-pixel read
+ * pitch); 0 the plain row.  Same bits either way.  Returns the previous setting. */
+int pnsfm_set_h16g_deinterleave(int on);
+int pnsfm_bn_fold_h16(const void* gamma, const void* beta, const void* running_mean, const void* running_var, double eps, float* out, int C,
+                      void* stream);
+int pnsfm_maxpool3x3s2_forward_h16(const void* x, void* y, int N, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,7 @@
 //                   7  split-bf16, ping-pong workgroup   conv2d_bx3pp_kernel        (conv2d_bx3pp.h)
 //                   8  split-bf16, 1x1 without LDS       conv1x1_bx3_kernel         (conv2d_bx3_1x1.h)
 //                   9  fp16 forward (inference)          conv2d_h16.h, included at the end
+//                  10  fp16 forward, gather + epilogue    conv2d_h16g.h, included behind it (ResNet networks)
 //   dispatch      enqueue_conv (one launch of a given geometry), launch_conv (conv_tune_key -> decision -> geometry -> launch) and its autotuner
 //   packers       pack_weights_kernel and the batched pack tables
 //   weight grad   sum_slabs_kernel, the stem and the generic f32 kernels; the tap-major, split-bf16 and nine-taps kernels live in
@@ -2688,3 +2689,4 @@ int pnsfm_tune_shipped_entries(void) {
 }  // extern "C"
 
 #include "conv2d_h16.h"      // fp16 forward (evaluation / inference): variant 9
+#include "conv2d_h16g.h"     // fp16 forward with a gather and a fused epilogue (ResNet networks): variant 10

@@ -697,3 +697,69 @@ int pnsfm_affine(const float* x, float* y, size_t n, float s, float t, void* str
 }
 
 }  // extern "C"
+
+// ---- fp16 forward (evaluation / inference of DepthResNet; include/pnsfm.h "fp16 forward: ResNet networks") ----------------------------
+// The BatchNorms of the fp16 forward are folded into the convolutions' epilogues (conv2d_h16g.h): what is left here is the fold itself
+// and the max pooling, which moves fp16 values (bit-equal to F.max_pool2d on the same values).
+namespace pnsfm {
+
+// one thread per channel: scale = gamma / sqrt(var + eps), shift = beta - mean scale, in fp64; out [2][C] fp32
+__global__ void __launch_bounds__(256) bn_fold_h16_kernel(const pnsfm_h16* __restrict__ gamma, const pnsfm_h16* __restrict__ beta,
+                                                          const pnsfm_h16* __restrict__ mean, const pnsfm_h16* __restrict__ var, double eps,
+                                                          float* __restrict__ out, int C) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= C) return;
+  const double scale = (double)(float)gamma[c] / sqrt((double)(float)var[c] + eps);
+  out[c] = (float)scale;
+  out[C + c] = (float)((double)(float)beta[c] - (double)(float)mean[c] * scale);
+}
+
+__global__ void __launch_bounds__(256) maxpool3x3s2_fwd_h16_kernel(const pnsfm_h16* __restrict__ x, pnsfm_h16* __restrict__ y, long long total,
+                                                                   int H, int W, int Ho, int Wo) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int ox = (int)(i % Wo);
+  const long long t = i / Wo;
+  const int oy = (int)(t % Ho);
+  const pnsfm_h16* p = x + (t / Ho) * (long long)H * W;
+  pnsfm_h16 best = (pnsfm_h16)0.f;
+  bool any = false;
+  for (int ky = 0; ky < 3; ++ky) {
+    const int iy = 2 * oy - 1 + ky;
+    if (iy < 0 || iy >= H) continue;
+    for (int kx = 0; kx < 3; ++kx) {
+      const int ix = 2 * ox - 1 + kx;
+      if (ix < 0 || ix >= W) continue;
+      const pnsfm_h16 v = p[(size_t)iy * W + ix];
+      const float vf = (float)v;
+      if (!any || vf > (float)best || vf != vf) { best = v; any = true; }
+    }
+  }
+  y[i] = best;
+}
+
+}  // namespace pnsfm
+
+extern "C" {
+
+int pnsfm_bn_fold_h16(const void* gamma, const void* beta, const void* running_mean, const void* running_var, double eps, float* out, int C,
+                      void* stream) {
+  using namespace pnsfm;
+  if (C <= 0 || !gamma || !beta || !running_mean || !running_var || !out) { set_error("bn_fold_h16: bad arguments C=%d", C); return -1; }
+  PNSFM_LAUNCH(bn_fold_h16_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const pnsfm_h16*)gamma,
+               (const pnsfm_h16*)beta, (const pnsfm_h16*)running_mean, (const pnsfm_h16*)running_var, eps, out, C);
+  return check_launch("bn_fold_h16");
+}
+
+int pnsfm_maxpool3x3s2_forward_h16(const void* x, void* y, int N, int H, int W, void* stream) {
+  using namespace pnsfm;
+  if (N <= 0 || H <= 0 || W <= 0 || !x || !y) { set_error("maxpool3x3s2_forward_h16: bad arguments N=%d H=%d W=%d", N, H, W); return -1; }
+  const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+  const long long total = (long long)N * Ho * Wo;
+  if (planes_ok("maxpool3x3s2_forward_h16", (long long)N * H * W)) return -1;
+  PNSFM_LAUNCH(maxpool3x3s2_fwd_h16_kernel, dim3(blocks_of(total)), dim3(256), 0, (hipStream_t)stream, (const pnsfm_h16*)x, (pnsfm_h16*)y, total,
+               H, W, Ho, Wo);
+  return check_launch("maxpool3x3s2_forward_h16");
+}
+
+}  // extern "C"

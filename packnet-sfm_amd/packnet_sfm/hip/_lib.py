@@ -105,6 +105,10 @@ SIGNATURES = {
     "pnsfm_upsample_nearest_forward_h16": (_i, [_p, _p, _i, _i, _i, _i, _p]),
     "pnsfm_invdepth_conv_forward_h16": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _f, _p]),
     "pnsfm_region_ops_h16": (_i, [_p, _i, _p]),
+    "pnsfm_conv2d_forward_h16g": (_i, [_p, _p]),
+    "pnsfm_set_h16g_deinterleave": (_i, [_i]),
+    "pnsfm_bn_fold_h16": (_i, [_p, _p, _p, _p, ctypes.c_double, _p, _i, _p]),
+    "pnsfm_maxpool3x3s2_forward_h16": (_i, [_p, _p, _i, _i, _i, _p]),
     # depth evaluation (post-processing and metrics; fp32 or fp16 storage by a flag per tensor)
     "pnsfm_post_process_inv_depth": (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _p]),
     "pnsfm_depth_metrics_ws_bytes": (_sz, [_i]),

@@ -81,6 +81,9 @@ class PackedConvWeight:
         self.bias_h16 = None
         self.key_h16 = None
         self.shape_h16 = None
+        self.fold_h16 = None          # fp16 forward of the ResNet networks: the folded BatchNorm behind the convolution
+        self.key_fold_h16 = None
+        self._src_fold_h16 = None
 
     def get(self, weight, need_bwd, tapT=False):
         """tapT: the packed images of weight.transpose(2, 3), read from `weight` in place (the same bytes as packing a materialised
@@ -129,6 +132,18 @@ class PackedConvWeight:
             self.shape_h16 = tuple(weight.shape)
             self.key_h16 = key
         return self.wp_h16, self.bias_h16
+
+    def get_fold_h16(self, bn):
+        """fp32 [2, C] scale | shift of an eval-mode fp16 BatchNorm2d behind this layer's convolution (ops.bn_fold_h16), re-folded only
+        when one of its four tensors changed: the key is key_of each, and aliases of them are held for the reason the class comment
+        gives."""
+        four = (bn.weight, bn.bias, bn.running_mean, bn.running_var)
+        key = tuple(self.key_of(t) for t in four) + (bn.eps,)
+        if self.key_fold_h16 != key:
+            self._src_fold_h16 = tuple(t.detach() for t in four)
+            self.fold_h16 = ops.bn_fold_h16(*(t.detach().contiguous() for t in four), bn.eps)
+            self.key_fold_h16 = key
+        return self.fold_h16
 
 
 # ---- batched re-pack: every conv weight of the model in ONE launch, right after the optimizer step ----------------------------
@@ -674,6 +689,47 @@ def conv2d_h16_composed(P, W_eff, bias_eff, cache, key):
         raise RuntimeError("conv2d_h16_composed: no packed weight for these parameters")
     Cout, _, ks, _ = cache.shape_h16
     return ops.conv2d_forward_h16((P.contiguous(),), cache.wp_h16, cache.bias_h16, Cout, ks)
+
+
+def conv2d_h16_fused(xs, weight, cache, *, stride=1, pad='zeros', up=1, bias=None, bn=None, res=None, act=ops.ACT_NONE, disp=(0., 1.),
+                     pre_affine=None):
+    """The fp16 forward's convolution of the ResNet networks, everything around it included, in one launch (csrc/conv2d_h16g.h):
+    act(bn(conv(pad(cat(upsample(xs))) * a + b, weight) + bias) + res).  xs: a tensor or up to three (their channel concatenation), each
+    up-sampled by `up` (one factor, or one per source) first; pad: 'zeros' | 'reflect' of k // 2; bn: an nn.BatchNorm2d in eval mode
+    (folded into a per-channel scale and shift, cached in `cache`); res: fp16 of the output's shape; pre_affine: (a, b)."""
+    xs = tuple(xs) if isinstance(xs, (tuple, list)) else (xs,)
+    ups = tuple(up) if isinstance(up, (tuple, list)) else (up,) * len(xs)
+    if pad not in ('zeros', 'reflect'):
+        raise ValueError("conv2d_h16_fused: pad must be 'zeros' or 'reflect', got %r" % (pad,))
+    bn_params = () if bn is None else (bn.weight, bn.bias, bn.running_mean, bn.running_var)
+    for t in xs + (res,):
+        if t is not None and t.dtype != torch.float16:
+            _h16_input(t, weight, bias, *bn_params)
+            raise RuntimeError("conv2d_h16_fused: float16 activations only, got %s" % t.dtype)
+    if bn is not None:
+        if bn.training or not bn.track_running_stats or bn.running_mean is None or not bn.affine:
+            raise NotImplementedError("fp16 BatchNorm runs with running statistics only (evaluation / inference): call .eval(); "
+                                      "training needs float32")
+        if bias is not None:
+            raise ValueError("conv2d_h16_fused: a bias and a BatchNorm behind one convolution are not supported")
+    _h16_params(weight, bias, *bn_params)
+    Cout, Cin, ks, _ = weight.shape
+    if sum(t.shape[1] for t in xs) != Cin:
+        raise RuntimeError("conv2d: inputs have %d channels, weight expects %d" % (sum(t.shape[1] for t in xs), Cin))
+    wp, b32 = cache.get_h16(weight, bias)
+    scale = shift = None
+    if bn is not None:
+        fold = cache.get_fold_h16(bn)
+        scale, shift = fold[0], fold[1]
+    elif b32 is not None:
+        shift = b32
+    n = len(xs)
+
+    def run(*a):
+        return ops.conv2d_forward_h16g(tuple(t.contiguous() for t in a[:n]), wp, Cout, ks, stride=stride, reflect=(pad == 'reflect'),
+                                       ups=ups, scale=scale, shift=shift, res=None if a[n] is None else a[n].contiguous(), act=act,
+                                       disp=disp, pre_affine=pre_affine)
+    return _h16_run(run, *xs, res, weight, bias, *bn_params[:2])
 
 
 # ---- the stride-1 conv nodes (Conv2dFn, ConvGnActFn): what their backward bodies share once dy exists ---------------------------------
@@ -1694,7 +1750,8 @@ def upsample_nearest(x, size=None, scale_factor=None):
 
 
 # ---- ResNet networks (csrc/resnet.h): dense BatchNorm (+ residual, ReLU), max pooling, reflection pad, activation + crop -----------------
-_RESNET_NO_H16 = "%s has no fp16 kernels: the fp16 forward covers the depth networks PackNet01 / PackNetSlim01 only; run it in float32"
+_RESNET_NO_H16 = ("%s has no fp16 kernel: in the fp16 forward (evaluation / inference) the BatchNorm, the reflection pad, the crop with "
+                  "its activation and the input affine live inside the convolution (conv2d_h16_fused); run this op in float32")
 
 
 def _no_h16(what, *tensors):
@@ -1760,7 +1817,8 @@ class MaxPool3x3s2Fn(Function):
 
 
 def maxpool3x3s2(x):
-    _no_h16('maxpool3x3s2', x)
+    if x.dtype == torch.float16:
+        return _h16_run(lambda t: ops.maxpool3x3s2_forward_h16(t.contiguous()), x)
     return MaxPool3x3s2Fn.apply(x)
 
 
@@ -1840,6 +1898,8 @@ def conv3x3_reflect(xs, weight, bias, cache, act=ops.ACT_ELU, up=1, disp=(0.0, 1
     if tuple(weight.shape[2:]) != (3, 3):
         raise ValueError("conv3x3_reflect: 3x3 weights only, got %s" % (tuple(weight.shape),))
     first = xs[0] if isinstance(xs, (tuple, list)) else xs
+    if first.dtype == torch.float16:        # fp16 forward: pad, up-sampling, concatenation, bias and activation in ONE launch
+        return conv2d_h16_fused(xs, weight, cache, pad='reflect', up=up, bias=bias, act=act, disp=disp)
     s0 = up[0] if isinstance(up, (tuple, list)) else up
     W = s0 * first.shape[3]
     # a padded map wider than 320 columns whose width is no multiple of 32 does not fit the convolution kernels' tiles (KITTI's 642):

@@ -1621,6 +1621,95 @@ def region_ops_h16(items):
         _lib.check(_lib.get().pnsfm_region_ops_h16(ctypes.byref(arr), len(chunk), _stream(ref)), "region_ops_h16")
 
 
+# ---- fp16 forward: ResNet networks (include/pnsfm.h) ------------------------------------------------------------------------------
+class _ConvH16G(ctypes.Structure):          # mirrors pnsfm_conv_h16g (include/pnsfm.h)
+    _fields_ = [('x', ctypes.c_void_p * 3), ('C', ctypes.c_int * 3), ('up', ctypes.c_int * 3), ('wp', ctypes.c_void_p),
+                ('scale', ctypes.c_void_p), ('shift', ctypes.c_void_p), ('res', ctypes.c_void_p), ('y', ctypes.c_void_p),
+                ('B', ctypes.c_int), ('Cout', ctypes.c_int), ('H', ctypes.c_int), ('W', ctypes.c_int), ('ks', ctypes.c_int),
+                ('stride', ctypes.c_int), ('pad_reflect', ctypes.c_int), ('act', ctypes.c_int), ('p0', ctypes.c_float),
+                ('p1', ctypes.c_float), ('pre', ctypes.c_int), ('pre_a', ctypes.c_float), ('pre_b', ctypes.c_float)]
+
+
+def conv2d_h16g_out_shape(xs, ups, Cout, ks, stride):
+    B = xs[0].shape[0]
+    H, W = xs[0].shape[2] * ups[0], xs[0].shape[3] * ups[0]
+    R = ks // 2
+    return B, Cout, (H + 2 * R - ks) // stride + 1, (W + 2 * R - ks) // stride + 1
+
+
+def conv2d_forward_h16g(xs, wp, Cout, ks, stride=1, reflect=False, ups=None, scale=None, shift=None, res=None, act=ACT_NONE,
+                        disp=(0.0, 1.0), pre_affine=None, out=None):
+    """y = act(scale * conv(G(xs), w) + shift + res) in ONE launch (two with a K split): xs 1..3 fp16 NCHW tensors, source i up-sampled by
+    ups[i] in {1, 2} onto the common H x W grid and concatenated along the channels; zero or reflect padding of ks // 2; stride 1 | 2;
+    scale / shift fp32 [Cout] or None; res fp16 of the output's shape or None; pre_affine (a, b): in-bounds inputs become
+    fp16(fma(x, a, b)).  out: a contiguous fp16 tensor of the output's shape to write into."""
+    xs = tuple(xs)
+    if not 1 <= len(xs) <= 3:
+        raise RuntimeError("conv2d_forward_h16g: 1 to 3 input tensors")
+    ups = (1,) * len(xs) if ups is None else tuple(int(u) for u in ups)
+    if len(ups) != len(xs) or any(u not in (1, 2) for u in ups):
+        raise ValueError("conv2d_forward_h16g: one up-sampling factor (1 | 2) per source, got %s for %d sources" % (ups, len(xs)))
+    _chk(*xs, wp, scale, shift, res, out); _h16(*xs, wp, res, out); _f32(scale, shift)
+    shape = conv2d_h16g_out_shape(xs, ups, Cout, ks, stride)
+    B, H, W = xs[0].shape[0], xs[0].shape[2] * ups[0], xs[0].shape[3] * ups[0]
+    for t, u in zip(xs, ups):
+        if t.dim() != 4 or t.shape[0] != B or (t.shape[2] * u, t.shape[3] * u) != (H, W):
+            raise RuntimeError("conv2d_forward_h16g: inputs of different batch / (up-sampled) spatial sizes")
+    if reflect and (H < 2 or W < 2 or H <= ks // 2 or W <= ks // 2):
+        raise ValueError("conv2d_forward_h16g: reflection padding needs an input larger than the pad (and at least 2 x 2), got %d x %d"
+                         % (H, W))
+    for v, n in ((scale, 'scale'), (shift, 'shift')):
+        if v is not None and v.numel() != Cout:
+            raise RuntimeError("conv2d_forward_h16g: %s must have %d elements" % (n, Cout))
+    if res is not None and tuple(res.shape) != shape:
+        raise RuntimeError("conv2d_forward_h16g: residual of shape %s, output %s" % (tuple(res.shape), shape))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float16, device=xs[0].device)
+    elif tuple(out.shape) != shape:
+        raise RuntimeError("conv2d_forward_h16g: out of shape %s, output %s" % (tuple(out.shape), shape))
+    d = _ConvH16G()
+    for i, (t, u) in enumerate(zip(xs, ups)):
+        d.x[i], d.C[i], d.up[i] = t.data_ptr(), t.shape[1], u - 1
+    d.wp, d.y = wp.data_ptr(), out.data_ptr()
+    d.scale = None if scale is None else scale.data_ptr()
+    d.shift = None if shift is None else shift.data_ptr()
+    d.res = None if res is None else res.data_ptr()
+    d.B, d.Cout, d.H, d.W, d.ks, d.stride, d.pad_reflect, d.act = B, Cout, H, W, ks, stride, 1 if reflect else 0, int(act)
+    d.p0, d.p1 = float(disp[0]), float(disp[1])
+    if pre_affine is not None:
+        d.pre, d.pre_a, d.pre_b = 1, float(pre_affine[0]), float(pre_affine[1])
+    _lib.check(_lib.get().pnsfm_conv2d_forward_h16g(ctypes.byref(d), _stream(xs[0])), "conv2d_forward_h16g")
+    return out
+
+
+def bn_fold_h16(gamma, beta, running_mean, running_var, eps, out=None):
+    """fp16 [C] x 4 -> fp32 [2, C]: scale = gamma / sqrt(var + eps) | shift = beta - mean * scale, computed in fp64."""
+    _chk(gamma, beta, running_mean, running_var, out); _h16(gamma, beta, running_mean, running_var); _f32(out)
+    C = gamma.numel()
+    if any(t.numel() != C for t in (beta, running_mean, running_var)):
+        raise RuntimeError("bn_fold_h16: the four tensors must have one length")
+    if out is None:
+        out = torch.empty((2, C), dtype=torch.float32, device=gamma.device)
+    elif tuple(out.shape) != (2, C):
+        raise RuntimeError("bn_fold_h16: out must be [2, %d]" % C)
+    _lib.check(_lib.get().pnsfm_bn_fold_h16(_ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var), float(eps), _ptr(out), C,
+                                            _stream(gamma)), "bn_fold_h16")
+    return out
+
+
+def maxpool3x3s2_forward_h16(x, out=None):
+    """x [..., H, W] fp16 -> y [..., Ho, Wo] fp16 (no arg-max plane: forward only)."""
+    _chk(x, out); _h16(x, out)
+    N, H, W = _planes(x, "maxpool3x3s2")
+    shape = tuple(x.shape[:-2]) + ((H - 1) // 2 + 1, (W - 1) // 2 + 1)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float16, device=x.device)
+    elif tuple(out.shape) != shape:
+        raise RuntimeError("maxpool3x3s2_forward_h16: out of shape %s, output %s" % (tuple(out.shape), shape))
+    _lib.check(_lib.get().pnsfm_maxpool3x3s2_forward_h16(_ptr(x), _ptr(out), N, H, W, _stream(x)), "maxpool3x3s2_forward_h16")
+    return out
+
+
 def conv2d_last_config():
     out = (ctypes.c_int * 8)()
     _lib.get().pnsfm_conv2d_last_config(out)

@@ -5,6 +5,8 @@ ImageNet weights, which come from torchvision -- imported only then), `forward(r
 training mode, the full-resolution one in eval mode}, parameters and buffers under encoder.encoder.* and decoder.decoder.*, so the
 model-zoo checkpoints load.  '50' (Bottleneck blocks) raises NotImplementedError.
 The depth range (0.1 .. 100 m) is folded into the decoder's output activation: 0.01 + 9.99 sigmoid(.).
+In eval mode the network also runs in fp16 (`.half()`, fp16 input): 35 launches of the gathering convolution of csrc/conv2d_h16g.h and one
+max pooling for version '18'; fp16 in training mode raises NotImplementedError (call .eval()).
 """
 from functools import partial
 

@@ -113,7 +113,7 @@ class PackNetSAN01(nn.Module):
     def forward(self, rgb, input_depth=None, **kwargs):
         if rgb.dtype == torch.float16 or (input_depth is not None and input_depth.dtype == torch.float16):
             raise NotImplementedError('PackNetSAN01 has no fp16 kernels (sparse depth branch): the fp16 forward covers PackNet01 / '
-                                      'PackNetSlim01 only; run PackNetSAN01 in float32')
+                                      'PackNetSlim01 / DepthResNet; run PackNetSAN01 in float32')
         if not self.training:
             inv_depths, _ = self.run_network(rgb, input_depth)
             return {'inv_depths': inv_depths}

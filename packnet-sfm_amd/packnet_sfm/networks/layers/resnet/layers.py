@@ -4,7 +4,9 @@ Stands in for the reference's packnet_sfm/networks/layers/resnet/layers.py: `Con
 conv.{weight, bias}), `ConvBlock` (Conv3x3 + ELU; parameters conv.conv.{weight, bias}), `upsample` (nearest x2) and `disp_to_depth`.
 A Conv3x3 runs as reflect_pad1 -> the zero-pad "same" MFMA convolution on the padded map -> a crop of the one-pixel frame
 (HF.conv3x3_reflect); the crop is fused with whatever activation follows, and the 2x up-sampling and the channel concatenation in front
-of the decoder's second convolution are folded into the padding kernel.
+of the decoder's second convolution are folded into the padding kernel.  On fp16 inputs (evaluation / inference) the whole Conv3x3 --
+up-sampling, concatenation, reflection pad, convolution, bias and activation -- is ONE launch of the gathering convolution
+(HF.conv2d_h16_fused, csrc/conv2d_h16g.h).
 """
 import torch.nn as nn
 

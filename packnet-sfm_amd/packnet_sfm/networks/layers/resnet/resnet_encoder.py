@@ -14,6 +14,9 @@ backward-data launch.  The stride-2 convolutions inside the blocks (up to 256 ->
 weight gradient through the stride-1 kernel on the zero-upsampled gradient (HF.conv2d_stride2(wgrad_s1=True)): the strided
 weight-gradient kernel cannot hold such a layer's patch in LDS.
 
+fp16 (evaluation / inference, eval mode only): BatchNorm, residual, ReLU and the input normalisation are folded into the convolutions
+(HF.conv2d_h16_fused, csrc/conv2d_h16g.h): the stem is one launch, a BasicBlock two, or three with its stride-2 shortcut.
+
 Initialisation: the distributions of the reference (convolutions kaiming-normal over fan-out, BatchNorm 1 / 0, fc at nn.Linear's
 default), created in torchvision's order; parity of the random stream with torchvision itself is not pinned by a test.
 """
@@ -39,7 +42,17 @@ class BasicBlock(nn.Module):
         self.stride = stride
         self._packed = [HF.PackedConvWeight() for _ in range(3)]
 
+    def _forward_h16(self, x):
+        """fp16 eval: conv1 + bn1 + ReLU | the 1x1 shortcut + its bn | conv2 + bn2 + residual + ReLU, one launch each."""
+        out = HF.conv2d_h16_fused(x, self.conv1.weight, self._packed[0], stride=self.stride, bn=self.bn1, act=_ops.ACT_RELU)
+        if self.downsample is not None:
+            conv, bn = self.downsample[0], self.downsample[1]
+            x = HF.conv2d_h16_fused(x, conv.weight, self._packed[2], stride=conv.stride[0], bn=bn)
+        return HF.conv2d_h16_fused(out, self.conv2.weight, self._packed[1], bn=self.bn2, res=x, act=_ops.ACT_RELU)
+
     def forward(self, x):
+        if x.dtype == torch.float16:
+            return self._forward_h16(x)
         if self.stride == 1:
             out, x = HF.conv2d_tap(x, self.conv1.weight, None, self._packed[0])
         else:
@@ -142,11 +155,34 @@ class ResnetEncoder(nn.Module):
         if pretrained:
             load_imagenet_state_dict(self.encoder, _imagenet_state_dict(num_layers), num_input_images)
 
+    def _forward_h16(self, image):
+        """fp16 eval: the stem ((x - 0.45) / 0.225 while staging, 7x7 stride 2, bn1, ReLU) in one launch, the max pooling in one, three
+        per block with a shortcut convolution and two per block without: 21 launches for ResNet18."""
+        e = self.encoder
+        stem = HF.conv2d_h16_fused(image, e.conv1.weight, e._packed, stride=2, bn=e.bn1, act=_ops.ACT_RELU,
+                                   pre_affine=(1.0 / 0.225, -0.45 / 0.225))
+        self.features = [stem, e.layer1(HF.maxpool3x3s2(stem))]
+        for layer in (e.layer2, e.layer3, e.layer4):
+            self.features.append(layer(self.features[-1]))
+        return self.features
+
     def forward(self, input_image):
         e = self.encoder
-        if input_image.dtype == torch.float16 or e.conv1.weight.dtype == torch.float16:
-            raise NotImplementedError('ResnetEncoder has no fp16 kernels: the fp16 forward covers the depth networks PackNet01 / '
-                                      'PackNetSlim01 only; run it in float32')
+        h16_in, h16_net = input_image.dtype == torch.float16, e.conv1.weight.dtype == torch.float16
+        if h16_in or h16_net:
+            # decided here, before any kernel or library call: pose networks and batch statistics have no fp16 path
+            if e.conv1.weight.shape[1] != 3:
+                raise NotImplementedError('the multi-image ResnetEncoder (PoseResNet) has no fp16 path: fp16 covers the evaluation / '
+                                          'inference forward of the depth networks; run it in float32')
+            if not h16_net:
+                raise RuntimeError('%s input into a %s network: convert the network with .half() / .to(dtype=torch.float16)'
+                                   % (input_image.dtype, e.conv1.weight.dtype))
+            if not h16_in:
+                raise RuntimeError('%s input into a float16 network: cast the input with .half()' % input_image.dtype)
+            if self.training:
+                raise NotImplementedError('ResnetEncoder in fp16 runs in eval mode only (BatchNorm with running statistics): call '
+                                          '.eval() for evaluation / inference, train in float32')
+            return self._forward_h16(input_image)
         self.features = []
         x = HF.affine(input_image, 1.0 / 0.225, -0.45 / 0.225)
         x = HF.conv2d_stride2(x, e.conv1.weight, None, e._packed)

@@ -58,7 +58,7 @@ class PoseNet(nn.Module):
     def forward(self, image, context):
         if image.dtype == torch.float16 or any(t.dtype == torch.float16 for t in context) or self.conv1[0].weight.dtype == torch.float16:
             raise NotImplementedError('PoseNet has no fp16 kernels: the fp16 forward covers the depth networks PackNet01 / '
-                                      'PackNetSlim01 only; run PoseNet in float32')
+                                      'PackNetSlim01 / DepthResNet; run PoseNet in float32')
         assert len(context) == self.nb_ref_imgs
         x = torch.cat([image] + list(context), 1)
         for i in range(7):

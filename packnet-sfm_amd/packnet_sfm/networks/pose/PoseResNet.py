@@ -25,6 +25,9 @@ class PoseResNet(nn.Module):
         return torch.cat((trans[:, 0], rot[:, 0]), 2)                  # [B, 1, 6]
 
     def forward(self, target_image, ref_imgs):
+        if any(t.dtype == torch.float16 for t in [target_image, self.encoder.encoder.conv1.weight] + list(ref_imgs)):
+            raise NotImplementedError('PoseResNet has no fp16 path: fp16 covers the evaluation / inference forward of the depth networks '
+                                      '(pose is not part of it); run it in float32')
         return torch.cat([self._pair(target_image, ref) for ref in ref_imgs], 1)
 
 
