@@ -122,9 +122,9 @@ def pinned(*pins):
 class LastConfig(dict):
     """pnsfm_conv2d_last_config by name.  `raw`: the eight ints; `build`: the kernel build a weight-gradient launch ran --
     (103, KS, NT, WM, TC, masked, OCC) | (104, WCI, TG, TR, masked) | (100, stride, MT, tile mode) | (102,) | (105, MT) -- and
-    (variant,) after a forward / backward-data launch.  Every layout has variant (the code 100..105 after a weight-gradient launch),
-    split, blocks, lds; forward / backward-data adds NT, MT, G, tm; 100 stride, MT, PT, tm; 103 NT, WM, TC, OCC, masked, KS; 104 WCI,
-    TG, TR, masked; 105 MT."""
+    (variant, MT, NT, G) after a forward / backward-data launch (G: taps per weight stage, 0 for the f32 kernels).
+    Every layout has variant (the code 100..105 after a weight-gradient launch), split, blocks, lds; forward / backward-data adds
+    NT, MT, G, tm; 100 stride, MT, PT, tm; 103 NT, WM, TC, OCC, masked, KS; 104 WCI, TG, TR, masked; 105 MT."""
 
     def __init__(self, c):
         code = c[0]
@@ -145,6 +145,7 @@ class LastConfig(dict):
             self.build = (105, c[2])
         elif code < 100:
             self.update(NT=c[1], MT=c[2], G=c[3], tm=c[5])
+            self.build = (code, c[2], c[1], c[3])
 
 
 def last_config():
