@@ -459,6 +459,43 @@ int pnsfm_smoothness_norm_backward(const float* inv_depth, const float* image, c
 int pnsfm_smoothness_backward(const float* inv_norm, const float* image, float* d_inv_norm,
                               float gx, float gy, int B, int H, int W, void* stream);
 
+/* ---- all scales in one launch (csrc/loss.hip), since ABI version 10 ---------------------------------------------------------------
+ * The loop over the scales of MultiViewPhotometricLoss.forward (multiview_photometric_loss.py:303-338) as ONE launch per kernel: the
+ * scale is one more block index.  With upsampled inverse-depth maps (the reference's default) every scale sees the same context
+ * images, target, intrinsics and poses; only the inverse depth differs.  Tables (inv_depth, d_inv_depth, image, upstream, H, W) are
+ * HOST arrays of n entries, 1 <= n <= PNSFM_LOSS_MAX_SCALES, of DEVICE pointers (plain ints for H, W); a null entry is an error
+ * except in `upstream` (null table or entry = 1).  The per-scale entry points above run the same kernels with n = 1, so every
+ * scale's results are bit for bit those of its own per-scale call; clipping (clip_loss > 0) has no all-scales form.
+ *   view synthesis  warped: [n][J][B][3][H][W].  Backward overwrites every d_inv_depth[i] and writes dT:[J,B,4,4] = the sum over
+ *                   the scales, each scale finished to float first, added as ((dT_{n-1} + dT_{n-2}) + ...) + dT_0.
+ *   identity        id:[J][B][H][W] = the per-pixel loss of the UNWARPED candidates ref[j] (the automask candidates), which does
+ *                   not depend on the scale: the values pnsfm_photometric_forward computes for them (one device function).
+ *   photometric     loss_mean: float[n]; argmin: uint8[n][B][H][W].  With automask != 0 the unwarped candidates are read from `id`
+ *                   (required then, ignored otherwise) instead of being evaluated from the reference tiles.
+ *                   Backward: warped, d_warped: [n][J][B][3][H][W]; d_warped[i] = grad_scale * upstream[i][0] * d(sum_i)/d(warped[i]).
+ *   smoothness      scales may differ in resolution: scale i is H[i] x W[i] with image[i]:[B,3,H[i],W[i]].  loss: float[n];
+ *                   mean: float[n][B].  Backward: d_inv_depth[i] = upstream[i][0] * dloss_i/d(inv_depth[i]), overwritten, or with
+ *                   accumulate != 0 ADDED to what d_inv_depth[i] holds (one rounded sum of the two terms). */
+#define PNSFM_LOSS_MAX_SCALES 8
+int pnsfm_view_synthesis_forward_ms(const float* const* inv_depth, int n, const float* ref, const float* K, const float* refK,
+                                    const float* T, float* warped, int J, int B, int H, int W, int padding_mode, void* stream);
+int pnsfm_view_synthesis_backward_ms(const float* d_warped, const float* const* inv_depth, int n, const float* ref, const float* K,
+                                     const float* refK, const float* T, float* const* d_inv_depth, float* dT, int J, int B, int H,
+                                     int W, int padding_mode, void* stream);
+int pnsfm_photometric_identity_forward(const float* ref, const float* target, float* id, int J, int B, int H, int W, float ssim_weight,
+                                       float C1, float C2, void* stream);
+int pnsfm_photometric_forward_ms(const float* warped, const float* id /*nullable without automask*/, const float* target,
+                                 float* loss_mean, uint8_t* argmin, int n, int J, int B, int H, int W, float ssim_weight, float C1,
+                                 float C2, int automask, int reduce_op, void* stream);
+int pnsfm_photometric_backward_ms(const float* warped, const float* target, const uint8_t* argmin, float* d_warped, float grad_scale,
+                                  const float* const* upstream /*nullable*/, int n, int J, int B, int H, int W, float ssim_weight,
+                                  float C1, float C2, int automask, int reduce_op, void* stream);
+int pnsfm_smoothness_norm_forward_ms(const float* const* inv_depth, const float* const* image, const int* H, const int* W, int n,
+                                     float* loss, float* mean, int B, void* stream);
+int pnsfm_smoothness_norm_backward_ms(const float* const* inv_depth, const float* const* image, const int* H, const int* W, int n,
+                                      const float* mean, const float* const* upstream /*nullable*/, float* const* d_inv_depth,
+                                      int accumulate, int B, void* stream);
+
 /* ---- batched strided-window operations (one launch for a list of copies / accumulations / zero-fills) -------------------------
  * The collapsed form of PackLayerConv3d (layers01.py:213-247) computes the r-pixel border frame on thin strips: gathering
  * the strips, dropping rows of the Conv3d output, pasting the results into the interior result and the mirror-image gradient

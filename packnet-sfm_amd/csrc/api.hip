@@ -178,7 +178,7 @@ bool stream_capturing(hipStream_t) { return false; }
 
 extern "C" {
 
-int pnsfm_version(void) { return 9; }
+int pnsfm_version(void) { return 10; }
 
 const char* pnsfm_last_error(void) { return pnsfm::g_err; }
 

@@ -38,11 +38,28 @@ __global__ void __launch_bounds__(256) sum_partials_kernel(const double* __restr
   }
 }
 
-// the same second stage, finishing the scalar the caller wants: fout[0] = (float)(sum_v out[v] * scale[v]) -- the pixel mean of a loss
-// map, or sum|Sx|/nx + sum|Sy|/ny -- so that no ATen launch is needed between the kernels and autograd (round 4)
-__global__ void __launch_bounds__(256) sum_partials_scaled_kernel(const double* __restrict__ part, int n, int nvals, double s0, double s1,
+// ---- the scales of the multi-view loss in one launch (include/pnsfm.h "all scales in one launch").  Every kernel of this file that
+// runs once per scale takes the scale as one more block index and its per-scale pointers from a table in the kernel arguments; the
+// per-scale entry points launch the SAME kernels with a table of one, so a scale's bits do not depend on how many scales share
+// the launch.
+#define MS_MAX PNSFM_LOSS_MAX_SCALES
+struct MsIn { const float* p[MS_MAX]; };
+struct MsOut { float* p[MS_MAX]; };
+// second stages of one launch: workgroup s adds partials [off[s], off[s] + cnt[s]) and scales the sums by s0[s], s1[s]
+struct SumTab {
+  int off[MS_MAX], cnt[MS_MAX];
+  double s0[MS_MAX], s1[MS_MAX];
+};
+
+// the same second stage, finishing the scalar the caller wants: fout[s] = (float)(sum_v out[v] * scale[v]) -- the pixel mean of a loss
+// map, or sum|Sx|/nx + sum|Sy|/ny -- so that no ATen launch is needed between the kernels and autograd (round 4).  grid: one
+// workgroup per scalar (`out`, the unscaled sums, with a grid of one only)
+__global__ void __launch_bounds__(256) sum_partials_scaled_kernel(const double* __restrict__ part, SumTab t, int nvals,
                                                                   double* __restrict__ out, float* __restrict__ fout) {
   __shared__ double red[4];
+  const int s = blockIdx.x, n = t.cnt[s];
+  const double s0 = t.s0[s], s1 = t.s1[s];
+  part += (size_t)t.off[s] * nvals;
   double acc_out = 0.0;
   for (int v = 0; v < nvals; ++v) {
     double acc = 0.0;
@@ -52,7 +69,7 @@ __global__ void __launch_bounds__(256) sum_partials_scaled_kernel(const double* 
     acc_out += tot * (v == 0 ? s0 : s1);
     __syncthreads();
   }
-  if (threadIdx.x == 0) fout[0] = (float)acc_out;
+  if (threadIdx.x == 0) fout[s] = (float)acc_out;
 }
 
 struct Cam {
@@ -122,15 +139,17 @@ __device__ __forceinline__ float pad_coordinate(float x, int size, int mode, flo
   return x;
 }
 
-// grid: (ceil(HW/256), B, J)
-__global__ void __launch_bounds__(256) view_synthesis_fwd_kernel(const float* __restrict__ inv_depth, const float* __restrict__ ref,
+// grid: (ceil(HW/256), B, n * J): scale s = z / J reads its own inverse depth and writes warped[s][J][B][3][H][W]
+__global__ void __launch_bounds__(256) view_synthesis_fwd_kernel(MsIn inv, const float* __restrict__ ref,
                                                                   const float* __restrict__ K, const float* __restrict__ refK,
                                                                   const float* __restrict__ T, float* __restrict__ warped,
-                                                                  int B, int H, int W, int pad_mode) {
+                                                                  int J, int B, int H, int W, int pad_mode) {
   const int HW = H * W;
   const int pix = blockIdx.x * 256 + threadIdx.x;
-  const int b = blockIdx.y, j = blockIdx.z;
+  const int b = blockIdx.y, s = blockIdx.z / J, j = blockIdx.z - s * J;
   if (pix >= HW) return;
+  const float* __restrict__ inv_depth = inv.p[s];
+  warped += (size_t)s * J * B * 3 * HW;
   Cam cam;
   load_cam(K, refK, b, cam);
   float Tm[12];
@@ -166,17 +185,21 @@ __global__ void __launch_bounds__(256) view_synthesis_fwd_kernel(const float* __
   for (int c = 0; c < 3; ++c) wb[(size_t)c * HW] = out[c];
 }
 
-// grid: (ceil(HW/256), B). Loops over the J context images so that d_inv_depth needs no atomics.
-// ws: double[J*B*12] (zeroed by the caller) receives d(loss)/d(T[:3,:4]).
-__global__ void __launch_bounds__(256) view_synthesis_bwd_kernel(const float* __restrict__ d_warped, const float* __restrict__ inv_depth,
+// grid: (ceil(HW/256), B, n). Loops over the J context images so that d_inv_depth needs no atomics.
+// ws: double[n][J*B][pixel blocks][12] receives the per-block partials of d(loss)/d(T[:3,:4]) of every scale.
+__global__ void __launch_bounds__(256) view_synthesis_bwd_kernel(const float* __restrict__ d_warped, MsIn inv,
                                                                   const float* __restrict__ ref, const float* __restrict__ K,
                                                                   const float* __restrict__ refK, const float* __restrict__ T,
-                                                                  float* __restrict__ d_inv_depth, double* __restrict__ ws,
+                                                                  MsOut d_inv, double* __restrict__ ws,
                                                                   int J, int B, int H, int W, int pad_mode) {
   __shared__ float redT[4][12];
   const int HW = H * W;
   const int pix = blockIdx.x * 256 + threadIdx.x;
-  const int b = blockIdx.y;
+  const int b = blockIdx.y, sc = blockIdx.z;
+  const float* __restrict__ inv_depth = inv.p[sc];
+  float* __restrict__ d_inv_depth = d_inv.p[sc];
+  d_warped += (size_t)sc * J * B * 3 * HW;
+  ws += (size_t)sc * J * B * gridDim.x * 12;
   const bool active = pix < HW;
   Cam cam;
   load_cam(K, refK, b, cam);
@@ -266,22 +289,33 @@ __global__ void __launch_bounds__(256) view_synthesis_bwd_kernel(const float* __
 }
 
 // dT[m] (4x4, last row zero) = sum over the pixel blocks' partials of matrix m: one wave per matrix, lane l adds blocks l, l + 64,
-// ... in order and the 64 lane sums meet in a fixed shuffle tree -- bit-reproducible
-__global__ void __launch_bounds__(64) view_synthesis_bwd_finish_kernel(const double* __restrict__ part, float* __restrict__ dT, int nblk) {
-  const int m = blockIdx.x, lane = threadIdx.x;
-  double s[12];
+// ... in order and the 64 lane sums meet in a fixed shuffle tree -- bit-reproducible.  With n scales in the launch (part: [n][nmat]
+// [nblk][12]) every scale is finished to a float on its own, as its own launch would, and the floats are added from the LAST scale
+// to the first, ((dT[n-1] + dT[n-2]) + ...) + dT[0]: the sums the autograd engine forms when each scale is a node of its own (it
+// runs the node created last first and adds each gradient to the running sum of the pose matrices)
+__global__ void __launch_bounds__(64) view_synthesis_bwd_finish_kernel(const double* __restrict__ part, float* __restrict__ dT, int nblk,
+                                                                        int n) {
+  const int m = blockIdx.x, lane = threadIdx.x, nmat = gridDim.x;
+  float tot[12];
+  for (int sc = n - 1; sc >= 0; --sc) {
+    double s[12];
 #pragma unroll
-  for (int i = 0; i < 12; ++i) s[i] = 0.0;
-  for (int p = lane; p < nblk; p += 64) {
-    const double* q = part + ((size_t)m * nblk + p) * 12;
+    for (int i = 0; i < 12; ++i) s[i] = 0.0;
+    for (int p = lane; p < nblk; p += 64) {
+      const double* q = part + (((size_t)sc * nmat + m) * nblk + p) * 12;
 #pragma unroll
-    for (int i = 0; i < 12; ++i) s[i] += q[i];
+      for (int i = 0; i < 12; ++i) s[i] += q[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 12; ++i) {
+      double v = s[i];
+      for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d);
+      tot[i] = sc == n - 1 ? (float)v : tot[i] + (float)v;
+    }
   }
+  if (lane == 0) {
 #pragma unroll
-  for (int i = 0; i < 12; ++i) {
-    double v = s[i];
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d);
-    if (lane == 0) dT[m * 16 + i] = (float)v;
+    for (int i = 0; i < 12; ++i) dT[m * 16 + i] = tot[i];
   }
   if (lane < 4) dT[m * 16 + 12 + lane] = 0.f;
 }
@@ -332,7 +366,91 @@ __device__ __forceinline__ SsimTerms ssim_terms(const WinStats& w, float C1, flo
 #define PH_S1 (PH_T + 2)  // with 1-pixel halo
 #define PH_S2 (PH_T + 4)  // with 2-pixel halo
 
-// grid: (ceil(W/16), ceil(H/16), B); block 256 = 16x16 pixels. LDS: (1 + 2J) images x 3 ch x 18x18.
+// The per-pixel loss of ONE candidate image against the target, w (1 - SSIM) / 2 + (1 - w) L1, channel mean, at LDS position cpos of
+// 18-wide tiles (img, tgt: [3][18*18]).  It is what win_stats -> ssim_terms -> the mix line compute, with every rounding WRITTEN
+// OUT: contraction is off and each fused multiply-add is an fmaf, in exactly the places where hipcc fused the un-pinned expression
+// in the kernel that the per-pixel fp64 pins and the trained results were established with (read off its ISA).  Both callers -- the
+// candidate loop of photometric_fwd_kernel and photometric_identity_kernel -- therefore produce the same bits whatever the
+// compiler makes of the code around the call.
+//   sums of x, y: taps in row order, plain adds;   sum x^2, sum xy: a0 * a0 (a0 * b0), then one fmaf per tap in row order;
+//   sum y^2: products of taps 3, 4, 6, 7 rounded and added, the other taps fused (the target-only sum, as the compiler vectorised it);
+//   sigma = fmaf(sum, 1/9, -(mean product));   B1 = fmaf(mx, mx, my * my) + C1;   the mix: two rounded products, one add.
+__device__ __forceinline__ float photometric_candidate(const float* img, const float* tgt, int cpos, float ssim_w, float C1, float C2) {
+#pragma clang fp contract(off)
+  const int plane = PH_S1 * PH_S1;
+  const float inv9 = 1.f / 9.f;
+  float ssim_acc = 0.f, l1_acc = 0.f;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    float a[9], b[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+      const int o = c * plane + cpos + (k / 3 - 1) * PH_S1 + (k % 3 - 1);
+      a[k] = img[o];
+      b[k] = tgt[o];
+    }
+    float sx = 0.f, sy = 0.f;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) { sx = sx + a[k]; sy = sy + b[k]; }
+    float sxx = a[0] * a[0], sxy = a[0] * b[0];
+#pragma unroll
+    for (int k = 1; k < 9; ++k) { sxx = fmaf(a[k], a[k], sxx); sxy = fmaf(a[k], b[k], sxy); }
+    float syy = b[1] * b[1];
+    syy = fmaf(b[0], b[0], syy);
+    syy = fmaf(b[2], b[2], syy);
+    syy = syy + b[3] * b[3];
+    syy = syy + b[4] * b[4];
+    syy = fmaf(b[5], b[5], syy);
+    syy = syy + b[6] * b[6];
+    syy = syy + b[7] * b[7];
+    syy = fmaf(b[8], b[8], syy);
+    const float mx = sx * inv9, my = sy * inv9;
+    const float mxmy = mx * my, mx2 = mx * mx, my2 = my * my;
+    const float sig_x = fmaf(sxx, inv9, -mx2), sig_y = fmaf(syy, inv9, -my2), sig_xy = fmaf(sxy, inv9, -mxmy);
+    const float A1 = 2.f * mxmy + C1;
+    const float A2 = 2.f * sig_xy + C2;
+    const float B1 = fmaf(mx, mx, my2) + C1;
+    const float B2 = (sig_x + sig_y) + C2;
+    const float ssim = (A1 * A2) / (B1 * B2);
+    ssim_acc = ssim_acc + fminf(fmaxf((1.f - ssim) * 0.5f, 0.f), 1.f);
+    l1_acc = l1_acc + fabsf(a[4] - b[4]);
+  }
+  const float ps = ssim_w * (ssim_acc / 3.f), pl = (1.f - ssim_w) * (l1_acc / 3.f);
+  return ps + pl;
+}
+
+// The loss of the UNWARPED candidates ref[j] (the automask candidates) per pixel, id[J][B][H][W]: it depends on (ref, target) alone, so
+// scales that share both share the map.  grid and tiles as photometric_fwd_kernel; LDS: 2 images x 3 ch x 18x18; z covers J * B.
+__global__ void __launch_bounds__(256) photometric_identity_kernel(const float* __restrict__ ref, const float* __restrict__ target,
+                                                                    float* __restrict__ id_out, int B, int H, int W, float ssim_w,
+                                                                    float C1, float C2) {
+  PNSFM_DYN_SMEM(float, smem);
+  const int HW = H * W;
+  const unsigned Lb = pnsfm_xcd_logical_block((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x, gridDim.x * gridDim.y * gridDim.z);
+  const int lbx = (int)(Lb % gridDim.x), lby = (int)((Lb / gridDim.x) % gridDim.y);
+  const int jb = (int)(Lb / (gridDim.x * gridDim.y)), b = jb % B;      // jb = j * B + b
+  const int tx0 = lbx * PH_T, ty0 = lby * PH_T;
+  const int plane = PH_S1 * PH_S1;
+  for (int e = threadIdx.x; e < 2 * 3 * plane; e += 256) {      // slot 0 = target, 1 = ref[j]
+    const int img = e / (3 * plane);
+    int r = e - img * 3 * plane;
+    const int c = r / plane;
+    r -= c * plane;
+    const int ly = r / PH_S1, lx = r - ly * PH_S1;
+    const int gy = reflect_idx(ty0 + ly - 1, H), gx = reflect_idx(tx0 + lx - 1, W);
+    const float* src = img == 0 ? target + (size_t)b * 3 * HW : ref + (size_t)jb * 3 * HW;
+    smem[e] = src[(size_t)c * HW + gy * W + gx];
+  }
+  __syncthreads();
+  const int ly = threadIdx.x >> 4, lx = threadIdx.x & 15;
+  const int gy = ty0 + ly, gx = tx0 + lx;
+  const float l = photometric_candidate(smem + 3 * plane, smem, (ly + 1) * PH_S1 + lx + 1, ssim_w, C1, C2);
+  if (gy < H && gx < W) id_out[(size_t)jb * HW + gy * W + gx] = l;
+}
+
+// grid: (ceil(W/16), ceil(H/16), n * B); block 256 = 16x16 pixels. LDS: (1 + 2J) images x 3 ch x 18x18, with idmap (1 + J).
+// idmap != null (all scales under automask): the unwarped candidates are READ from photometric_identity_kernel's map instead of being
+// evaluated from reference tiles -- no reference tiles in LDS, a third of the candidate arithmetic of an automask launch.
 // clip_loss > 0 (multiview_photometric_loss.py:214-219: every candidate map is clamped at mean + clip*std of ITSELF, a
 // float, so no gradient flows through the statistics) needs those statistics first: with `stats` != null the kernel only
 // accumulates sum / sum-of-squares per candidate (double[2*ncand]); a finish kernel turns them into thresholds `clip_thr`
@@ -342,20 +460,28 @@ __global__ void __launch_bounds__(256) photometric_fwd_kernel(const float* __res
                                                                const float* __restrict__ target, double* __restrict__ loss_sum,
                                                                uint8_t* __restrict__ argmin, int J, int B, int H, int W,
                                                                float ssim_w, float C1, float C2, int automask, int reduce_op,
-                                                               const float* __restrict__ clip_thr, double* __restrict__ stats) {
+                                                               const float* __restrict__ clip_thr, double* __restrict__ stats,
+                                                               const float* __restrict__ idmap, int nblk1) {
   PNSFM_DYN_SMEM(float, smem);
   __shared__ double red[4];
   const int HW = H * W;
   // logical tile (x, y, image): the physical workgroup index (x fastest) goes round robin over the 8 XCDs, so horizontally adjacent
   // 16-pixel tiles -- two per 128-byte line -- and the tiles sharing halo rows would each pull the same lines into a different L2
   // (r04_traffic.json: 3.9x the algorithmic bytes); one contiguous range of the tile order per XCD keeps neighbours on one L2
-  const unsigned Lb = pnsfm_xcd_logical_block((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x, gridDim.x * gridDim.y * gridDim.z);
+  const unsigned L = pnsfm_xcd_logical_block((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x, gridDim.x * gridDim.y * gridDim.z);
+  // grid z = n * B, nblk1 = the tiles of one scale: scale sc reads warped[sc] and writes argmin[sc] and the partials [sc * nblk1,
+  // (sc + 1) * nblk1); Lb is the tile's index within its scale, as in a launch of that scale alone
+  const int sc = (int)(L / (unsigned)nblk1);
+  const unsigned Lb = L - (unsigned)sc * (unsigned)nblk1;
+  warped += (size_t)sc * J * B * 3 * HW;
+  argmin += (size_t)sc * B * HW;
   const int lbx = (int)(Lb % gridDim.x), lby = (int)((Lb / gridDim.x) % gridDim.y);
   const int b = (int)(Lb / (gridDim.x * gridDim.y));
   const int tx0 = lbx * PH_T, ty0 = lby * PH_T;
   const int plane = PH_S1 * PH_S1;
-  // image slots: 0 = target, 1+2j = warped[j], 2+2j = ref[j]
-  const int nimg = 1 + 2 * J;
+  // image slots: 0 = target, 1 + per * j = warped[j], with per == 2: 2 + 2j = ref[j]
+  const int per = idmap ? 1 : 2;
+  const int nimg = 1 + per * J;
   for (int e = threadIdx.x; e < nimg * 3 * plane; e += 256) {
     const int img = e / (3 * plane);
     int r = e - img * 3 * plane;
@@ -363,14 +489,16 @@ __global__ void __launch_bounds__(256) photometric_fwd_kernel(const float* __res
     r -= c * plane;
     const int ly = r / PH_S1, lx = r - ly * PH_S1;
     const int gy = reflect_idx(ty0 + ly - 1, H), gx = reflect_idx(tx0 + lx - 1, W);
-    const float* src;
-    if (img == 0) src = target + (size_t)b * 3 * HW;
-    else {
-      const int j = (img - 1) >> 1;
-      src = (((img - 1) & 1) ? ref : warped) + ((size_t)j * B + b) * 3 * HW;
+    const float* src = target + (size_t)b * 3 * HW;
+    bool load = true;
+    if (img != 0) {
+      const int j = (img - 1) / per;
+      const bool is_ref = per == 2 && ((img - 1) & 1);
+      load = !is_ref || automask;
+      if (load) src = (is_ref ? ref : warped) + ((size_t)j * B + b) * 3 * HW;
     }
     float v = 0.f;
-    if (img == 0 || !(((img - 1) & 1) && !automask)) v = src[(size_t)c * HW + gy * W + gx];
+    if (load) v = src[(size_t)c * HW + gy * W + gx];
     smem[e] = v;
   }
   __syncthreads();
@@ -384,18 +512,9 @@ __global__ void __launch_bounds__(256) photometric_fwd_kernel(const float* __res
   const float* tgt = smem;
   for (int j = 0; j < J; ++j) {
     for (int id = 0; id < (automask ? 2 : 1); ++id) {
-      const float* img = smem + (1 + 2 * j + id) * 3 * plane;
-      float ssim_acc = 0.f, l1_acc = 0.f;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const float* xs = img + c * plane;
-        const float* ys = tgt + c * plane;
-        const WinStats w = win_stats(xs, ys, cpos, PH_S1);
-        const SsimTerms t = ssim_terms(w, C1, C2);
-        ssim_acc += fminf(fmaxf((1.f - t.ssim) * 0.5f, 0.f), 1.f);
-        l1_acc += fabsf(xs[cpos] - ys[cpos]);
-      }
-      float l = ssim_w * (ssim_acc / 3.f) + (1.f - ssim_w) * (l1_acc / 3.f);
+      float l;
+      if (id == 1 && idmap) l = valid ? idmap[((size_t)j * B + b) * HW + gy * W + gx] : 0.f;
+      else l = photometric_candidate(smem + (1 + per * j + id) * 3 * plane, tgt, cpos, ssim_w, C1, C2);
       cl[ncand] = l;
       if (clip_thr != nullptr && l > clip_thr[ncand]) { l = clip_thr[ncand]; clamp_mask |= 1 << ncand; }
       if (ncand == 0 || l < best) { best = l; best_i = ncand; }
@@ -421,7 +540,7 @@ __global__ void __launch_bounds__(256) photometric_fwd_kernel(const float* __res
   // stage 1 of the pixel mean: one partial per workgroup (loss_sum = the launch's partial buffer); sum_partials_kernel adds
   // them in a fixed order -- no atomics, the loss is bit-reproducible
   const double s = block_sum_256d((double)contrib, red);
-  if (threadIdx.x == 0) loss_sum[Lb] = s;
+  if (threadIdx.x == 0) loss_sum[L] = s;
 }
 
 // grid as forward. LDS: (1 + J) images x 3 ch x 20x20  +  J x 3 ch x 3 coefficient planes x 18x18.
@@ -431,12 +550,18 @@ __global__ void __launch_bounds__(256) photometric_bwd_kernel(const float* __res
                                                                const uint8_t* __restrict__ argmin, float* __restrict__ d_warped,
                                                                float grad_scale, int J, int B, int H, int W, float ssim_w,
                                                                float C1, float C2, int automask, int reduce_op, int clip,
-                                                               const float* __restrict__ gdev) {
+                                                               MsIn gdev, int nblk1) {
   PNSFM_DYN_SMEM(float, smem);
-  if (gdev) grad_scale *= gdev[0];        // upstream gradient of the scalar loss, still on the device (no `d * g` pass over d_warped)
   const int HW = H * W;
-  // logical tile order: one contiguous range per XCD (see photometric_fwd_kernel)
-  const unsigned Lb = pnsfm_xcd_logical_block((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x, gridDim.x * gridDim.y * gridDim.z);
+  // logical tile order: one contiguous range per XCD; grid z = n * B, scale sc = tile / nblk1 (see photometric_fwd_kernel)
+  const unsigned L = pnsfm_xcd_logical_block((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x, gridDim.x * gridDim.y * gridDim.z);
+  const int sc = (int)(L / (unsigned)nblk1);
+  const unsigned Lb = L - (unsigned)sc * (unsigned)nblk1;
+  const float* g_up = gdev.p[sc];
+  if (g_up) grad_scale *= g_up[0];        // upstream gradient of the scalar loss, still on the device (no `d * g` pass over d_warped)
+  warped += (size_t)sc * J * B * 3 * HW;
+  d_warped += (size_t)sc * J * B * 3 * HW;
+  argmin += (size_t)sc * B * HW;
   const int lbx = (int)(Lb % gridDim.x), lby = (int)((Lb / gridDim.x) % gridDim.y);
   const int b = (int)(Lb / (gridDim.x * gridDim.y));
   const int tx0 = lbx * PH_T, ty0 = lby * PH_T;
@@ -694,12 +819,40 @@ __global__ void __launch_bounds__(256) l1cand_bwd_kernel(const float* __restrict
 //             sum_partials_scaled_kernel (loss = sum|Sx|/nx + sum|Sy|/ny as a float)
 //   backward: with n = d / m and g_n = dL/dn:  dL/dd_i = g_n,i / m - [mean > 1e-6] * (sum_j g_n,j d_j) / (m^2 HW)
 //             sn_bwd_kernel writes g_n and per-block partials of sum g_n d;  sn_bwd_apply_kernel finishes in place.
-__global__ void __launch_bounds__(256) sn_mean_kernel(const float* __restrict__ inv, double* __restrict__ part, int HW) {
+// The scales of one launch may differ in resolution (the reference's smoothness runs on the network's own scales unless the maps are
+// upsampled), so grid x runs over the pixel blocks of ALL scales and a block-range table selects the scale: scale s owns blocks
+// [blk0[s], blk0[s + 1]).  grid: (blk0[n], B).  Partials of scale s start at B * blk0[s] (x 2 for the |Sx|, |Sy| pairs) and are laid
+// out [b][block of the scale] behind that, as a launch of that scale alone lays them out.
+struct SnTab {
+  const float* inv[MS_MAX];
+  const float* img[MS_MAX];
+  int H[MS_MAX], W[MS_MAX];
+  int blk0[MS_MAX + 1];
+  float gx[MS_MAX], gy[MS_MAX];      // backward: 1 / (B H (W - 1)), 1 / (B (H - 1) W)
+  int n;
+};
+
+struct SnBlock { int s, bx, nblk; size_t slot; };     // scale, block within the scale, blocks of the scale, partial slot of (b, bx)
+
+__device__ __forceinline__ SnBlock sn_block(const SnTab& t) {
+  SnBlock k;
+  k.s = 0;
+  while (k.s + 1 < t.n && (int)blockIdx.x >= t.blk0[k.s + 1]) ++k.s;
+  k.bx = (int)blockIdx.x - t.blk0[k.s];
+  k.nblk = t.blk0[k.s + 1] - t.blk0[k.s];
+  k.slot = (size_t)gridDim.y * t.blk0[k.s] + (size_t)blockIdx.y * k.nblk + k.bx;
+  return k;
+}
+
+__global__ void __launch_bounds__(256) sn_mean_kernel(SnTab t, double* __restrict__ part) {
   __shared__ double red[4];
-  const int pix = blockIdx.x * 256 + threadIdx.x;
+  const SnBlock k = sn_block(t);
+  const int HW = t.H[k.s] * t.W[k.s];
+  const float* __restrict__ inv = t.inv[k.s];
+  const int pix = k.bx * 256 + threadIdx.x;
   const double v = pix < HW ? (double)inv[(size_t)blockIdx.y * HW + pix] : 0.0;
-  const double t = block_sum_256d(v, red);
-  if (threadIdx.x == 0) part[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = t;
+  const double tt = block_sum_256d(v, red);
+  if (threadIdx.x == 0) part[k.slot] = tt;
 }
 
 // m_b = clamp(mean of sample b, 1e-6): the partials are added in index order by every block alike (identical bits everywhere)
@@ -713,15 +866,19 @@ __device__ __forceinline__ float sn_sample_mean(const double* __restrict__ mpart
   return mean > 1e-6f ? mean : 1e-6f;
 }
 
-__global__ void __launch_bounds__(256) sn_fwd_kernel(const float* __restrict__ inv, const float* __restrict__ image,
-                                                      const double* __restrict__ mpart, double* __restrict__ sums,
-                                                      float* __restrict__ mean_out, int H, int W) {
+// mean_out: [n][B]
+__global__ void __launch_bounds__(256) sn_fwd_kernel(SnTab t, const double* __restrict__ mpart, double* __restrict__ sums,
+                                                      float* __restrict__ mean_out) {
   __shared__ double red[4];
+  const SnBlock k = sn_block(t);
+  const int H = t.H[k.s], W = t.W[k.s];
+  const float* __restrict__ inv = t.inv[k.s];
+  const float* __restrict__ image = t.img[k.s];
   const int HW = H * W;
-  const int pix = blockIdx.x * 256 + threadIdx.x;
+  const int pix = k.bx * 256 + threadIdx.x;
   const int b = blockIdx.y;
-  const float m = sn_sample_mean(mpart + (size_t)b * gridDim.x, (int)gridDim.x, HW, red, nullptr);
-  if (blockIdx.x == 0 && threadIdx.x == 0) mean_out[b] = m;
+  const float m = sn_sample_mean(mpart + (k.slot - k.bx), k.nblk, HW, red, nullptr);
+  if (k.bx == 0 && threadIdx.x == 0) mean_out[(size_t)k.s * gridDim.y + b] = m;
   float sx = 0.f, sy = 0.f;
   if (pix < HW) {
     const int y = pix / W, x = pix - y * W;
@@ -734,20 +891,25 @@ __global__ void __launch_bounds__(256) sn_fwd_kernel(const float* __restrict__ i
   const double tx = block_sum_256d((double)sx, red);
   const double ty = block_sum_256d((double)sy, red);
   if (threadIdx.x == 0) {
-    const size_t blk = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
-    sums[2 * blk] = tx;
-    sums[2 * blk + 1] = ty;
+    sums[2 * k.slot] = tx;
+    sums[2 * k.slot + 1] = ty;
   }
 }
 
-__global__ void __launch_bounds__(256) sn_bwd_kernel(const float* __restrict__ inv, const float* __restrict__ image,
-                                                      const float* __restrict__ mean, float* __restrict__ g_n, double* __restrict__ part,
-                                                      float gx, float gy, int H, int W) {
+// g_n: per scale, where d loss / d (normalised inverse depth) goes: the scale's d_inv_depth itself (sn_bwd_apply_kernel then finishes
+// it in place) or a temporary when d_inv_depth already holds a gradient that the apply kernel adds to
+__global__ void __launch_bounds__(256) sn_bwd_kernel(SnTab t, const float* __restrict__ mean, MsOut g_n_tab, double* __restrict__ part) {
   __shared__ double red[4];
+  const SnBlock k = sn_block(t);
+  const int H = t.H[k.s], W = t.W[k.s];
+  const float* __restrict__ inv = t.inv[k.s];
+  const float* __restrict__ image = t.img[k.s];
+  float* __restrict__ g_n = g_n_tab.p[k.s];
+  const float gx = t.gx[k.s], gy = t.gy[k.s];
   const int HW = H * W;
-  const int pix = blockIdx.x * 256 + threadIdx.x;
+  const int pix = k.bx * 256 + threadIdx.x;
   const int b = blockIdx.y;
-  const float m = mean[b];
+  const float m = mean[(size_t)k.s * gridDim.y + b];
   float g = 0.f, d = 0.f;
   if (pix < HW) {
     const int y = pix / W, x = pix - y * W;
@@ -761,25 +923,35 @@ __global__ void __launch_bounds__(256) sn_bwd_kernel(const float* __restrict__ i
     if (y >= 1)    { const float w = edge_weight(im, HW, pix - W, pix); g -= gy * sgnf((ib[pix - W] / m - r) * w) * w; }
     g_n[(size_t)b * HW + pix] = g;
   }
-  const double t = block_sum_256d((double)g * (double)d, red);
-  if (threadIdx.x == 0) part[(size_t)b * gridDim.x + blockIdx.x] = t;
+  const double tt = block_sum_256d((double)g * (double)d, red);
+  if (threadIdx.x == 0) part[k.slot] = tt;
 }
 
-__global__ void __launch_bounds__(256) sn_bwd_apply_kernel(float* __restrict__ d_inv, const float* __restrict__ mean,
-                                                            const double* __restrict__ part, const float* __restrict__ gdev, int HW) {
+// d_inv = g (g_n / m - corr), or with `accumulate` d_inv + that: the second term of a gradient whose first term (the photometric
+// one) d_inv already holds.  The sum is one rounded add of the two rounded terms -- what the autograd engine's a + b of the two
+// tensors gives -- so the product must not contract into it.  (g_n and d_inv may be the same buffer: no __restrict__.)
+__global__ void __launch_bounds__(256) sn_bwd_apply_kernel(SnTab t, MsOut d_inv_tab, MsOut g_n_tab, const float* __restrict__ mean,
+                                                            const double* __restrict__ part, MsIn gdev, int accumulate) {
   __shared__ double red[4];
+  const SnBlock k = sn_block(t);
+  const int HW = t.H[k.s] * t.W[k.s];
+  float* d_inv = d_inv_tab.p[k.s];
+  const float* g_n = g_n_tab.p[k.s];
   const int b = blockIdx.y;
   double acc = 0.0;
-  for (int i = threadIdx.x; i < (int)gridDim.x; i += 256) acc += part[(size_t)b * gridDim.x + i];
+  for (int i = threadIdx.x; i < k.nblk; i += 256) acc += part[k.slot - k.bx + i];
   const double dot = block_sum_256d(acc, red);
-  const float m = mean[b];
+  const float m = mean[(size_t)k.s * gridDim.y + b];
   // m == 1e-6 means the clamp was active (a mean that is exactly 1e-6 un-clamped differs from it by the clamp's own tie rule only)
   const float corr = m > 1e-6f ? (float)(dot / ((double)m * (double)m * (double)HW)) : 0.f;
-  const float g = gdev ? gdev[0] : 1.f;
-  const int pix = blockIdx.x * 256 + threadIdx.x;
+  const float* g_up = gdev.p[k.s];
+  const float g = g_up ? g_up[0] : 1.f;
+  const int pix = k.bx * 256 + threadIdx.x;
   if (pix < HW) {
-    float* p = d_inv + (size_t)b * HW + pix;
-    *p = g * (*p / m - corr);
+#pragma clang fp contract(off)
+    const size_t o = (size_t)b * HW + pix;
+    const float term = g * (g_n[o] / m - corr);
+    d_inv[o] = accumulate ? d_inv[o] + term : term;
   }
 }
 
@@ -787,34 +959,74 @@ __global__ void __launch_bounds__(256) sn_bwd_apply_kernel(float* __restrict__ d
 
 using namespace pnsfm;
 
+// a HOST table of n device pointers -> the kernel-argument table; false (error set, nothing launched) on a bad n or a null entry
+template <class Tab, class P>
+static bool ms_table(const char* what, const char* name, P const* host, int n, Tab& tab, bool nullable = false) {
+  if (n < 1 || n > MS_MAX) { set_error("%s: n must be 1..%d scales (got %d)", what, MS_MAX, n); return false; }
+  for (int i = 0; i < MS_MAX; ++i) tab.p[i] = nullptr;
+  if (!host) {
+    if (nullable) return true;
+    set_error("%s: the table %s is null", what, name);
+    return false;
+  }
+  for (int i = 0; i < n; ++i) {
+    if (!host[i] && !nullable) { set_error("%s: %s[%d] is null", what, name, i); return false; }
+    tab.p[i] = host[i];
+  }
+  return true;
+}
+
+static SumTab sum_tab(int n, int cnt, double s0, double s1) {     // n scalars of cnt partials each, back to back
+  SumTab t;
+  for (int i = 0; i < MS_MAX; ++i) { t.off[i] = i < n ? i * cnt : 0; t.cnt[i] = i < n ? cnt : 0; t.s0[i] = s0; t.s1[i] = s1; }
+  return t;
+}
+
 extern "C" {
+
+int pnsfm_view_synthesis_forward_ms(const float* const* inv_depth, int n, const float* ref, const float* K, const float* refK,
+                                    const float* T, float* warped, int J, int B, int H, int W, int padding_mode, void* stream) {
+  MsIn inv;
+  if (!ms_table("view_synthesis_forward", "inv_depth", inv_depth, n, inv)) return -1;
+  if (J < 1 || B < 1 || H < 2 || W < 2) { set_error("view_synthesis_forward: bad shape"); return -1; }
+  if (padding_mode < 0 || padding_mode > 2) { set_error("view_synthesis_forward: padding_mode must be 0 (zeros), 1 (border) or 2 (reflection)"); return -1; }
+  dim3 grid(ceil_div(H * W, 256), B, n * J);
+  PNSFM_LAUNCH(view_synthesis_fwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, inv, ref, K, refK, T, warped, J, B, H, W,
+               padding_mode);
+  return check_launch("view_synthesis_forward");
+}
 
 int pnsfm_view_synthesis_forward(const float* inv_depth, const float* ref, const float* K, const float* refK, const float* T,
                                  float* warped, int J, int B, int H, int W, int padding_mode, void* stream) {
-  if (J < 1 || B < 1 || H < 2 || W < 2) { set_error("view_synthesis_forward: bad shape"); return -1; }
-  if (padding_mode < 0 || padding_mode > 2) { set_error("view_synthesis_forward: padding_mode must be 0 (zeros), 1 (border) or 2 (reflection)"); return -1; }
-  dim3 grid(ceil_div(H * W, 256), B, J);
-  PNSFM_LAUNCH(view_synthesis_fwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, inv_depth, ref, K, refK, T, warped, B, H, W,
-               padding_mode);
-  return check_launch("view_synthesis_forward");
+  return pnsfm_view_synthesis_forward_ms(&inv_depth, 1, ref, K, refK, T, warped, J, B, H, W, padding_mode, stream);
+}
+
+int pnsfm_view_synthesis_backward_ms(const float* d_warped, const float* const* inv_depth, int n, const float* ref, const float* K,
+                                     const float* refK, const float* T, float* const* d_inv_depth, float* dT, int J, int B, int H,
+                                     int W, int padding_mode, void* stream) {
+  MsIn inv;
+  MsOut d_inv;
+  if (!ms_table("view_synthesis_backward", "inv_depth", inv_depth, n, inv)) return -1;
+  if (!ms_table("view_synthesis_backward", "d_inv_depth", d_inv_depth, n, d_inv)) return -1;
+  if (J < 1 || B < 1 || H < 2 || W < 2) { set_error("view_synthesis_backward: bad shape"); return -1; }
+  if (padding_mode < 0 || padding_mode > 2) { set_error("view_synthesis_backward: bad padding_mode"); return -1; }
+  hipStream_t s = (hipStream_t)stream;
+  dim3 grid(ceil_div(H * W, 256), B, n);
+  ScratchLease lease(s, (size_t)n * J * B * grid.x * 12 * sizeof(double));      // per-block partials of the pose gradient
+  double* const part = lease.as<double>();
+  if (!part) return -1;
+  PNSFM_LAUNCH(view_synthesis_bwd_kernel, grid, dim3(256), 0, s, d_warped, inv, ref, K, refK, T, d_inv, part, J, B,
+               H, W, padding_mode);
+  int e = check_launch("view_synthesis_backward");
+  if (e) return e;
+  PNSFM_LAUNCH(view_synthesis_bwd_finish_kernel, dim3(J * B), dim3(64), 0, s, (const double*)part, dT, (int)grid.x, n);
+  return check_launch("view_synthesis_backward_finish");
 }
 
 int pnsfm_view_synthesis_backward(const float* d_warped, const float* inv_depth, const float* ref, const float* K,
                                   const float* refK, const float* T, float* d_inv_depth, float* dT, int J, int B, int H, int W,
                                   int padding_mode, void* stream) {
-  if (J < 1 || B < 1 || H < 2 || W < 2) { set_error("view_synthesis_backward: bad shape"); return -1; }
-  if (padding_mode < 0 || padding_mode > 2) { set_error("view_synthesis_backward: bad padding_mode"); return -1; }
-  hipStream_t s = (hipStream_t)stream;
-  dim3 grid(ceil_div(H * W, 256), B);
-  ScratchLease lease(s, (size_t)J * B * grid.x * 12 * sizeof(double));      // per-block partials of the pose gradient
-  double* const part = lease.as<double>();
-  if (!part) return -1;
-  PNSFM_LAUNCH(view_synthesis_bwd_kernel, grid, dim3(256), 0, s, d_warped, inv_depth, ref, K, refK, T, d_inv_depth, part, J, B,
-               H, W, padding_mode);
-  int e = check_launch("view_synthesis_backward");
-  if (e) return e;
-  PNSFM_LAUNCH(view_synthesis_bwd_finish_kernel, dim3(J * B), dim3(64), 0, s, (const double*)part, dT, (int)grid.x);
-  return check_launch("view_synthesis_backward_finish");
+  return pnsfm_view_synthesis_backward_ms(d_warped, &inv_depth, 1, ref, K, refK, T, &d_inv_depth, dT, J, B, H, W, padding_mode, stream);
 }
 
 __global__ void photometric_clip_finish_kernel(const double* __restrict__ stats, float* __restrict__ thr, int ncand, double n,
@@ -858,30 +1070,90 @@ int pnsfm_photometric_forward(const float* warped, const float* ref, const float
     int e = (int)hipMemsetAsync(stats, 0, 12 * sizeof(double), s);
     if (e) { set_error("photometric_forward: memset failed"); return e; }
     PNSFM_LAUNCH(photometric_fwd_kernel, grid, dim3(256), smem, s, warped, ref, target, part, argmin, J, B, H, W, ssim_weight,
-                 C1, C2, automask, reduce_op, (const float*)nullptr, stats);
+                 C1, C2, automask, reduce_op, (const float*)nullptr, stats, (const float*)nullptr, nblk);
     PNSFM_LAUNCH(photometric_clip_finish_kernel, dim3(1), dim3(64), 0, s, (const double*)stats, thr_w, J * (automask ? 2 : 1),
                  (double)B * H * W, clip_loss);
     thr = thr_w;
   }
   PNSFM_LAUNCH(photometric_fwd_kernel, grid, dim3(256), smem, s, warped, ref, target, part, argmin, J, B, H, W, ssim_weight,
-               C1, C2, automask, reduce_op, thr, (double*)nullptr);
+               C1, C2, automask, reduce_op, thr, (double*)nullptr, (const float*)nullptr, nblk);
   if (loss_mean)
-    PNSFM_LAUNCH(sum_partials_scaled_kernel, dim3(1), dim3(256), 0, s, (const double*)part, nblk, 1, 1.0 / ((double)B * H * W), 0.0,
-                 loss_sum, loss_mean);
+    PNSFM_LAUNCH(sum_partials_scaled_kernel, dim3(1), dim3(256), 0, s, (const double*)part, sum_tab(1, nblk, 1.0 / ((double)B * H * W), 0.0),
+                 1, loss_sum, loss_mean);
   else
     PNSFM_LAUNCH(sum_partials_kernel, dim3(1), dim3(256), 0, s, (const double*)part, nblk, 1, loss_sum);
   return check_launch("photometric_forward");
 }
 
+static bool photometric_ms_args(const char* what, int n, int J, int B, int H, int W, float ssim_weight, int automask, int reduce_op) {
+  if (n < 1 || n > MS_MAX) { set_error("%s: n must be 1..%d scales (got %d)", what, MS_MAX, n); return false; }
+  if (J < 1 || J > 3 || B < 1 || H < 3 || W < 3) { set_error("%s: bad shape (J=%d B=%d H=%d W=%d; J<=3)", what, J, B, H, W); return false; }
+  if (!(ssim_weight >= 0.f) || (ssim_weight == 0.f && reduce_op == 0)) {
+    set_error("%s: ssim_weight must be > 0 (or == 0 with the 'mean' reduce op)", what);
+    return false;
+  }
+  if (automask && reduce_op != 0) { set_error("%s: automask requires the 'min' reduce op", what); return false; }
+  return true;
+}
+
+int pnsfm_photometric_identity_forward(const float* ref, const float* target, float* id, int J, int B, int H, int W, float ssim_weight,
+                                       float C1, float C2, void* stream) {
+  if (!photometric_ms_args("photometric_identity_forward", 1, J, B, H, W, ssim_weight, 1, 0)) return -1;
+  if (!ref || !target || !id) { set_error("photometric_identity_forward: null pointer"); return -1; }
+  dim3 grid(ceil_div(W, PH_T), ceil_div(H, PH_T), J * B);
+  PNSFM_LAUNCH(photometric_identity_kernel, grid, dim3(256), (size_t)2 * 3 * PH_S1 * PH_S1 * sizeof(float), (hipStream_t)stream, ref, target,
+               id, B, H, W, ssim_weight, C1, C2);
+  return check_launch("photometric_identity_forward");
+}
+
+int pnsfm_photometric_forward_ms(const float* warped, const float* id, const float* target, float* loss_mean, uint8_t* argmin, int n,
+                                 int J, int B, int H, int W, float ssim_weight, float C1, float C2, int automask, int reduce_op,
+                                 void* stream) {
+  if (!photometric_ms_args("photometric_forward_ms", n, J, B, H, W, ssim_weight, automask, reduce_op)) return -1;
+  if (!warped || !target || !loss_mean || !argmin) { set_error("photometric_forward_ms: null pointer"); return -1; }
+  if (automask && !id) { set_error("photometric_forward_ms: automask needs the identity map (pnsfm_photometric_identity_forward)"); return -1; }
+  hipStream_t s = (hipStream_t)stream;
+  dim3 grid(ceil_div(W, PH_T), ceil_div(H, PH_T), n * B);
+  const int nblk1 = (int)(grid.x * grid.y) * B;
+  ScratchLease lease(s, (size_t)n * nblk1 * sizeof(double));
+  double* part = lease.as<double>();
+  if (!part) return -1;
+  // without automask the kernel has no unwarped candidate: the two-slot layout of the per-scale form, reference slots left empty
+  const float* idmap = automask ? id : nullptr;
+  const size_t smem = (size_t)(1 + (idmap ? 1 : 2) * J) * 3 * PH_S1 * PH_S1 * sizeof(float);
+  PNSFM_LAUNCH(photometric_fwd_kernel, grid, dim3(256), smem, s, warped, warped, target, part, argmin, J, B, H, W,
+               ssim_weight, C1, C2, automask, reduce_op, (const float*)nullptr, (double*)nullptr, idmap, nblk1);
+  PNSFM_LAUNCH(sum_partials_scaled_kernel, dim3(n), dim3(256), 0, s, (const double*)part, sum_tab(n, nblk1, 1.0 / ((double)B * H * W), 0.0),
+               1, (double*)nullptr, loss_mean);
+  return check_launch("photometric_forward_ms");
+}
+
+static int photometric_backward_n(const float* warped, const float* target, const uint8_t* argmin, float* d_warped, float grad_scale,
+                                  const float* const* upstream, int n, int J, int B, int H, int W, float ssim_weight, float C1, float C2,
+                                  int automask, int reduce_op, int clip, void* stream) {
+  MsIn up;
+  if (!ms_table("photometric_backward", "upstream", upstream, n, up, true)) return -1;
+  if (J < 1 || J > 3 || B < 1 || H < 3 || W < 3) { set_error("photometric_backward: bad shape (J<=3)"); return -1; }
+  dim3 grid(ceil_div(W, PH_T), ceil_div(H, PH_T), n * B);
+  const size_t smem = ((size_t)(1 + J) * 3 * PH_S2 * PH_S2 + (size_t)J * 9 * PH_S1 * PH_S1) * sizeof(float);
+  PNSFM_LAUNCH(photometric_bwd_kernel, grid, dim3(256), smem, (hipStream_t)stream, warped, target, argmin, d_warped,
+               grad_scale, J, B, H, W, ssim_weight, C1, C2, automask, reduce_op, clip ? 1 : 0, up, (int)(grid.x * grid.y) * B);
+  return check_launch("photometric_backward");
+}
+
 int pnsfm_photometric_backward(const float* warped, const float* target, const uint8_t* argmin, float* d_warped,
                                float grad_scale, const float* upstream, int J, int B, int H, int W, float ssim_weight, float C1,
                                float C2, int automask, int reduce_op, int clip, void* stream) {
-  if (J < 1 || J > 3 || H < 3 || W < 3) { set_error("photometric_backward: bad shape (J<=3)"); return -1; }
-  dim3 grid(ceil_div(W, PH_T), ceil_div(H, PH_T), B);
-  const size_t smem = ((size_t)(1 + J) * 3 * PH_S2 * PH_S2 + (size_t)J * 9 * PH_S1 * PH_S1) * sizeof(float);
-  PNSFM_LAUNCH(photometric_bwd_kernel, grid, dim3(256), smem, (hipStream_t)stream, warped, target, argmin, d_warped,
-               grad_scale, J, B, H, W, ssim_weight, C1, C2, automask, reduce_op, clip ? 1 : 0, upstream);
-  return check_launch("photometric_backward");
+  return photometric_backward_n(warped, target, argmin, d_warped, grad_scale, &upstream, 1, J, B, H, W, ssim_weight, C1, C2,
+                                automask, reduce_op, clip, stream);
+}
+
+int pnsfm_photometric_backward_ms(const float* warped, const float* target, const uint8_t* argmin, float* d_warped, float grad_scale,
+                                  const float* const* upstream, int n, int J, int B, int H, int W, float ssim_weight, float C1, float C2,
+                                  int automask, int reduce_op, void* stream) {
+  if (!warped || !target || !argmin || !d_warped) { set_error("photometric_backward_ms: null pointer"); return -1; }
+  return photometric_backward_n(warped, target, argmin, d_warped, grad_scale, upstream, n, J, B, H, W, ssim_weight, C1, C2, automask,
+                                reduce_op, 0, stream);
 }
 
 int pnsfm_smoothness_forward(const float* inv_norm, const float* image, double* sums, int B, int H, int W, void* stream) {
@@ -919,8 +1191,8 @@ int pnsfm_photometric_l1_forward(const float* warped, const float* ref, const fl
   }
   PNSFM_LAUNCH(l1cand_fwd_kernel, grid, dim3(256), 0, s, warped, ref, target, clip ? (const float*)thr : (const float*)nullptr, part, rec,
                (double*)nullptr, J, B, H, W, automask, reduce_op);
-  PNSFM_LAUNCH(sum_partials_scaled_kernel, dim3(1), dim3(256), 0, s, (const double*)part, nblk, 1, 1.0 / ((double)B * H * W), 0.0,
-               (double*)nullptr, loss_mean);
+  PNSFM_LAUNCH(sum_partials_scaled_kernel, dim3(1), dim3(256), 0, s, (const double*)part, sum_tab(1, nblk, 1.0 / ((double)B * H * W), 0.0),
+               1, (double*)nullptr, loss_mean);
   return check_launch("photometric_l1_forward");
 }
 
@@ -932,35 +1204,93 @@ int pnsfm_photometric_l1_backward(const float* warped, const float* target, cons
   return check_launch("photometric_l1_backward");
 }
 
-int pnsfm_smoothness_norm_forward(const float* inv_depth, const float* image, float* loss, float* mean, int B, int H, int W,
-                                  void* stream) {
-  if (B < 1 || H < 2 || W < 2) { set_error("smoothness_norm_forward: bad shape"); return -1; }
+// the block-range table of n scales; false (error set) on a bad n, a null entry or a bad shape
+static bool sn_table(const char* what, const float* const* inv_depth, const float* const* image, const int* H, const int* W, int n,
+                     int B, SnTab& t, SumTab* sums = nullptr) {
+  MsIn inv, img;
+  if (!ms_table(what, "inv_depth", inv_depth, n, inv) || !ms_table(what, "image", image, n, img)) return false;
+  if (!H || !W) { set_error("%s: the table of heights or widths is null", what); return false; }
+  if (B < 1) { set_error("%s: bad shape", what); return false; }
+  t.n = n;
+  t.blk0[0] = 0;
+  for (int i = 0; i < MS_MAX; ++i) {
+    const bool on = i < n;
+    if (on && (H[i] < 2 || W[i] < 2)) { set_error("%s: bad shape (scale %d: H=%d W=%d)", what, i, H[i], W[i]); return false; }
+    t.inv[i] = inv.p[i];
+    t.img[i] = img.p[i];
+    t.H[i] = on ? H[i] : 0;
+    t.W[i] = on ? W[i] : 0;
+    const int nblk = on ? ceil_div(H[i] * W[i], 256) : 0;
+    t.blk0[i + 1] = t.blk0[i] + nblk;
+    const double nx = on ? (double)B * H[i] * (W[i] - 1) : 1.0, ny = on ? (double)B * (H[i] - 1) * W[i] : 1.0;
+    t.gx[i] = (float)(1.0 / nx);
+    t.gy[i] = (float)(1.0 / ny);
+    if (sums) {      // forward: the second stage of scale i
+      sums->off[i] = B * t.blk0[i];
+      sums->cnt[i] = B * nblk;
+      sums->s0[i] = 1.0 / nx;
+      sums->s1[i] = 1.0 / ny;
+    }
+  }
+  return true;
+}
+
+int pnsfm_smoothness_norm_forward_ms(const float* const* inv_depth, const float* const* image, const int* H, const int* W, int n,
+                                     float* loss, float* mean, int B, void* stream) {
+  SnTab t;
+  SumTab sums;
+  if (!sn_table("smoothness_norm_forward", inv_depth, image, H, W, n, B, t, &sums)) return -1;
+  if (!loss || !mean) { set_error("smoothness_norm_forward: null pointer"); return -1; }
   hipStream_t s = (hipStream_t)stream;
-  dim3 grid(ceil_div(H * W, 256), B);
+  dim3 grid(t.blk0[n], B);
   const int nblk = (int)(grid.x * grid.y);
   ScratchLease lease(s, (size_t)3 * nblk * sizeof(double));
   double* mpart = lease.as<double>();
   if (!mpart) return -1;
   double* part = mpart + nblk;
-  PNSFM_LAUNCH(sn_mean_kernel, grid, dim3(256), 0, s, inv_depth, mpart, H * W);
-  PNSFM_LAUNCH(sn_fwd_kernel, grid, dim3(256), 0, s, inv_depth, image, (const double*)mpart, part, mean, H, W);
-  PNSFM_LAUNCH(sum_partials_scaled_kernel, dim3(1), dim3(256), 0, s, (const double*)part, nblk, 2, 1.0 / ((double)B * H * (W - 1)),
-               1.0 / ((double)B * (H - 1) * W), (double*)nullptr, loss);
+  PNSFM_LAUNCH(sn_mean_kernel, grid, dim3(256), 0, s, t, mpart);
+  PNSFM_LAUNCH(sn_fwd_kernel, grid, dim3(256), 0, s, t, (const double*)mpart, part, mean);
+  PNSFM_LAUNCH(sum_partials_scaled_kernel, dim3(n), dim3(256), 0, s, (const double*)part, sums, 2, (double*)nullptr, loss);
   return check_launch("smoothness_norm_forward");
+}
+
+int pnsfm_smoothness_norm_forward(const float* inv_depth, const float* image, float* loss, float* mean, int B, int H, int W,
+                                  void* stream) {
+  return pnsfm_smoothness_norm_forward_ms(&inv_depth, &image, &H, &W, 1, loss, mean, B, stream);
+}
+
+int pnsfm_smoothness_norm_backward_ms(const float* const* inv_depth, const float* const* image, const int* H, const int* W, int n,
+                                      const float* mean, const float* const* upstream, float* const* d_inv_depth, int accumulate,
+                                      int B, void* stream) {
+  SnTab t;
+  MsIn up;
+  MsOut d_inv, g_n;
+  if (!sn_table("smoothness_norm_backward", inv_depth, image, H, W, n, B, t)) return -1;
+  if (!ms_table("smoothness_norm_backward", "upstream", upstream, n, up, true)) return -1;
+  if (!ms_table("smoothness_norm_backward", "d_inv_depth", d_inv_depth, n, d_inv)) return -1;
+  if (!mean) { set_error("smoothness_norm_backward: null pointer"); return -1; }
+  hipStream_t s = (hipStream_t)stream;
+  dim3 grid(t.blk0[n], B);
+  // scratch: the per-block partials of sum g_n d | accumulating: g_n of every scale (d_inv_depth holds the other term)
+  const size_t npart = (size_t)grid.x * grid.y;
+  size_t nfloat = 0;
+  for (int i = 0; i < n; ++i) nfloat += (size_t)B * t.H[i] * t.W[i];
+  ScratchLease lease(s, npart * sizeof(double) + (accumulate ? nfloat * sizeof(float) : 0));
+  double* part = lease.as<double>();
+  if (!part) return -1;
+  g_n = d_inv;
+  if (accumulate) {
+    float* f = reinterpret_cast<float*>(part + npart);
+    for (int i = 0; i < n; ++i) { g_n.p[i] = f; f += (size_t)B * t.H[i] * t.W[i]; }
+  }
+  PNSFM_LAUNCH(sn_bwd_kernel, grid, dim3(256), 0, s, t, mean, g_n, part);
+  PNSFM_LAUNCH(sn_bwd_apply_kernel, grid, dim3(256), 0, s, t, d_inv, g_n, mean, (const double*)part, up, accumulate ? 1 : 0);
+  return check_launch("smoothness_norm_backward");
 }
 
 int pnsfm_smoothness_norm_backward(const float* inv_depth, const float* image, const float* mean, const float* upstream,
                                    float* d_inv_depth, int B, int H, int W, void* stream) {
-  if (B < 1 || H < 2 || W < 2) { set_error("smoothness_norm_backward: bad shape"); return -1; }
-  hipStream_t s = (hipStream_t)stream;
-  dim3 grid(ceil_div(H * W, 256), B);
-  ScratchLease lease(s, (size_t)grid.x * grid.y * sizeof(double));
-  double* part = lease.as<double>();
-  if (!part) return -1;
-  PNSFM_LAUNCH(sn_bwd_kernel, grid, dim3(256), 0, s, inv_depth, image, mean, d_inv_depth, part, (float)(1.0 / ((double)B * H * (W - 1))),
-               (float)(1.0 / ((double)B * (H - 1) * W)), H, W);
-  PNSFM_LAUNCH(sn_bwd_apply_kernel, grid, dim3(256), 0, s, d_inv_depth, mean, (const double*)part, upstream, H * W);
-  return check_launch("smoothness_norm_backward");
+  return pnsfm_smoothness_norm_backward_ms(&inv_depth, &image, &H, &W, 1, mean, &upstream, &d_inv_depth, 0, B, stream);
 }
 
 int pnsfm_smoothness_backward(const float* inv_norm, const float* image, float* d_inv_norm, float gx, float gy, int B, int H,

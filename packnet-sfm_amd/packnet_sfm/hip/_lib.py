@@ -92,6 +92,14 @@ SIGNATURES = {
     "pnsfm_photometric_backward": (_i, [_p, _p, _p, _p, _f, _p, _i, _i, _i, _i, _f, _f, _f, _i, _i, _i, _p]),
     "pnsfm_smoothness_norm_forward": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
     "pnsfm_smoothness_norm_backward": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p]),
+    # all scales of the multi-view loss in one launch (tables: host arrays of device pointers / ints)
+    "pnsfm_view_synthesis_forward_ms": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "pnsfm_view_synthesis_backward_ms": (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "pnsfm_photometric_identity_forward": (_i, [_p, _p, _p, _i, _i, _i, _i, _f, _f, _f, _p]),
+    "pnsfm_photometric_forward_ms": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _f, _i, _i, _p]),
+    "pnsfm_photometric_backward_ms": (_i, [_p, _p, _p, _p, _f, _p, _i, _i, _i, _i, _i, _f, _f, _f, _i, _i, _p]),
+    "pnsfm_smoothness_norm_forward_ms": (_i, [_p, _p, _p, _p, _i, _p, _p, _i, _p]),
+    "pnsfm_smoothness_norm_backward_ms": (_i, [_p, _p, _p, _p, _i, _p, _p, _p, _i, _i, _p]),
     "pnsfm_region_ops": (_i, [_p, _i, _p]),
     # fp16 forward (evaluation / inference)
     "pnsfm_conv2d_packed_elems_h16": (_sz, [_i, _i, _i]),

@@ -2274,6 +2274,88 @@ def smoothness_norm(inv_depth, image):
     return SmoothnessNormFn.apply(inv_depth, image)
 
 
+# The scales of the multi-view loss in one launch per kernel (PNSFM_LOSS_MS=0 / set_loss_ms(False): one set of launches per scale, the
+# former path, the A/B switch and the reference of tests/loss_ms_cases.py).
+_LOSS_MS = os.environ.get('PNSFM_LOSS_MS', '1') != '0'
+_LOSS_MS_USED = [False]
+
+
+def set_loss_ms(on):
+    """Switch the all-scales loss node on or off; returns the previous setting."""
+    global _LOSS_MS
+    prev, _LOSS_MS = _LOSS_MS, bool(on)
+    return prev
+
+
+def loss_ms_used():
+    """Whether the last multiview_loss_terms call ran the all-scales node (False: the per-scale path)."""
+    return _LOSS_MS_USED[0]
+
+
+class MultiviewLossTermsFn(Function):
+    """The photometric and smoothness terms of n scales that share the context images, the target, the intrinsics and the poses (every
+    inverse-depth map at the image's resolution): view synthesis, photometric terms and smoothness of ALL scales, one launch per kernel,
+    the unwarped automask candidates evaluated once.  Outputs: the n photometric scalars, then (with_smooth) the n smoothness scalars,
+    0-dim views of two [n] tensors.  Backward returns every scale's complete d_inv_depth (photometric + smoothness term, summed in
+    the smoothness kernel) and the pose gradient summed over the scales inside the finish kernel.  Bit for bit the per-scale nodes'
+    results (csrc/loss.hip: the same kernels, a table of one scale)."""
+
+    @staticmethod
+    def forward(ctx, ref, target, K, refK, T, ssim_w, C1, C2, automask, reduce_op, padding_mode, with_smooth, *inv_depths):
+        ref, target, K, refK, T = (t.contiguous() for t in (ref, target, K, refK, T))
+        invs = [d.contiguous() for d in inv_depths]
+        n = len(invs)
+        J, B, _, H, W = ref.shape
+        warped = ops.view_synthesis_forward_ms(invs, ref, K, refK, T.detach(), padding_mode)
+        idmap = ops.photometric_identity_forward(ref, target, ssim_w, C1, C2) if automask else None
+        photo, argmin = ops.photometric_forward_ms(warped, idmap, target, ssim_w, C1, C2, automask, reduce_op)
+        outs = [photo[i] for i in range(n)]
+        mean = None
+        if with_smooth:
+            smooth, mean = ops.smoothness_norm_forward_ms(invs, [target] * n)
+            outs += [smooth[i] for i in range(n)]
+        ctx.save_for_backward(ref, target, K, refK, T, warped, argmin, mean, *invs)
+        ctx.meta = (ssim_w, C1, C2, automask, reduce_op, padding_mode, with_smooth, n, B * H * W)
+        ctx.set_materialize_grads(False)
+        return tuple(outs)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        ref, target, K, refK, T, warped, argmin, mean = ctx.saved_tensors[:8]
+        invs = list(ctx.saved_tensors[8:])
+        ssim_w, C1, C2, automask, reduce_op, padding_mode, with_smooth, n, npix = ctx.meta
+
+        def upstream(gs):      # a term nothing was computed from has no gradient: a zero scalar keeps the one launch
+            return [(g if g is not None else torch.zeros((), device=ref.device)).reshape(1).to(torch.float32).contiguous() for g in gs]
+
+        d_warped = ops.photometric_backward_ms(warped, target, argmin, 1.0 / npix, upstream(grads[:n]), ssim_w, C1, C2, automask,
+                                               reduce_op)
+        d_inv, dT = ops.view_synthesis_backward_ms(d_warped, invs, ref, K, refK, T.detach(), padding_mode)
+        d_invs = [d_inv[i] for i in range(n)]
+        if with_smooth:
+            ops.smoothness_norm_backward_ms(invs, [target] * n, mean, upstream(grads[n:2 * n]), d_invs)
+        return (None, None, None, None, dT) + (None,) * 7 + tuple(d_invs)
+
+
+def multiview_loss_terms(inv_depths, refs, image, K, refK, T, ssim_w, C1, C2, automask, reduce_op, clip_loss=0.0,
+                         padding_mode='zeros', with_smooth=True):
+    """(photometric, smoothness): two lists of n 0-dim tensors (smoothness empty without with_smooth) for loss_combine, or None
+    where the all-scales node does not apply -- the switch is off, a scale is not at the image's resolution, clipping is on, or the
+    configuration takes the L1-only kernels -- and the caller runs the per-scale path.  loss_ms_used() reports which."""
+    if padding_mode not in ops.PADDING_MODES:
+        raise ValueError('Unknown padding_mode {}'.format(padding_mode))
+    n = len(inv_depths)
+    ok = (_LOSS_MS and 1 <= n <= ops.LOSS_MAX_SCALES and clip_loss <= 0.0 and not (ssim_w == 0.0 and reduce_op == REDUCE_MIN)
+          and all(tuple(d.shape[-2:]) == tuple(image.shape[-2:]) for d in inv_depths))
+    _LOSS_MS_USED[0] = bool(ok)
+    if not ok:
+        return None
+    outs = MultiviewLossTermsFn.apply(refs, image, K, refK, T, ssim_w, C1, C2, bool(automask), reduce_op,
+                                      ops.PADDING_MODES[padding_mode], bool(with_smooth), *inv_depths)
+    return list(outs[:n]), list(outs[n:])
+
+
 # ---- depth evaluation (include/pnsfm.h "depth evaluation"; csrc/depth_eval.h) ------------------------------------------------------
 # Forward only, like the fp16 forward: evaluation runs under torch.no_grad(); with a gradient-requiring input the result carries a
 # node whose backward raises, for fp32 and fp16 alike.

@@ -1022,6 +1022,131 @@ def smoothness_norm_backward(inv_depth, image, mean, upstream):
     return d
 
 
+# ---- all scales in one launch (include/pnsfm.h "all scales in one launch") ----
+LOSS_MAX_SCALES = 8      # PNSFM_LOSS_MAX_SCALES of include/pnsfm.h (the library refuses more: "n must be 1..8 scales")
+
+
+def _ptr_table(tensors):
+    """HOST array of the device pointers of `tensors` (None: null).  Lengths are not checked here: the library refuses n < 1 and
+    n > LOSS_MAX_SCALES (the smoothness wrappers, which need a first image for B and the device, refuse an empty list themselves)"""
+    return (ctypes.c_void_p * max(len(tensors), 1))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+def _upstream_table(upstream, n):
+    """the optional list of n float32 device scalars that a backward kernel multiplies each scale's gradient by"""
+    if upstream is None:
+        return None
+    if len(upstream) != n:
+        raise ValueError("need one upstream scalar per scale (got %d for %d scales)" % (len(upstream), n))
+    _chk(*upstream); _f32(*upstream)
+    return ctypes.byref(_ptr_table(upstream))
+
+
+def view_synthesis_forward_ms(inv_depths, ref, K, refK, T, padding_mode=0):
+    """inv_depths: n x [B,1,H,W] -> warped [n,J,B,3,H,W], one launch."""
+    _chk(ref, K, refK, T, *inv_depths); _f32(ref, K, refK, T, *inv_depths)
+    J, B, _, H, W = ref.shape
+    n = len(inv_depths)
+    warped = torch.empty((max(n, 1),) + tuple(ref.shape), dtype=torch.float32, device=ref.device)
+    _lib.check(_lib.get().pnsfm_view_synthesis_forward_ms(ctypes.byref(_ptr_table(inv_depths)), n, _ptr(ref), _ptr(K), _ptr(refK), _ptr(T),
+                                                          _ptr(warped), J, B, H, W, int(padding_mode), _stream(ref)),
+               "view_synthesis_forward_ms")
+    return warped
+
+
+def view_synthesis_backward_ms(d_warped, inv_depths, ref, K, refK, T, padding_mode=0):
+    """d_warped [n,J,B,3,H,W] -> (d_inv [n,B,1,H,W], dT [J,B,4,4] summed over the scales), two launches."""
+    _chk(d_warped, ref, K, refK, T, *inv_depths); _f32(d_warped, ref, K, refK, T, *inv_depths)
+    J, B, _, H, W = ref.shape
+    n = len(inv_depths)
+    d_inv = torch.empty((max(n, 1), B, 1, H, W), dtype=torch.float32, device=ref.device)
+    dT = torch.empty_like(T)
+    _lib.check(_lib.get().pnsfm_view_synthesis_backward_ms(_ptr(d_warped), ctypes.byref(_ptr_table(inv_depths)), n, _ptr(ref), _ptr(K),
+                                                           _ptr(refK), _ptr(T), ctypes.byref(_ptr_table([d_inv[i] for i in range(n)])),
+                                                           _ptr(dT), J, B, H, W, int(padding_mode), _stream(ref)),
+               "view_synthesis_backward_ms")
+    return d_inv, dT
+
+
+def photometric_identity_forward(ref, target, ssim_weight, C1, C2):
+    """-> id [J,B,H,W]: the per-pixel loss of the unwarped candidates ref[j] against target."""
+    _chk(ref, target); _f32(ref, target)
+    J, B, _, H, W = ref.shape
+    idmap = torch.empty((J, B, H, W), dtype=torch.float32, device=ref.device)
+    _lib.check(_lib.get().pnsfm_photometric_identity_forward(_ptr(ref), _ptr(target), _ptr(idmap), J, B, H, W, float(ssim_weight),
+                                                             float(C1), float(C2), _stream(ref)), "photometric_identity_forward")
+    return idmap
+
+
+def photometric_forward_ms(warped, idmap, target, ssim_weight, C1, C2, automask, reduce_op):
+    """warped [n,J,B,3,H,W] -> (loss float32[n], argmin uint8[n,B,H,W]); idmap: photometric_identity_forward's, needed under automask."""
+    _chk(warped, idmap, target); _f32(warped, idmap, target)
+    n, J, B, _, H, W = warped.shape
+    loss = torch.empty((n,), dtype=torch.float32, device=warped.device)
+    argmin = torch.empty((n, B, H, W), dtype=torch.uint8, device=warped.device)
+    _lib.check(_lib.get().pnsfm_photometric_forward_ms(_ptr(warped), _ptr(idmap), _ptr(target), _ptr(loss), _ptr(argmin), n, J, B, H, W,
+                                                       float(ssim_weight), float(C1), float(C2), int(automask), int(reduce_op),
+                                                       _stream(warped)), "photometric_forward_ms")
+    return loss, argmin
+
+
+def photometric_backward_ms(warped, target, argmin, grad_scale, upstream, ssim_weight, C1, C2, automask, reduce_op):
+    """d_warped [n,J,B,3,H,W]; upstream: list of n float32 device scalars (or None)."""
+    _chk(warped, target, argmin); _f32(warped, target)
+    n, J, B, _, H, W = warped.shape
+    d_warped = torch.empty_like(warped)
+    _lib.check(_lib.get().pnsfm_photometric_backward_ms(_ptr(warped), _ptr(target), _ptr(argmin), _ptr(d_warped), float(grad_scale),
+                                                        _upstream_table(upstream, n), n, J, B, H, W, float(ssim_weight), float(C1),
+                                                        float(C2), int(automask), int(reduce_op), _stream(warped)),
+               "photometric_backward_ms")
+    return d_warped
+
+
+def _sn_tables(inv_depths, images):
+    n = len(inv_depths)
+    if n < 1:
+        raise ValueError("smoothness_norm: needs at least one scale")
+    if len(images) != n:
+        raise ValueError("need one image per inverse-depth map (got %d for %d)" % (len(images), n))
+    _chk(*inv_depths, *images); _f32(*inv_depths, *images)
+    B = images[0].shape[0]
+    for d, im in zip(inv_depths, images):
+        if tuple(im.shape) != (B, 3) + tuple(d.shape[-2:]) or tuple(d.shape[:2]) != (B, 1):
+            raise ValueError("smoothness_norm: inverse depth %s does not go with image %s" % (tuple(d.shape), tuple(im.shape)))
+    Hs = (ctypes.c_int * n)(*[d.shape[-2] for d in inv_depths])
+    Ws = (ctypes.c_int * n)(*[d.shape[-1] for d in inv_depths])
+    return n, B, ctypes.byref(_ptr_table(inv_depths)), ctypes.byref(_ptr_table(images)), ctypes.byref(Hs), ctypes.byref(Ws)
+
+
+def smoothness_norm_forward_ms(inv_depths, images):
+    """n scales, each at its own resolution -> (loss float32[n], mean float32[n,B]), three launches."""
+    n, B, pi, pim, pH, pW = _sn_tables(inv_depths, images)
+    dev = images[0].device
+    loss = torch.empty((max(n, 1),), dtype=torch.float32, device=dev)
+    mean = torch.empty((max(n, 1), B), dtype=torch.float32, device=dev)
+    _lib.check(_lib.get().pnsfm_smoothness_norm_forward_ms(pi, pim, pH, pW, n, _ptr(loss), _ptr(mean), B, _stream(images[0])),
+               "smoothness_norm_forward_ms")
+    return loss, mean
+
+
+def smoothness_norm_backward_ms(inv_depths, images, mean, upstream, d_inv=None):
+    """-> the list of n gradients.  d_inv: optional list of n tensors that hold another term of the gradient; the smoothness term is
+    then ADDED to them in place (one rounded sum per element) and they are returned."""
+    n, B, pi, pim, pH, pW = _sn_tables(inv_depths, images)
+    _chk(mean); _f32(mean)
+    acc = d_inv is not None
+    if acc:
+        _chk(*d_inv); _f32(*d_inv)
+        if len(d_inv) != n or any(g.shape != d.shape for g, d in zip(d_inv, inv_depths)):
+            raise ValueError("smoothness_norm_backward_ms: d_inv must match the inverse-depth maps")
+    else:
+        d_inv = [torch.empty_like(d) for d in inv_depths]
+    _lib.check(_lib.get().pnsfm_smoothness_norm_backward_ms(pi, pim, pH, pW, n, _ptr(mean), _upstream_table(upstream, n),
+                                                            ctypes.byref(_ptr_table(d_inv)), int(acc), B, _stream(images[0])),
+               "smoothness_norm_backward_ms")
+    return list(d_inv)
+
+
 def smoothness_forward(inv_norm, image):
     _chk(inv_norm, image); _f32(inv_norm, image)
     B, _, H, W = image.shape

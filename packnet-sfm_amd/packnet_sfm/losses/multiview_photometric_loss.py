@@ -74,6 +74,14 @@ class MultiViewPhotometricLoss(LossBase):
         K32, rK32 = K.float(), ref_K.float()
         reduce_op = HF.REDUCE_MIN if self.photometric_reduce_op == 'min' else HF.REDUCE_MEAN
 
+        # every scale at the image's resolution (upsample_depth_maps, the default): the scales share refs, target, K and T, and the
+        # terms of all of them come from one launch per kernel (HF.multiview_loss_terms; None: the per-scale path below)
+        terms = HF.multiview_loss_terms(list(inv_depths[:n]), refs_full, image, K32.contiguous(), rK32.contiguous(), T,
+                                        self.ssim_loss_weight, self.C1, self.C2, bool(self.automask_loss), reduce_op,
+                                        float(self.clip_loss), self.padding_mode, with_smooth=self.smooth_loss_weight > 0.0)
+        if terms is not None:
+            return self._combine(*terms)
+
         photometric, smoothness = [], []
         for i in range(n):
             h, w = inv_depths[i].shape[-2:]
@@ -90,6 +98,9 @@ class MultiViewPhotometricLoss(LossBase):
         if self.smooth_loss_weight > 0.0:
             # (mean normalisation of the inverse depth, reference :269-271, fused into the kernels)
             smoothness = [HF.smoothness_norm(inv_depths[i], images[i]) for i in range(n)]
+        return self._combine(photometric, smoothness)
+
+    def _combine(self, photometric, smoothness):
         # loss = mean_i photometric[i] + weight * mean_i (smoothness[i] / 2^i): the reference's Python sums of 0-dim tensors
         # (:248-252, :275-280, :337-338) as one launch over the 2n device scalars, same operation order
         loss, smoothness_loss, _photometric_only = HF.loss_combine(photometric, smoothness, self.smooth_loss_weight)
